@@ -5,11 +5,15 @@ Workload (BASELINE.json configs[1]): SD1.5 UNet fp16 + PPOScheduler (order 4, CF
 prompts per GPU, 8 solver steps, synthetic seeded weights / prompt embeddings / noise (no
 checkpoints exist offline).  A "step" of this bench = one full 8-step generation of one batch
 (8 CFG dual-batch UNet forwards at effective batch 32 + 8 fused solver updates); the unit of the
-metric is one image's final latents ("latent-images/s", the roofline numerator).  The VAE
-decode to 512x512 pixels (decode_latents, utils.py:6-34) is the step after the path:
-it is timed in a second, separate K-step loop and reported as "pixel_images_per_s" (latents + decode).
+metric is one image's final latents ("latent-images/s", the roofline numerator).
 
-Contract: python bench.py --gpus N --steps K --warmup W ; one JSON line on rank 0.
+Contract: python bench.py --gpus N --steps K --warmup W ; one JSON line on rank 0.  A plain run sets up,
+warms up, times the K steps and prints the line (headline, ms_per_step, the roofline of the timed
+forwards).  --dump-outputs DIR also writes the final latents of the last timed step as DIR/latents.npy
+(float32).  --full adds everything else the line has carried: the VAE decode to 512x512 pixels
+(decode_latents, utils.py:6-34) timed in a second K-step loop ("pixel_images_per_s"),
+the other residual-stream modes, the per-kernel profile, the measured ceilings, the other configurations
+(sub-records), the live PMC traffic, the power samples, the CPU baseline and the parity against it.
 Multi-GPU: one process per GPU (torch.distributed/RCCL only for the barrier and the max-over-ranks
 time); prompts are sharded with no data-path collective (gen_ppo.py:349-357) -> weak scaling.
 """
@@ -439,6 +443,30 @@ def extra_flux(dev, n=8):
     return rec
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, arrays, rank=None):
+    """`--dump-outputs DIR`: each array as DIR/<name>.npy (float32; float64 stays float64), for comparing two builds output for output.  The inputs
+    are the same on every run with the same arguments: seeded weights, prompt embeddings and noise, and the policy's action draws come from the default
+    CUDA generator, seeded before the warm-up.  Over 64 MB in all, each array keeps a fixed, seeded sample of its leading-dim rows
+    (sorted), and the row indices are written next to it as <name>_rows.npy."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    host = {k: v.detach().cpu().numpy() for k, v in arrays.items()}
+    host = {k: v if v.dtype == np.float64 else v.astype(np.float32) for k, v in host.items()}
+    total = sum(v.nbytes for v in host.values())
+    cost = total + sum(8 * v.shape[0] for v in host.values() if v.ndim > 0)      # (+ 8 bytes of row index per kept row)
+    suffix = "" if rank is None else f"_rank{rank}"
+    for k, v in host.items():
+        if total > DUMP_LIMIT_BYTES and v.ndim > 0 and v.shape[0] > 1:
+            keep = max(1, v.shape[0] * (DUMP_LIMIT_BYTES - 4096) // cost)     # (4 KB for the .npy headers)
+            rows = np.sort(np.random.default_rng(0).choice(v.shape[0], size=keep, replace=False))
+            np.save(os.path.join(dirname, f"{k}_rows{suffix}.npy"), rows.astype(np.float64))
+            v = v[rows]
+        np.save(os.path.join(dirname, f"{k}{suffix}.npy"), v)
+
+
 def dry_run(args):
     """`--dry-run`: everything bench.py does around the GPU work and nothing on a GPU -- the rendezvous (gloo instead of RCCL), the shard
     bounds, the start barrier, the max-over-ranks reduction and the one JSON line -- so that the N > 1 launch path can be exercised in the
@@ -473,9 +501,9 @@ def dry_run(args):
     per_rank = [{"rank": int(r[0]), "local_rank": int(r[1]), "device": int(r[2]), "images": int(r[3]), "elapsed_s": r[4],
                  "prompt_shard": [int(r[5]), int(r[6])], "latent_checksum": r[7], "host_id": int(r[8])} for r in rows]
     # what main() runs OUTSIDE the timed region on this launch: the cpu_baseline leg and the sub-record extras are N = 1 only (same conditions as in
-    # main()), so an 8-GPU timed region and its barriers see nothing but the sampling loop
-    side_work = {"cpu_baseline": world == 1 and not args.no_cpu_baseline, "extras": world == 1 and bool(args.extras),
-                 "ceilings": world == 1 and bool(args.ceilings), "kernel_profile_pass": rank == 0 and bool(args.profile_kernels)}
+    # main()), so an 8-GPU timed region and its barriers see nothing but the sampling loop; and all of it only under --full
+    side_work = {"cpu_baseline": args.full and world == 1 and not args.no_cpu_baseline, "extras": args.full and world == 1 and bool(args.extras),
+                 "ceilings": args.full and world == 1 and bool(args.ceilings), "kernel_profile_pass": args.full and rank == 0 and bool(args.profile_kernels)}
     if rank == 0:
         print(json.dumps({"dry_run": True, "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "scaling": "weak",
                           "images": B * world * args.steps, "max_elapsed_s": elapsed, "shards": bounds, "per_rank": per_rank,
@@ -513,7 +541,14 @@ def main():
     ap.add_argument("--force-dist", action="store_true", help="initialise the RCCL process group and run the N > 1 barrier / all_reduce(MAX) / per-rank all-gather "
                     "branch even at world size 1 (a one-GPU box exercising the exact code an 8-GPU launch runs; tests/test_engine_gpu.py)")
     ap.add_argument("--dry-run", action="store_true", help="exercise the launch / rendezvous / sharding / reduction path without touching a GPU")
+    ap.add_argument("--full", action="store_true", help="also run what the headline does not need (off by default): the decode loop, the other residual-stream "
+                    "modes, the per-kernel profile, the ceilings, the extras, the live traffic, the power samples, the CPU baseline and the parity; "
+                    "--decode / --ceilings / --profile-kernels / --extras / --traffic / --no-cpu-baseline select among them")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write the final latents of the last one as DIR/latents.npy "
+                    "(float32; N > 1: DIR/latents_rank<r>.npy per rank)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # plain `python bench.py --gpus N`: start the one-process-per-GPU job as a CHILD (nothing has touched the GPU yet) and pass its exit code on
@@ -567,8 +602,9 @@ def main():
         for p in sch.factor_net.parameters():      # seeded N(0, 0.5) policy (zero-init = uniform sampling), SURVEY 8(d)
             p.copy_(torch.randn(p.shape, generator=g) * 0.5)
     sch.factor_net.to(dev)
+    full = args.full
     vae, vae_sd = None, None
-    if args.decode:
+    if full and args.decode:
         vae = HipAutoencoderKL(device=dev)
         vae_sd = synthetic_vae_state_dict(vae.manifest(), seed=20251227)
         vae.load_state_dict(vae_sd)
@@ -587,6 +623,9 @@ def main():
     def one(output_type="latent"):
         return eng.generate(pe, ne, latents=noise, num_inference_steps=n, use_graph=bool(args.graph), output_type=output_type)
 
+    # the policy draws its actions from the default CUDA generator, which an unseeded process starts from a seed of its own: seeded here, so that the same
+    # arguments give the same draws, and the same latents, on every run (--dump-outputs)
+    torch.cuda.manual_seed(20251228)
     for _ in range(args.warmup):
         one()
     torch.cuda.synchronize()
@@ -594,7 +633,7 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     eng.forward_events = [] if not args.graph else None
-    power = PowerSampler(local).start() if rank == 0 else None      # (a host thread reading two sysfs files every 20 ms; rank 0 only)
+    power = PowerSampler(local).start() if full and rank == 0 else None      # (a host thread reading two sysfs files every 20 ms; rank 0 only)
     t0 = time.perf_counter()
     for _ in range(args.steps):
         out = one()
@@ -604,6 +643,9 @@ def main():
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     power = power.stop() if power is not None else None
+    if args.dump_outputs:
+        # the caller's result of the last timed step, copied before any later pass can reuse the engine's buffers
+        dump_outputs(args.dump_outputs, {"latents": out}, None if world == 1 else rank)
     elapsed_local = elapsed
     if dist is not None:
         tt = torch.tensor([elapsed], device=dev, dtype=torch.float64)
@@ -654,7 +696,7 @@ def main():
 
     # ---- second loop: the same K generations followed by the VAE decode (pixel images) ------------------------
     decode_ms = pixel_elapsed = None
-    if args.decode:
+    if vae is not None:                                     # (--full --decode 1)
         one("pt")                                           # untimed: workspace allocation
         torch.cuda.synchronize()
         if dist is not None:
@@ -722,7 +764,7 @@ def main():
                         "headline": True}}
     if sched:
         modes[head_key]["forwards_on_split_stream"] = f"{k_hi} of {n}"
-    if world == 1 and not args.graph and sched:
+    if full and world == 1 and not args.graph and sched:
         # the same K generations with EVERY forward on the split stream (round 5's headline configuration)
         eng.hi_precision_steps = "all"
         one(); torch.cuda.synchronize()
@@ -737,7 +779,7 @@ def main():
         eng.hi_precision_steps = hps
         assert torch.isfinite(o3).all()
         modes["f16x2"] = {"images_per_s": B * args.steps / el3, "unet_forward_ms": f3, "roofline_frac": flops_fwd / (f3 * 1e-3) / 1e12 / PEAK_F16_TFLOPS, "headline": False}
-    if world == 1 and not args.graph:
+    if full and world == 1 and not args.graph:
         unet.set_residual_precision(other_mode)
         one(); torch.cuda.synchronize()
         eng.forward_events = []
@@ -772,7 +814,7 @@ def main():
                      "tflops": round(v["flops"] / (v["ms"] * 1e-3) / 1e12, 1) if v["ms"] > 0 and v["flops"] > 0 else None,
                      "gbps": round(v["bytes"] / (v["ms"] * 1e-3) / 1e9, 1) if v["ms"] > 0 else None} for k, v in prof.items()},
                 sum(v["bytes"] for v in prof.values()))
-    if args.profile_kernels and rank == 0:
+    if full and args.profile_kernels and rank == 0:
         kernels, b_head = _profile_pass()
         if headline_mode == "f16":
             algo_bytes_one_plane = b_head
@@ -788,7 +830,7 @@ def main():
     # ---- same-run measured ceilings (makes the fraction of the spec-sheet peak auditable): what the vendor GEMM library and a
     # plain device copy reach on THIS box, on random data.  Reference points only - nothing on the product path uses hipBLASLt or torch math.
     ceilings = None
-    if rank == 0 and world == 1 and args.ceilings:
+    if full and rank == 0 and world == 1 and args.ceilings:
         def _ev(fn, it):
             for _ in range(3): fn()
             torch.cuda.synchronize()
@@ -828,7 +870,7 @@ def main():
 
     # ---- the other configurations of BASELINE.json, measured in the same driver-run process (sub-records; N = 1 only) -------------
     extras = None
-    if rank == 0 and world == 1 and args.extras:
+    if full and rank == 0 and world == 1 and args.extras:
         extras = {}
         for name, fn in (("four_step", lambda: extra_four_step(eng, unet, pe, ne, noise, args.guidance, max(2, args.steps))),
                          ("solver_k1", lambda: extra_solver(dev, sch)),
@@ -839,7 +881,7 @@ def main():
             except Exception as e:                      # a failing extra must not take the headline line down with it
                 extras[name] = {"error": f"{type(e).__name__}: {e}"}
 
-    if rank == 0 and world == 1 and args.traffic == "live" and eff_batch == 32:
+    if full and rank == 0 and world == 1 and args.traffic == "live" and eff_batch == 32:
         live, src = live_traffic(headline_mode)
         if live is not None and sched:
             # the schedule's forwards are of two kinds: measure the one-plane forward too and quote the per-launch MEAN of the mix the timed loop ran
@@ -883,7 +925,8 @@ def main():
             roofline["traffic_ratio"] = roofline["traffic"] / roofline["traffic_algorithmic_one_plane"]
         if extras:
             rec.update({k: v for k, v in extras.items() if v is not None})
-        rec["power_over_timed_region"] = power
+        if full:
+            rec["power_over_timed_region"] = power
         if ceilings:
             rec["ceilings"] = ceilings
             if ceilings.get("sustained_conv3_lw_64x64_320_tflops"):
@@ -891,7 +934,7 @@ def main():
                 rec["roofline"]["achieved_over_sustained_conv3_lw"] = achieved / ceilings["sustained_conv3_lw_64x64_320_tflops"]
                 rec["roofline"]["achieved_over_sustained_vendor_gemm"] = achieved / ceilings["sustained_vendor_gemm_f16_8192_tflops"]
             rec["roofline"]["frac_of_vendor_gemm"] = achieved / ceilings["vendor_gemm_f16_8192_tflops"]
-        if not args.no_cpu_baseline and world == 1:
+        if full and not args.no_cpu_baseline and world == 1:
             rec["cpu_baseline"] = cpu_baseline(sd, unet.config, n, args.guidance, vae_sd=vae_sd)
             # "latent L2 vs ref" (the metric's second half): the HIP engine on the inputs of the CPU leg, against the fp32 latents it just produced
             replay = rec["cpu_baseline"].pop("_replay")

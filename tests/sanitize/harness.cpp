@@ -1,5 +1,5 @@
 // Sanitizer harness for the HOST side of libconsolver_hip (the reference has no sanitizer story; this is ours).
-// Built by tests/test_sanitize_host.py with -fsanitize=address,undefined from the real unet.cpp / vae.cpp / flux.cpp / clip.cpp / ops_api.cpp / api.cpp
+// Built by tests/test_sanitize_host.py with -fsanitize=address,undefined -fno-gpu-sanitize from the real unet.cpp / vae.cpp / flux.cpp / clip.cpp / ops_api.cpp / api.cpp
 // plus tests/sanitize/stubs.cpp (host malloc as device memory, launch stubs that touch every tensor's first and last byte).  Drives, without a GPU:
 //   weight registration and repacking, finalize, the dry-run workspace sizing (every execution variant, both residual-stream modes), forwards through the
 //   first-fit arena with a workspace of EXACTLY the size the library asked for, the profiling event pool, and the error paths.

@@ -1,7 +1,7 @@
 // Host-only stand-ins for the sanitizer harness (tests/sanitize/harness.cpp; TEST INFRASTRUCTURE, never linked into libconsolver_hip.so).
 //
 // The executors (unet.cpp / vae.cpp / flux.cpp / clip.cpp / ops_api.cpp / api.cpp) are host code: weight repacking, a first-fit arena over the caller's
-// workspace, the dry-run workspace sizing and the launch sequence.  They are compiled here with -fsanitize=address,undefined (hipcc --cuda-host-only) and
+// workspace, the dry-run workspace sizing and the launch sequence.  They are compiled here with -fsanitize=address,undefined -fno-gpu-sanitize (hipcc --cuda-host-only) and
 // linked against THIS file instead of the HIP kernels and the HIP runtime:
 //   * "device" memory is host malloc, so AddressSanitizer sees every buffer the executors carve out of the workspace;
 //   * every launch_* stub TOUCHES the first and last byte of each tensor the real kernel would read or write (sizes from the launch arguments), so an

@@ -370,11 +370,11 @@ def test_pipeline_call_surface():
 
 @pytest.mark.gpu
 def test_bench_prints_one_contract_line():
-    """bench.py (N = 1, short) prints ONE JSON line with the driver's keys plus roofline / ceilings / cpu_baseline objects"""
+    """bench.py --full (N = 1, short) prints ONE JSON line with the driver's keys plus roofline / ceilings / cpu_baseline objects"""
     import json, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "1", "--decode", "0", "--extras", "0",
-                        "--no-cpu-baseline", "--profile-kernels", "0", "--traffic", "none", "--force-dist"], capture_output=True, text=True, timeout=900, cwd=root)
+                        "--no-cpu-baseline", "--profile-kernels", "0", "--traffic", "none", "--force-dist", "--full"], capture_output=True, text=True, timeout=900, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
@@ -395,3 +395,25 @@ def test_bench_prints_one_contract_line():
     assert abs(rf["achieved_executed"] / rf["achieved"] - rf["flops_executed_per_launch"] / rf["flops_per_launch"]) < 1e-9
     assert rec["ceilings"]["vendor_gemm_f16_8192_tflops"] > 100 and rec["ceilings"]["dtod_copy_1gib_tbps"] > 1.0
     assert rec["cpu_baseline"] is None          # --no-cpu-baseline
+
+
+def test_bench_plain_run_dumps_the_timed_latents(tmp_path):
+    """a plain bench.py run (no --full) times exactly --steps generations, prints the headline keys and none of the side work, and --dump-outputs
+    writes the final latents of the last timed step (float32, the engine's output shape, finite)"""
+    import json, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--dump-outputs", str(tmp_path)],
+                       capture_output=True, text=True, timeout=900, cwd=root)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    rec = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in rec, k
+    assert rec["steps"] == 2 and rec["warmup"] == 1 and rec["unit"] == "images/s" and rec["higher_is_better"] is True and rec["dtype"] == "f16"
+    assert abs(rec["value"] - 16 * 1e3 / rec["ms_per_step"]) < 1e-6 * rec["value"]
+    for k in ("ceilings", "cpu_baseline", "parity", "pixel_images_per_s", "roofline_kernels", "four_step", "flux_edit", "power_over_timed_region"):
+        assert rec.get(k) is None, k
+    assert sorted(os.listdir(tmp_path)) == ["latents.npy"]
+    lat = np.load(tmp_path / "latents.npy")
+    assert lat.dtype == np.float32 and lat.shape == (16, 4, 64, 64) and np.isfinite(lat).all() and lat.std() > 0.1

@@ -70,6 +70,30 @@ def test_two_process_gloo_launch(tmp_path):
     assert (tmp_path / "rank0.ok").read_text() == "ok" and (tmp_path / "rank1.ok").read_text() == "ok"
 
 
+def test_bench_dump_outputs_layout_and_cap(tmp_path):
+    """bench.py --dump-outputs: float32 .npy per output; over the 64 MB cap a fixed, seeded sample of leading-dim rows plus its row indices"""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    x = torch.randn(16, 4, 8, 8, dtype=torch.float16)
+    bench.dump_outputs(str(tmp_path / "a"), {"latents": x})
+    assert sorted(os.listdir(tmp_path / "a")) == ["latents.npy"]
+    got = np.load(tmp_path / "a" / "latents.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, x.float().numpy())
+    y = torch.randn(4096, 4, 64, 64)                     # 256 MB: over the cap
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), {"latents": y}, rank=1)
+    files = sorted(os.listdir(tmp_path / "b"))
+    assert files == ["latents_rank1.npy", "latents_rows_rank1.npy"]
+    assert sum(os.path.getsize(tmp_path / "b" / f) for f in files) <= 64 << 20
+    rows = np.load(tmp_path / "b" / "latents_rows_rank1.npy")
+    got = np.load(tmp_path / "b" / "latents_rank1.npy")
+    assert rows.dtype == np.float64 and len(rows) > 900 and np.all(np.diff(rows) > 0)
+    assert np.array_equal(got, y.numpy()[rows.astype(np.int64)])
+    assert np.array_equal(rows, np.load(tmp_path / "c" / "latents_rows_rank1.npy"))      # the same sample every run
+
+
 def test_bench_launcher_branch_dry_run():
     """`python bench.py --gpus 2 --dry-run`: bench.py's own child-launch branch (torch.distributed.run, one process per rank, 127.0.0.1
     rendezvous) + sharding + start barrier + max-over-ranks reduction + the single JSON line from rank 0, with gloo in place of RCCL and no
@@ -106,11 +130,14 @@ def test_bench_launcher_branch_dry_run():
         assert shards == [[r * per, (r + 1) * per if r < N - 1 else 16 * N] for r in range(N)], shards
         assert shards[0][0] == 0 and shards[-1][1] == 16 * N and all(a[1] == b[0] for a, b in zip(shards, shards[1:]))
         assert recN["n_gpus"] == N and recN["images"] == 16 * N and recN["per_rank_distinct_devices"] == N
-    # N = 1 takes the in-process path (no launcher)
-    r1 = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--dry-run"], capture_output=True, text=True, timeout=120, cwd=ROOT)
+    # N = 1 takes the in-process path (no launcher); the side work runs under --full only
+    r1 = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--dry-run", "--full"], capture_output=True, text=True, timeout=120, cwd=ROOT)
     rec1 = json.loads([l for l in r1.stdout.splitlines() if l.startswith("{")][0])
     assert rec1["n_gpus"] == 1 and rec1["shards"] == [[0, 16]] and len(rec1["per_rank"]) == 1
     assert rec1["side_work_after_timed_region"]["cpu_baseline"] is True and rec1["side_work_after_timed_region"]["extras"] is True
+    r0 = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--dry-run"], capture_output=True, text=True, timeout=120, cwd=ROOT)
+    rec0 = json.loads([l for l in r0.stdout.splitlines() if l.startswith("{")][0])
+    assert rec0["n_gpus"] == 1 and rec0["shards"] == [[0, 16]] and not any(rec0["side_work_after_timed_region"].values())
 
 
 GEN_WORKER = r'''

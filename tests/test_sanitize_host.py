@@ -1,7 +1,7 @@
 """AddressSanitizer + UndefinedBehaviorSanitizer run of the library's HOST side.
 
 The executors' host code -- weight repacking, the first-fit arena over the caller's workspace, the dry-run workspace sizing over all execution
-variants, the launch sequences -- is compiled from the real sources with ``-fsanitize=address,undefined`` (hipcc ``--cuda-host-only``: no device code,
+variants, the launch sequences -- is compiled from the real sources with ``-fsanitize=address,undefined -fno-gpu-sanitize`` (hipcc ``--cuda-host-only``: no device code,
 no GPU) and linked with tests/sanitize/stubs.cpp (host malloc stands in for device memory; every launch stub touches the first and last byte of each
 tensor the kernel would access).  tests/sanitize/harness.cpp then drives create -> set_weight -> finalize -> workspace_bytes -> forward through the
 arena with a workspace of exactly the requested size, in both residual-stream modes and every knob variant, plus the error paths.
@@ -30,7 +30,7 @@ def test_host_executors_under_asan_ubsan(tmp_path):
     hipcc = _hipcc()
     if hipcc is None:
         pytest.skip("hipcc not found")
-    flags = ["-x", "hip", "--cuda-host-only", "--offload-arch=gfx950", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined",
+    flags = ["-x", "hip", "--cuda-host-only", "--offload-arch=gfx950", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-gpu-sanitize",
              "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer", "-w", "-I" + os.path.join(ROOT, "include")]
     srcs = [os.path.join(CSRC, s) for s in HOST_SOURCES] + [os.path.join(ROOT, "tests", "sanitize", f) for f in ("stubs.cpp", "harness.cpp")]
     objs = []
@@ -43,7 +43,7 @@ def test_host_executors_under_asan_ubsan(tmp_path):
         out, _ = p.communicate()
         assert p.returncode == 0, f"{s}:\n{out}"
     exe = str(tmp_path / "harness")
-    r = subprocess.run([hipcc, "-fsanitize=address,undefined", "-o", exe] + objs, capture_output=True, text=True)
+    r = subprocess.run([hipcc, "-fsanitize=address,undefined", "-fno-gpu-sanitize", "-o", exe] + objs, capture_output=True, text=True)
     assert r.returncode == 0, r.stdout + r.stderr
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0:halt_on_error=1", UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
     r = subprocess.run([exe], capture_output=True, text=True, env=env, timeout=1200)
