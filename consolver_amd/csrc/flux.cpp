@@ -469,6 +469,8 @@ int cs_flux_forward(CsFlux* f, const void* hidden_states, int batch, int img_len
     if (f->cfg.guidance_embeds && !guidance) CS_FAIL(CS_E_ARG, "guidance is required (guidance_embeds)");
     if (img_len <= 0 || txt_len <= 0) CS_FAIL(CS_E_SHAPE, "sequence lengths must be positive");
     if (f->out_f32 && f->residual != CS_RESIDUAL_F16X2) CS_FAIL(CS_E_STATE, "flux: an fp32 output (cs_flux_set_output_dtype) is the split stream's (CS_RESIDUAL_F16X2)");
+    const TuneSet k = tune_snapshot();           // one knob set for the whole forward (ops.h, TuneSet)
+    TuneScope scope(&k);
     return flux_forward(f, false, hidden_states, batch, img_len, encoder_hidden_states, txt_len, pooled_f32, timestep, guidance, rope_cos, rope_sin, out,
                         (char*)workspace, workspace_bytes, (hipStream_t)stream);
 }
@@ -500,6 +502,8 @@ int cs_flux_forward_joint(CsFlux* f, const void* latents, int lat_len, const voi
     if (f->cfg.guidance_embeds && !guidance) CS_FAIL(CS_E_ARG, "guidance is required (guidance_embeds)");
     if (lat_len <= 0 || txt_len <= 0 || image_len < 0) CS_FAIL(CS_E_SHAPE, "sequence lengths must be positive");
     if (image_len > 0 && !image_latents) CS_FAIL(CS_E_ARG, "image_latents is NULL but image_len > 0");
+    const TuneSet k = tune_snapshot();
+    TuneScope scope(&k);
     return flux_forward(f, false, latents, batch, lat_len + image_len, encoder_hidden_states, txt_len, pooled_f32, timestep, guidance, rope_cos,
                         rope_sin, out, (char*)workspace, workspace_bytes, (hipStream_t)stream, image_len > 0 ? image_latents : nullptr, image_len);
 }

@@ -4,10 +4,11 @@
 #include "common.h"
 
 // ---- kernel-selection knobs (cs_set_tuning / cs_unet_set_tuning) -------------------------------------------------------------------------------------
-// One process-wide set (cs_set_tuning) and, for the duration of a host call that runs with per-handle overrides (cs_unet_forward on a handle with
-// cs_unet_set_tuning entries), a per-THREAD set: the call builds its own TuneSet (process-wide values + the handle's overrides) on its stack and installs a
-// pointer to it in `t_tune`; every launcher reads the knobs through tune().  Nothing writes the process-wide set on behalf of a handle, so another thread's
-// forward / op call never sees a handle's overrides, and forwards of different handles do not serialise on a lock.
+// One process-wide set (cs_set_tuning) and, for the duration of a model-level host call (cs_unet_* forwards and dry runs, cs_vae_decode / _encode,
+// cs_flux_forward / _joint), a per-THREAD set: the call takes one copy of the process-wide set (tune_snapshot), applies the handle's cs_unet_set_tuning
+// overrides to it where there are any, and installs a pointer to it in `t_tune` for the whole call.  The executor and every launcher then read that one set
+// (tune()), so a cs_set_tuning on another thread cannot change a call in flight, and nothing writes the process-wide set on behalf of a handle.  The op-level
+// cs_op_* entry points read the process-wide set directly.
 struct TuneSet {
     int halo = 1;           // conv3_halo_kernel use: 0 never, 1 when it pays, 2 whenever the shape allows (tests), 3 force the 320 / 256-wide form, 4 never the wide form
     int conv_lw = 1;        // 1: stride-1 3x3 convs with N % 160 == 0 or N % 128 == 0 through conv3_lw_kernel (loader waves), 2: the same without its immediate-offset (FAST) path, 3: N % 160 == 0 only, 0: the 8-wave halo kernels
@@ -58,6 +59,8 @@ struct TuneScope {                                  // RAII: install / remove a 
 };
 // key -> field of `set` (validated against the knob table: known key, value in range); CS_OK or CS_E_ARG with the error text set.  Writes only `set`.
 int tune_apply(TuneSet& set, const char* key, int value);
+// a copy of the process-wide set, taken under the lock its writers hold (ops_api.cpp)
+TuneSet tune_snapshot();
 
 struct IgemmArgs {
     // activations, NHWC fp16; up to two sources concatenated along channels (skip-concat fusion)
@@ -99,11 +102,23 @@ struct IgemmArgs {
     //   consumer: ln_stats (that buffer), ln_groups = G, ln_eps, ln_s, ln_b (fp32 [N]); w = W'; bias is ignored (b' holds it).  The row length is c0.
     float* row_stats; int* row_stats_groups;
     const float* ln_stats; int ln_groups; float ln_eps; const float* ln_s; const float* ln_b;
-    // optional (upsample != 0, 3x3): the filter in its sub-pixel form, [4][N][4 c0] from conv_up_fold_pack_host.  When given (and the shape fits: input 8 x 8 or a
-    // multiple of 16 x 16, N % 160 == 0, no residual / temb) the layer runs 16 instead of 36 multiplies per input pixel on pre-summed taps -- weights rounded to fp16
-    // once more, so the CALLER decides where that is acceptable (the UNet executor: one-plane forwards only, tune().up_fold).
+    // optional (upsample != 0, 3x3): the filter in its sub-pixel form, [4][N][4 c0] from conv_up_fold_pack_host.  When given (and igemm_sub_pixel holds) the layer
+    // runs 16 instead of 36 multiplies per input pixel on pre-summed taps -- weights rounded to fp16 once more, so the CALLER decides where that is acceptable
+    // (the UNet executor: one-plane forwards only, knob up_fold).
     const f16* w_up_sub;
 };
+// padding rows of conv3_lw_kernel: the chunk offset c * 128 B (c < LW_ZERO_CHUNKS) is added to every source, the zero source included, so the region spans
+// LW_ZERO_CHUNKS chunks + one 128-byte row + slack.  launch_igemm_impl sends Cin > 64 * LW_ZERO_CHUNKS (SD1.5 / VAE: <= 2560) to the halo kernels.
+constexpr int LW_ZERO_CHUNKS = 64;
+// launch_igemm runs `a` in the sub-pixel form (conv3_lw_kernel<.., SUB> on a.w_up_sub): the caller gave the filter and the shape fits -- input a multiple of
+// 16 x 16 with N % 160 == 0 or N % 128 == 0, or 8 x 8 with N % 160 == 0; one source of at most LW_ZERO_CHUNKS 64-channel chunks; no residual / temb / GEGLU --
+// under the knobs `t` (conv_lw on, no trace bit).  The one statement of that rule: the launcher chooses the kernel by it, the executors' FLOP counts ask it.
+inline bool igemm_sub_pixel(const IgemmArgs& a, const TuneSet& t) {
+    if (!(a.taps == 9 && a.upsample && a.w_up_sub && a.stride == 1 && a.c1 == 0 && !a.geglu && !a.res && !a.temb && a.Ho == 2 * a.Hi && a.Wo == 2 * a.Wi &&
+          a.c0 / 64 <= LW_ZERO_CHUNKS && t.conv_lw != 0 && !(t.debug & 16384)))
+        return false;
+    return (a.Hi % 16 == 0 && a.Wi % 16 == 0 && (a.N % 160 == 0 || a.N % 128 == 0)) || (a.Hi == 8 && a.Wi == 8 && a.N % 160 == 0);
+}
 int launch_igemm(const IgemmArgs& a, hipStream_t s);
 double igemm_flops(const IgemmArgs& a);
 void conv_up_fold_pack_host(const f16* w, int N, int Cin, f16* out);     // w [N][9 Cin] -> out [4][N][4 Cin]: the sub-pixel filters of IgemmArgs::w_up_sub

@@ -9,7 +9,7 @@ int debug_attn_trace_read(void* dst, size_t bytes);
 #include <mutex>
 TuneSet g_tune;
 thread_local const TuneSet* t_tune = nullptr;
-static std::mutex g_tune_write_mutex;      // writers of the process-wide set (cs_set_tuning / cs_reset_tuning); per-handle overrides never write it (ops.h, TuneSet)
+static std::mutex g_tune_write_mutex;      // writers of the process-wide set (cs_set_tuning / cs_reset_tuning) and tune_snapshot; per-handle overrides never write it (ops.h, TuneSet)
 
 // every kernel-selection knob: name, field, accepted range (or the two-value set {lo, hi} when `pair`); the defaults are TuneSet's member initialisers
 struct TuneKnob { const char* key; int TuneSet::* var; int lo, hi; bool pair; };
@@ -41,6 +41,11 @@ int tune_apply(TuneSet& set, const char* key, int value) {
             return CS_OK;
         }
     CS_FAIL(CS_E_ARG, "unknown tuning key '%s'", key);
+}
+
+TuneSet tune_snapshot() {
+    std::lock_guard<std::mutex> lock(g_tune_write_mutex);
+    return g_tune;
 }
 
 extern "C" {

@@ -354,24 +354,17 @@ bool make_xformer(CsUNet* u, const std::string& p, Xformer& x) {
 
 // ------------------------------------------------------------------------- run context
 struct Run {
-    CsUNet* u; hipStream_t s; bool dry; int B; int rc = CS_OK;
+    CsUNet* u;
+    const TuneSet& knobs;          // this call's knobs (run_forward installs the same set for the launchers)
+    hipStream_t s; bool dry; int B; int rc = CS_OK;
     const f16* ctx = nullptr; f16* kv = nullptr; const f16* tproj = nullptr; int tstride = 0;
     float* gn_ws = nullptr;
     float* sk_ws = nullptr; size_t sk_bytes = 0;
-    // execution variant, snapshotted from the process-wide knobs ONCE per forward (cs_set_tuning from another thread cannot change a forward in
-    // flight; the workspace query passes its variants here instead of writing the globals)
-    int v_gn_fuse = 1, v_xattn_fused = 1, v_cfg_share = 1;
     bool split = false;            // CS_RESIDUAL_F16X2: residual-stream tensors carry a lo plane
-    int v_split_a = 1;             // snapshot of tune().x2_split_a
-    int v_ln_fold = 1;             // snapshot of tune().ln_fold
-    int v_conv_in_mfma = 1;        // snapshot of tune().conv_in_mfma
-    int v_lo8 = 1;                 // snapshot of tune().lo8
-    int v_sc_skip = 0;             // snapshot of tune().x2_sc_skip
-    int v_up_fold = 1;             // snapshot of tune().up_fold
     // the transformer hidden state's lo plane as bytes: only where every consumer of that plane adds it (folded LayerNorms: ln_kernel reads an fp16 lo plane;
     // proj_out not reading hi + lo as its operand)
-    bool fold_of(const Xformer& X) const { return v_ln_fold != 0 && !((u->ln_unfold_mask >> X.index) & 1u); }
-    bool h_lo8(bool fold) const { return split && v_lo8 != 0 && fold && !(v_split_a & 2); }
+    bool fold_of(const Xformer& X) const { return knobs.ln_fold != 0 && !((u->ln_unfold_mask >> X.index) & 1u); }
+    bool h_lo8(bool fold) const { return split && knobs.lo8 != 0 && fold && !(knobs.x2_split_a & 2); }
     St salloc_h(size_t elems, bool fold) { St t; t.hi = alloc(elems); t.lo8 = h_lo8(fold); t.lo = split ? alloc(t.lo8 ? (elems + 1) / 2 : elems) : nullptr; return t; }
     float* calib = nullptr;        // calibration forward: per (block, LayerNorm) sums of mean^2 / var over the rows of the hidden state in front of that LayerNorm
     void calib_point(const Xformer& X, int which, const float* rs, int M, int G, int C, float eps) {
@@ -405,7 +398,7 @@ struct Run {
     // residual-stream tensors: hi plane (+ lo plane in the split mode)
     St salloc(size_t halfs) { St t; t.hi = alloc(halfs); t.lo = split ? alloc(halfs) : nullptr; return t; }
     void srelease(const St& t) { release(t.hi); u->arena.free(t.lo); }
-    bool stats_fusable(int HW, int C) const { return v_gn_fuse != 0 && HW % 64 == 0 && C % 2 == 0; }
+    bool stats_fusable(int HW, int C) const { return knobs.gn_fuse != 0 && HW % 64 == 0 && C % 2 == 0; }
     // partial-sum buffer for a [Bt][HW][C] tensor about to be produced (Bt samples); registered under `out` by the caller
     float* alloc_stats(int Bt, int HW, int C) { return (float*)alloc((size_t)Bt * (HW / 64) * C * 2); }      // C/2 pairs x 2 floats = C floats = 2C halfs
 
@@ -427,6 +420,12 @@ struct Run {
             rc = f();
         }
     }
+    // a device-to-device copy on the stream, under the same rule as a launch (none in a dry run or after an error); a failed one fails the forward
+    void copy(void* dst, const void* src, size_t bytes) {
+        if (dry || rc != CS_OK) return;
+        const hipError_t e = hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, s);
+        if (e != hipSuccess) { cs_set_error("unet: device copy of %zu B failed: %s", bytes, hipGetErrorString(e)); rc = CS_E_HIP; }
+    }
 
     // want_stats: the output feeds a GroupNorm (or a skip connection that does): its statistics come out of the epilogue.
     // stats_into: write them into this (larger) buffer instead of a fresh one, nothing registered (two launches filling one tensor).
@@ -446,15 +445,14 @@ struct Run {
         a.res_lo = res.lo; a.out_lo = out.lo; a.lo8 = lo8_of(res, out);
         a.splitk_ws = sk_ws; a.splitk_ws_bytes = sk_bytes;
         // an upsampler in its sub-pixel form: pre-summed taps are one more fp16 rounding of the weights (~2^-12 of the output, straight onto the stream):
-        // in the forwards that run on one fp16 plane, whose stream is rounded to fp16 sixty times anyway; the split stream keeps the exact filter
-        const bool sub = up && c.w_sub && (v_up_fold == 2 || (v_up_fold == 1 && !split)) && !res.hi && !temb && tune().conv_lw != 0 && !(tune().debug & 16384) &&
-                         ((Hi == 8 && Wi == 8) || (Hi % 16 == 0 && Wi % 16 == 0));      // (launch_igemm_impl's own conditions for the sub-pixel kernel: the executed-FLOP count follows them)
-        if (sub) a.w_up_sub = c.w_sub;
+        // in the forwards that run on one fp16 plane, whose stream is rounded to fp16 sixty times anyway; the split stream keeps the exact filter.
+        // Whether the shape takes that form is the launcher's rule (igemm_sub_pixel), which the executed-FLOP count asks too
+        if (up && c.w_sub && (knobs.up_fold == 2 || (knobs.up_fold == 1 && !split)) && !res.hi && !temb) a.w_up_sub = c.w_sub;
         const double M = (double)B * Ho * Wo;
         const double bytes = 2.0 * (M * (c0 + c1) + (double)c.cout * c.taps * (c0 + c1) + M * c.cout * ((res.hi ? 2 : 1) + (res.lo ? 1 : 0) + (out.lo ? 1 : 0)));
         // algo_flops: the REFERENCE graph's count for this layer where the executed form pads it (conv_in on the MFMA conv runs 64 input channels for 4):
         // cs_unet_flops is the algorithmic count of SURVEY 8(d), independent of how a layer is executed
-        launch(c.taps == 9 ? P_CONV3 : P_GEMM, (algo_flops >= 0 && !count_executed) ? algo_flops : igemm_flops(a) * ((count_executed && a.a0_lo) ? 2.0 : (count_executed && sub) ? 4.0 / 9.0 : 1.0), bytes, [&] { return launch_igemm(a, s); });
+        launch(c.taps == 9 ? P_CONV3 : P_GEMM, (algo_flops >= 0 && !count_executed) ? algo_flops : igemm_flops(a) * ((count_executed && a.a0_lo) ? 2.0 : (count_executed && igemm_sub_pixel(a, knobs)) ? 4.0 / 9.0 : 1.0), bytes, [&] { return launch_igemm(a, s); });
     }
     void linear(const f16* x, int M, int K, const f16* w, const f16* b, int N, St res, St out, int geglu, float* row_stats = nullptr, int* row_groups = nullptr) {
         IgemmArgs a{};
@@ -502,7 +500,7 @@ struct Run {
     // fused LN2 -> to_q -> cross attention -> to_out + residual (xattn.hip); h_in may equal h_out
     // (an UNFOLDED block -- cs_unet_calibrate_ln_fold: DC-heavy hidden state -- also leaves the fused kernel: its LayerNorm reads the hi plane, the LayerNorm kernel hi + lo)
     bool xattn_fusable(const Xformer& X, int HW) const {
-        return v_xattn_fused != 0 && X.c == 320 && u->cfg.num_heads == 8 && HW % 128 == 0 && u->cfg.ctx_len <= 80 && !((u->ln_unfold_mask >> X.index) & 1u);
+        return knobs.xattn_fused != 0 && X.c == 320 && u->cfg.num_heads == 8 && HW % 128 == 0 && u->cfg.ctx_len <= 80 && !((u->ln_unfold_mask >> X.index) & 1u);
     }
     void xattn_fused(const Xformer& X, St h_in, St h_out, const f16* kvl, int HW, float* row_stats = nullptr) {
         XattnArgs a{};
@@ -528,7 +526,7 @@ struct Run {
         St res = x;
         if (r.has_sc) {                                      // split mode: the 1x1 multiplies hi + lo of [x | skip] (two passes of its k loop over the same weights)
             // (x2_sc_skip: the shortcuts whose hi + lo operand buys the least per microsecond read the hi plane only -- tools/sim_precision_r06.py)
-            const bool sa = split && (v_split_a & 1) && !((v_sc_skip >> r.sc_index) & 1) && x.lo && (!cs || skip.lo);
+            const bool sa = split && (knobs.x2_split_a & 1) && !((knobs.x2_sc_skip >> r.sc_index) & 1) && x.lo && (!cs || skip.lo);
             conv(r.sc, x.hi, cx, skip.hi, cs, H, W, H, W, 1, 0, nullptr, St(), out, false, nullptr, sa ? x.lo : nullptr, sa ? skip.lo : nullptr);
             res = out;
         }
@@ -537,62 +535,87 @@ struct Run {
         return out;
     }
 
-    // in-place on a fresh output: returns new tensor [B,HW,C]
-    St xformer(const Xformer& X, St x, int H, int W) {
-        const int C = X.c, HW = H * W, L = u->cfg.ctx_len; const int M = B * HW;
-        f16* g = alloc((size_t)M * C);
+    // ---- transformer block; in-place on a fresh output: returns new tensor [B,HW,C] ----------------------------------------------------------------------
+    // CFG dual batch, shared prefix (n_share = n_lat > 0): with classifier-free guidance the two halves of the batch (unconditional | text,
+    // gen_pretrain/pipeline.py:1054) carry the SAME latents and the same timestep; they differ only in the text context, which first enters at the
+    // cross-attention of the first transformer block.  Everything before that point -- conv_in, the first resnet, and GroupNorm / proj_in / LayerNorm / QKV /
+    // self-attention / to_out / LayerNorm2 / to_q of the first transformer block -- is the same function of the same inputs for sample b and sample b + n_lat,
+    // so it is computed once at batch n_lat (x: ONE half) and the residual stream is duplicated right before the two halves diverge.  Bit-identical to running
+    // the full batch (the kernels are batch-independent per sample); ~1/32 of the forward's FLOPs are not executed.
+    // (The allocation sequence of each case is what cs_unet_workspace_bytes measured: the first-fit arena's peak depends on it.)
+    St xformer(const Xformer& X, St x, int H, int W, int n_share = 0) {
+        const int C = X.c, HW = H * W, L = u->cfg.ctx_len;
+        const int Bfull = B, Bp = n_share ? n_share : B, halves = n_share ? 2 : 1;     // Bp: the batch of the prefix and of each half's own launches
+        const int M = Bfull * HW, M1 = Bp * HW;
+        B = Bp;
+        f16* g = alloc((size_t)M1 * C);
         group_norm(X.gn, x, C, St(), 0, HW, false, g);
         // folded LayerNorms: every layer that writes the hidden state leaves its row statistics in rs (G column groups), the next LayerNorm's consumer reads them
         const bool fold = fold_of(X);
-        St h = salloc_h((size_t)M * C, fold);
-        float* rs = fold ? alloc_rowstats(M, C) : nullptr; int G = 1;
+        St h = salloc_h((size_t)M1 * C, fold);
+        float* rs = fold ? alloc_rowstats(M, C) : nullptr; int G = 1;                  // (full batch: the halves' statistics land side by side later)
         conv(X.proj_in, g, C, nullptr, 0, H, W, H, W, 1, 0, nullptr, St(), h, false, nullptr, nullptr, nullptr, rs, &G);
-        calib_point(X, 0, rs, M, G, C, X.ln1.eps);
+        calib_point(X, 0, rs, M1, G, C, X.ln1.eps);
         // self attention
-        f16* qkv = alloc((size_t)M * 3 * C);
-        if (fold) linear_ln(h.hi, M, C, X.f_qkv, rs, G, X.ln1.eps, 3 * C, qkv, 0);
-        else { layer_norm(X.ln1, h, M, g); linear(g, M, C, X.wqkv, nullptr, 3 * C, St(), St(qkv), 0); }
+        f16* qkv = alloc((size_t)M1 * 3 * C);
+        if (fold) linear_ln(h.hi, M1, C, X.f_qkv, rs, G, X.ln1.eps, 3 * C, qkv, 0);
+        else { layer_norm(X.ln1, h, M1, g); linear(g, M1, C, X.wqkv, nullptr, 3 * C, St(), St(qkv), 0); }
         attention(false, qkv, 3 * C, qkv + C, 3 * C, qkv + 2 * C, 3 * C, g, C, HW, HW, C);
         release(qkv);
-        linear(g, M, C, X.wo1, X.bo1, C, h, h, 0, rs, &G);
-        // cross attention (K/V of the text context are cached in kv)
-        const f16* kvl = kv + X.kv_off * (size_t)B * L;
-        if (xattn_fusable(X, HW)) {
-            xattn_fused(X, h, h, kvl, HW, rs); G = 1;        // (its own norm2 stays inside the kernel; it leaves the statistics norm3's consumer needs)
-        } else {
-            calib_point(X, 1, rs, M, G, C, X.ln2.eps);
-            f16* q = alloc((size_t)M * C);
-            if (fold) linear_ln(h.hi, M, C, X.f_q2, rs, G, X.ln2.eps, C, q, 0);
-            else { layer_norm(X.ln2, h, M, g); linear(g, M, C, X.wq2, nullptr, C, St(), St(q), 0); }
-            attention(true, q, C, kvl, 2 * C, kvl + C, 2 * C, g, C, HW, L, C);
-            release(q);
-            linear(g, M, C, X.wo2, X.bo2, C, h, h, 0, rs, &G);
+        linear(g, M1, C, X.wo1, X.bo1, C, h, h, 0, rs, &G);
+        // cross attention (K/V of the text context are cached in kv): the fused sub-block runs its own norm2 / to_q inside the kernel and leaves the statistics
+        // norm3's consumer needs; the unfused one runs to_q on the prefix
+        const bool fused = xattn_fusable(X, HW);
+        f16* q = nullptr;
+        if (!fused) {
+            calib_point(X, 1, rs, M1, G, C, X.ln2.eps);
+            q = alloc((size_t)M1 * C);
+            if (fold) linear_ln(h.hi, M1, C, X.f_q2, rs, G, X.ln2.eps, C, q, 0);
+            else { layer_norm(X.ln2, h, M1, g); linear(g, M1, C, X.wq2, nullptr, C, St(), St(q), 0); }
         }
+        // ---- the halves diverge: each half attends to its own K/V on its own copy of the residual stream (the fused sub-block reads the shared stream and
+        // writes each half's copy: no duplication copy)
+        const St hp = h;
+        if (n_share) { release(g); h = salloc_h((size_t)M * C, fold); g = alloc((size_t)M * C); }
+        const f16* kvl = kv + X.kv_off * (size_t)Bfull * L;
+        for (int half = 0; half < halves; ++half) {
+            const size_t o = (size_t)half * M1 * C;
+            const f16* kvh = kvl + (size_t)half * Bp * L * 2 * C;
+            if (fused) {
+                xattn_fused(X, hp, h.at(o), kvh, HW, rs ? rs + (size_t)half * M1 * 2 : nullptr);
+            } else {
+                if (n_share) { copy(h.hi + o, hp.hi, (size_t)M1 * C * sizeof(f16)); if (h.lo) copy(h.at(o).lo, hp.lo, (size_t)M1 * C * (h.lo8 ? 1 : sizeof(f16))); }
+                attention(true, q, C, kvh, 2 * C, kvh + C, 2 * C, g + o, C, HW, L, C);
+            }
+        }
+        if (q) release(q);
+        if (n_share) srelease(hp);
+        B = Bfull;
+        if (fused) G = 1;
+        else linear(g, M, C, X.wo2, X.bo2, C, h, h, 0, rs, &G);
         // feed forward (GEGLU fused into the first GEMM's epilogue)
         calib_point(X, 2, rs, M, G, C, X.ln3.eps);
         f16* ff = alloc((size_t)M * 4 * C);
         if (fold) linear_ln(h.hi, M, C, X.f_ff1, rs, G, X.ln3.eps, 8 * C, ff, 1);
         else { layer_norm(X.ln3, h, M, g); linear(g, M, C, X.wff1, X.bff1, 8 * C, St(), St(ff), 1); }
-        const bool po = split && (v_split_a & 2);
+        const bool po = split && (knobs.x2_split_a & 2);
         linear(ff, M, 4 * C, X.wff2, X.bff2, C, h, po ? h : St(h.hi), 0);      // the hidden after the feed-forward has one consumer, proj_out's operand: hi plane only unless proj_out reads hi + lo
         release(ff);
-        // proj_out + residual with the block input
+        // proj_out + residual with the block input, which exists once per half: one launch per half, one statistics buffer for the full batch
         St out(g, split ? alloc((size_t)M * C) : nullptr);
-        conv(X.proj_out, h.hi, C, nullptr, 0, H, W, H, W, 1, 0, nullptr, x, out, true, nullptr, po ? h.lo : nullptr);
+        float* st = stats_fusable(HW, C) ? alloc_stats(Bfull, HW, C) : nullptr;
+        B = Bp;
+        for (int half = 0; half < halves; ++half) {
+            const size_t o = (size_t)half * M1 * C;
+            conv(X.proj_out, h.hi + o, C, nullptr, 0, H, W, H, W, 1, 0, nullptr, x, out.at(o), false, st ? st + (size_t)half * Bp * (HW / 64) * C : nullptr,
+                 po ? h.lo + o : nullptr);
+        }
+        B = Bfull;
+        if (st) stat_of[g] = {st, HW / 64};
         srelease(h); u->arena.free(rs);
         return out;
     }
 };
-
-// ---- CFG dual batch, shared prefix --------------------------------------------------------------------------------------
-// With classifier-free guidance the two halves of the batch (unconditional | text, gen_pretrain/pipeline.py:1054) carry the SAME
-// latents and the same timestep; they differ only in the text context, which first enters at the cross-attention of the first
-// transformer block.  Everything before that point -- conv_in, the first resnet, and GroupNorm / proj_in / LayerNorm / QKV /
-// self-attention / to_out / LayerNorm2 / to_q of the first transformer block -- is the same function of the same inputs for sample
-// b and sample b + n_lat, so it is computed once at batch n_lat and the residual stream is duplicated right before the two halves
-// diverge.  Bit-identical to running the full batch (the kernels are batch-independent per sample); ~1/32 of the forward's FLOPs are
-// not executed.  `xformer_cfg_shared` is `xformer` with that split.
-St Run_xformer_cfg_shared(Run& R, const Xformer& X, St x_half, int H, int W, int n_lat);
 
 size_t kv_cache_bytes(const CsUNet* u, int B) { return ((u->kv_halfs_per_token * (size_t)B * u->cfg.ctx_len * sizeof(f16)) + 255) & ~(size_t)255; }
 size_t sk_ws_bytes(const CsUNet*, int B) { return ((size_t)B * (8u << 20)) + (16u << 20); }
@@ -601,83 +624,17 @@ size_t gn_ws_bytes(const CsUNet* u, int B) {
     return (((size_t)B * (GN_SPLITS + 1) * cmax * 2 * sizeof(float)) + 255) & ~(size_t)255;
 }
 
-St Run_xformer_cfg_shared(Run& R, const Xformer& X, St x_half, int H, int W, int n_lat) {
-    CsUNet* u = R.u;
-    const int C = X.c, HW = H * W, L = u->cfg.ctx_len;
-    const int Bfull = R.B, M1 = n_lat * HW, M = Bfull * HW;
-    // ---- shared part at batch n_lat ----
-    R.B = n_lat;
-    f16* g1 = R.alloc((size_t)M1 * C);
-    R.group_norm(X.gn, x_half, C, St(), 0, HW, false, g1);
-    const bool fold = R.fold_of(X);
-    St h1 = R.salloc_h((size_t)M1 * C, fold);
-    float* rs = fold ? R.alloc_rowstats(M, C) : nullptr; int G = 1;          // (sized for the full batch: the halves' statistics land side by side later)
-    R.conv(X.proj_in, g1, C, nullptr, 0, H, W, H, W, 1, 0, nullptr, St(), h1, false, nullptr, nullptr, nullptr, rs, &G);
-    R.calib_point(X, 0, rs, M1, G, C, X.ln1.eps);
-    f16* qkv = R.alloc((size_t)M1 * 3 * C);
-    if (fold) R.linear_ln(h1.hi, M1, C, X.f_qkv, rs, G, X.ln1.eps, 3 * C, qkv, 0);
-    else { R.layer_norm(X.ln1, h1, M1, g1); R.linear(g1, M1, C, X.wqkv, nullptr, 3 * C, St(), St(qkv), 0); }
-    R.attention(false, qkv, 3 * C, qkv + C, 3 * C, qkv + 2 * C, 3 * C, g1, C, HW, HW, C);
-    R.release(qkv);
-    R.linear(g1, M1, C, X.wo1, X.bo1, C, h1, h1, 0, rs, &G);
-    const f16* kvl = R.kv + X.kv_off * (size_t)Bfull * L;
-    St h; f16* g;
-    if (R.xattn_fusable(X, HW)) {
-        // the fused sub-block reads the shared residual stream and writes each half's own copy: no duplication copy, LN2 / to_q run per half
-        R.release(g1);
-        h = R.salloc_h((size_t)M * C, fold);
-        g = R.alloc((size_t)M * C);
-        for (int half = 0; half < 2; ++half)
-            R.xattn_fused(X, h1, h.at((size_t)half * M1 * C), kvl + (size_t)half * n_lat * L * 2 * C, HW, rs ? rs + (size_t)half * M1 * 2 : nullptr);
-        G = 1;
-        R.srelease(h1);
-        R.B = Bfull;
-    } else {
-        R.calib_point(X, 1, rs, M1, G, C, X.ln2.eps);
-        f16* q = R.alloc((size_t)M1 * C);
-        if (fold) R.linear_ln(h1.hi, M1, C, X.f_q2, rs, G, X.ln2.eps, C, q, 0);
-        else { R.layer_norm(X.ln2, h1, M1, g1); R.linear(g1, M1, C, X.wq2, nullptr, C, St(), St(q), 0); }
-        R.release(g1);
-        // ---- the halves diverge: cross attention against each half's own K/V, residual stream duplicated ----
-        h = R.salloc_h((size_t)M * C, fold);
-        g = R.alloc((size_t)M * C);
-        for (int half = 0; half < 2; ++half) {
-            if (!R.dry && R.rc == CS_OK) {
-                hipMemcpyAsync(h.hi + (size_t)half * M1 * C, h1.hi, (size_t)M1 * C * sizeof(f16), hipMemcpyDeviceToDevice, R.s);
-                if (h.lo) hipMemcpyAsync(h.at((size_t)half * M1 * C).lo, h1.lo, (size_t)M1 * C * (h.lo8 ? 1 : sizeof(f16)), hipMemcpyDeviceToDevice, R.s);
-            }
-            const f16* kvh = kvl + (size_t)half * n_lat * L * 2 * C;
-            R.attention(true, q, C, kvh, 2 * C, kvh + C, 2 * C, g + (size_t)half * M1 * C, C, HW, L, C);
-        }
-        R.release(q); R.srelease(h1);
-        R.B = Bfull;
-        R.linear(g, M, C, X.wo2, X.bo2, C, h, h, 0, rs, &G);
-    }
-    R.calib_point(X, 2, rs, M, G, C, X.ln3.eps);
-    f16* ff = R.alloc((size_t)M * 4 * C);
-    if (fold) R.linear_ln(h.hi, M, C, X.f_ff1, rs, G, X.ln3.eps, 8 * C, ff, 1);
-    else { R.layer_norm(X.ln3, h, M, g); R.linear(g, M, C, X.wff1, X.bff1, 8 * C, St(), St(ff), 1); }
-    const bool po = R.split && (R.v_split_a & 2);
-    R.linear(ff, M, 4 * C, X.wff2, X.bff2, C, h, po ? h : St(h.hi), 0);
-    R.release(ff);
-    // proj_out + residual with the block input, which exists once: one launch per half
-    St out(g, R.split ? R.alloc((size_t)M * C) : nullptr);
-    float* st = R.stats_fusable(HW, C) ? R.alloc_stats(Bfull, HW, C) : nullptr;     // one statistics buffer for the full batch, filled per half
-    R.B = n_lat;
-    for (int half = 0; half < 2; ++half)
-        R.conv(X.proj_out, h.hi + (size_t)half * M1 * C, C, nullptr, 0, H, W, H, W, 1, 0, nullptr, x_half, out.at((size_t)half * M1 * C), false,
-               st ? st + (size_t)half * n_lat * (HW / 64) * C : nullptr, po ? h.lo + (size_t)half * M1 * C : nullptr);
-    R.B = Bfull;
-    if (st) R.stat_of[g] = {st, HW / 64};
-    R.srelease(h); u->arena.free(rs);
-    return out;
+// the knobs one call of this handle runs with: one copy of the process-wide set, the handle's own overrides on top
+TuneSet handle_tune(const CsUNet* u) {
+    TuneSet k = tune_snapshot();
+    for (auto& kv : u->tune) tune_apply(k, kv.first.c_str(), kv.second);
+    return k;
 }
 
-struct Variant { int gn_fuse, xattn_fused, cfg_share, ln_fold, conv_in_mfma, lo8; };
-static Variant current_variant() { return Variant{tune().gn_fuse, tune().xattn_fused, tune().cfg_share, tune().ln_fold, tune().conv_in_mfma, tune().lo8}; }
-
-int run_forward(CsUNet* u, bool dry, const f16* latents, int n_lat, int dup, const float* t, int nt, const f16* ctx, f16* out,
-                char* ws, size_t ws_bytes, int kv_valid, hipStream_t s, Variant var = current_variant(), bool count_executed = false, float* calib = nullptr) {
+// k: the knobs of the whole forward, for the executor and (installed here) every launcher it calls
+int run_forward(CsUNet* u, const TuneSet& k, bool dry, const f16* latents, int n_lat, int dup, const float* t, int nt, const f16* ctx, f16* out,
+                char* ws, size_t ws_bytes, int kv_valid, hipStream_t s, bool count_executed = false, float* calib = nullptr) {
+    TuneScope scope(&k);
     const CsUNetConfig& c = u->cfg;
     const int B = n_lat * dup;
     const size_t kvb = kv_cache_bytes(u, B), gnb = gn_ws_bytes(u, B) + sk_ws_bytes(u, B);
@@ -685,10 +642,8 @@ int run_forward(CsUNet* u, bool dry, const f16* latents, int n_lat, int dup, con
     if (dry) ws = reinterpret_cast<char*>((uintptr_t)1 << 40);      // a base that is never dereferenced (offsets from a null pointer are undefined behaviour)
     u->arena.reset(ws + kvb + gnb, dry ? 0 : ws_bytes - kvb - gnb, dry);
     u->dry_flops = 0;
-    Run R{u, s, dry, B};
-    R.split = u->residual == CS_RESIDUAL_F16X2; R.v_split_a = tune().x2_split_a; R.count_executed = count_executed;
-    R.v_lo8 = var.lo8; R.v_sc_skip = tune().x2_sc_skip; R.v_up_fold = tune().up_fold; R.calib = dry ? nullptr : calib;
-    R.v_gn_fuse = var.gn_fuse; R.v_xattn_fused = var.xattn_fused; R.v_cfg_share = var.cfg_share; R.v_ln_fold = var.ln_fold; R.v_conv_in_mfma = var.conv_in_mfma;
+    Run R{u, k, s, dry, B};
+    R.split = u->residual == CS_RESIDUAL_F16X2; R.count_executed = count_executed; R.calib = dry ? nullptr : calib;
     R.ctx = ctx; R.kv = (f16*)ws; R.gn_ws = (float*)(ws + kvb);
     R.sk_ws = (float*)(ws + kvb + gn_ws_bytes(u, B)); R.sk_bytes = sk_ws_bytes(u, B);
     const int c0 = c.block_out_channels[0], td = 4 * c0, L = c.ctx_len;
@@ -718,8 +673,8 @@ int run_forward(CsUNet* u, bool dry, const f16* latents, int n_lat, int dup, con
     std::vector<std::pair<St, int>> skips;
     St h = R.salloc((size_t)B * H * W * c0);
     // CFG dual batch with one timestep: the first resnet and the first transformer block up to its cross attention are shared
-    const bool share = (dup == 2 && nt == 1 && c.down_has_attn[0] && R.v_cfg_share != 0 && !u->down_res[0].empty());
-    if (R.v_conv_in_mfma && c.in_channels <= 64 && (H * W) % 64 == 0) {
+    const bool share = (dup == 2 && nt == 1 && c.down_has_attn[0] && k.cfg_share != 0 && !u->down_res[0].empty());
+    if (k.conv_in_mfma && c.in_channels <= 64 && (H * W) % 64 == 0) {
         // latents -> NHWC-64 (n_lat samples), then the MFMA conv over them; the dual batch's second half is a copy (sample b reads latent b % n_lat)
         f16* z = R.alloc((size_t)n_lat * H * W * 64);
         R.launch(P_MISC, 0, 2.0 * n_lat * H * W * 64, [&] { return launch_latent_to_nhwc64(latents, nullptr, nullptr, z, n_lat, c.in_channels, H * W, 1.0f, 0.0f, s); });
@@ -732,15 +687,14 @@ int run_forward(CsUNet* u, bool dry, const f16* latents, int n_lat, int dup, con
                2.0 * Bkeep * H * W * 9.0 * c.in_channels * c0);      // (the graph's conv_in: 4 input channels, full batch -- as the conv_in_kernel branch counts it)
         R.B = Bkeep;
         R.release(z);
-        if (dup == 2 && !dry && R.rc == CS_OK) {
+        if (dup == 2) {
             const size_t half = (size_t)n_lat * H * W * c0;
             // (round 6 tried these three copies on a side stream -- forked here, joined in front of the last up resnet, their only full-batch reader: the forward got
             //  0.15 ms SLOWER, 29.35 -> 29.50 ms alternating on one box (profiles/r06_ab_copy_async.txt): a second queue's blit kernels take CU slots and bandwidth
             //  from the conv they run beside, and the fork / join events are not free.  In line they cost 30 us.)
-            hipStream_t cs = s;
-            hipMemcpyAsync(h.hi + half, h.hi, half * sizeof(f16), hipMemcpyDeviceToDevice, cs);
-            if (h.lo) hipMemcpyAsync(h.lo + half, h.lo, half * sizeof(f16), hipMemcpyDeviceToDevice, cs);
-            if (st) { const size_t sh = (size_t)n_lat * (H * W / 64) * c0; hipMemcpyAsync(st + sh, st, sh * sizeof(float), hipMemcpyDeviceToDevice, cs); }
+            R.copy(h.hi + half, h.hi, half * sizeof(f16));
+            if (h.lo) R.copy(h.lo + half, h.lo, half * sizeof(f16));
+            if (st) { const size_t sh = (size_t)n_lat * (H * W / 64) * c0; R.copy(st + sh, st, sh * sizeof(float)); }
         }
         if (st) R.stat_of[h.hi] = {st, H * W / 64};
     } else {
@@ -756,7 +710,7 @@ int run_forward(CsUNet* u, bool dry, const f16* latents, int n_lat, int dup, con
                 St r1 = R.resnet(u->down_res[0][0], h, ch, St(), 0, H, W);
                 R.B = B;
                 ch = u->down_res[0][0].cout;
-                r = Run_xformer_cfg_shared(R, u->down_att[0][0], r1, H, W, n_lat);
+                r = R.xformer(u->down_att[0][0], r1, H, W, n_lat);
                 R.srelease(r1);
             } else {
                 r = R.resnet(u->down_res[i][j], h, ch, St(), 0, H, W);
@@ -800,7 +754,7 @@ int run_forward(CsUNet* u, bool dry, const f16* latents, int n_lat, int dup, con
     // in front of eps (3.5 % of the per-forward error, tools/sim_precision_head.py).  Two planes, conv_out multiplies both: a second 25 us pass over the lo plane on top of
     // the first pass's fp32 result; the output (fp32 for the native engine, the model dtype for the plain protocol) is rounded from that once.
     const bool head2_shape = R.split && H % 16 == 0 && W % 16 == 0 && ch % 64 == 0;
-    const bool head2 = head2_shape && tune().head_x2 != 0 && tune().conv_out_mfma != 0;
+    const bool head2 = head2_shape && k.head_x2 != 0 && k.conv_out_mfma != 0;
     // (the workspace query -- dry -- reserves the head's lo plane and the 16-bit output's fp32 scratch whatever the knobs and the output dtype are at that moment)
     f16* n_lo = (head2 || (dry && head2_shape)) ? R.alloc((size_t)B * H * W * ch) : nullptr;
     float* head32 = ((head2 && u->out_dtype != CS_F32) || (dry && head2_shape)) ? (float*)R.alloc((size_t)B * H * W * c.out_channels * 2) : nullptr;
@@ -912,7 +866,7 @@ int cs_unet_finalize(CsUNet* u) {
         u->has_up[i] = i < 3;
         if (i < 3) {
             ok = ok && make_conv(u, b + ".upsamplers.0.conv", u->up_samp[i]);
-            // the same filter in its sub-pixel form (4 phases x 4 summed taps: 16 / 9 of the bytes), for the forwards that run on one fp16 plane (tune().up_fold)
+            // the same filter in its sub-pixel form (4 phases x 4 summed taps: 16 / 9 of the bytes), for the forwards that run on one fp16 plane (knob up_fold)
             Conv& uc = u->up_samp[i];
             if (ok && uc.taps == 9 && uc.cout % 160 == 0 && uc.cin % 64 == 0) {
                 std::vector<f16> sub((size_t)4 * uc.cout * 4 * uc.cin);
@@ -935,15 +889,19 @@ size_t cs_unet_workspace_bytes(const CsUNet* cu, int batch) {
     if (!u || !u->finalized || batch <= 0) return 0;
     // the arena's peak depends on the execution variant (CFG shared prefix on / off, fused cross-attention block on / off): the workspace
     // covers all of them, whatever the knobs say now, so that toggling a knob later never outgrows a workspace sized earlier
+    // (the knobs it does not enumerate come from the process-wide set)
+    const TuneSet base = tune_snapshot();
     size_t peak = 0;
     for (int variant = 0; variant < 32; ++variant) {         // (every knob that changes the allocation sequence: the first-fit arena's peak depends on the holes it leaves)
-        const Variant v{(variant >> 1) & 1, variant & 1, 1, (variant >> 2) & 1, (variant >> 3) & 1, variant >> 4};
-        run_forward(u, true, nullptr, batch, 1, nullptr, batch /* worst case: per-sample timesteps */, nullptr, nullptr, nullptr, 0, 0, nullptr, v);
+        TuneSet v = base;
+        v.xattn_fused = variant & 1; v.gn_fuse = (variant >> 1) & 1; v.ln_fold = (variant >> 2) & 1; v.conv_in_mfma = (variant >> 3) & 1; v.lo8 = variant >> 4;
+        v.cfg_share = 1;
+        run_forward(u, v, true, nullptr, batch, 1, nullptr, batch /* worst case: per-sample timesteps */, nullptr, nullptr, nullptr, 0, 0, nullptr);
         peak = std::max(peak, u->arena.peak);
         if (batch % 2 == 0) {
             for (int share = 0; share < 2; ++share) {          // (first-fit: the CFG dual batch with and without the shared prefix leaves different holes)
-                Variant vs = v; vs.cfg_share = share;
-                run_forward(u, true, nullptr, batch / 2, 2, nullptr, 1, nullptr, nullptr, nullptr, 0, 0, nullptr, vs);
+                v.cfg_share = share;
+                run_forward(u, v, true, nullptr, batch / 2, 2, nullptr, 1, nullptr, nullptr, nullptr, 0, 0, nullptr);
                 peak = std::max(peak, u->arena.peak);
             }
         }
@@ -954,17 +912,14 @@ size_t cs_unet_workspace_bytes(const CsUNet* cu, int batch) {
 double cs_unet_flops_executed(const CsUNet* cu, int n_lat, int dup) {
     CsUNet* u = const_cast<CsUNet*>(cu);
     if (!u || !u->finalized || n_lat <= 0 || (dup != 1 && dup != 2)) return 0;
-    TuneSet mine = g_tune;                                   // what THIS handle's forwards execute: its own knob overrides included
-    for (auto& kv : u->tune) tune_apply(mine, kv.first.c_str(), kv.second);
-    TuneScope scope(u->tune.empty() ? nullptr : &mine);
-    run_forward(u, true, nullptr, n_lat, dup, nullptr, 1, nullptr, nullptr, nullptr, 0, 0, nullptr, current_variant(), true);
+    run_forward(u, handle_tune(u), true, nullptr, n_lat, dup, nullptr, 1, nullptr, nullptr, nullptr, 0, 0, nullptr, true);     // (what THIS handle's forwards execute)
     return u->dry_flops;
 }
 
 double cs_unet_flops(const CsUNet* cu, int batch) {
     CsUNet* u = const_cast<CsUNet*>(cu);
     if (!u || !u->finalized || batch <= 0) return 0;
-    run_forward(u, true, nullptr, batch, 1, nullptr, 1, nullptr, nullptr, nullptr, 0, 0, nullptr);
+    run_forward(u, handle_tune(u), true, nullptr, batch, 1, nullptr, 1, nullptr, nullptr, nullptr, 0, 0, nullptr);
     return u->dry_flops;
 }
 
@@ -977,15 +932,8 @@ int cs_unet_forward(CsUNet* u, const void* latents, int n_lat, int dup, const fl
     if (!latents || !timesteps || !ctx || !out || !workspace) CS_FAIL(CS_E_ARG, "null pointer");
     if (n_timesteps != 1 && n_timesteps != n_lat * dup) CS_FAIL(CS_E_SHAPE, "n_timesteps must be 1 or the batch size");
     u->ev_used = 0;
-    // per-handle knob overrides: this call's own knob set (process-wide values + the handle's entries), visible to THIS thread's launchers only (ops.h, TuneSet)
-    TuneSet mine = g_tune;
-    for (auto& kv : u->tune) tune_apply(mine, kv.first.c_str(), kv.second);
-    int rc;
-    {
-        TuneScope scope(u->tune.empty() ? nullptr : &mine);
-        rc = run_forward(u, false, (const f16*)latents, n_lat, dup, timesteps, n_timesteps, (const f16*)ctx, (f16*)out, (char*)workspace,
-                         workspace_bytes, kv_cache_valid, (hipStream_t)stream);
-    }
+    const int rc = run_forward(u, handle_tune(u), false, (const f16*)latents, n_lat, dup, timesteps, n_timesteps, (const f16*)ctx, (f16*)out, (char*)workspace,
+                               workspace_bytes, kv_cache_valid, (hipStream_t)stream);
     if (rc == CS_OK && u->profiling) {
         CS_CHECK_HIP(hipStreamSynchronize((hipStream_t)stream));
         for (int k = 0; k < P_COUNT; ++k) { u->prof_ms[k] = u->prof_flops[k] = u->prof_bytes[k] = 0; u->prof_launches[k] = 0; }
@@ -1019,15 +967,10 @@ int cs_unet_calibrate_ln_fold(CsUNet* u, const void* latents, int n_lat, int dup
     u->ln_unfold_mask = 0;
     CS_CHECK_HIP(hipMemsetAsync(u->calib, 0, nslots * sizeof(float), s));
     u->ev_used = 0;
-    TuneSet mine = g_tune;
-    for (auto& kv : u->tune) tune_apply(mine, kv.first.c_str(), kv.second);
-    mine.ln_fold = 1; mine.cfg_share = 0;        // (every row of the batch through every statistics point)
-    int rc;
-    {
-        TuneScope scope(&mine);
-        rc = run_forward(u, false, (const f16*)latents, n_lat, dup, timesteps, n_timesteps, (const f16*)ctx, (f16*)out, (char*)workspace, workspace_bytes, 0, s,
-                         current_variant(), false, u->calib);
-    }
+    TuneSet k = handle_tune(u);
+    k.ln_fold = 1; k.cfg_share = 0;              // (every row of the batch through every statistics point)
+    const int rc = run_forward(u, k, false, (const f16*)latents, n_lat, dup, timesteps, n_timesteps, (const f16*)ctx, (f16*)out, (char*)workspace, workspace_bytes, 0, s,
+                               false, u->calib);
     if (rc != CS_OK) { u->ln_unfold_mask = keep; return rc; }
     std::vector<float> host(nslots);
     CS_CHECK_HIP(hipStreamSynchronize(s));

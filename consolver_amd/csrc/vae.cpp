@@ -178,16 +178,13 @@ struct Run {
     // normalised at most two convolutions after it was written (x -> conv1 -> conv2 (+ shortcut) -> next resnet)
     float* st_buf[3] = {nullptr, nullptr, nullptr}; const f16* st_of[3] = {nullptr, nullptr, nullptr}; int st_S[3] = {0, 0, 0}; int st_next = 0;
     size_t st_floats = 0;
-    // gn_fuse is snapshotted once per decode / encode (the process-wide knob cannot change a run in flight); the buffers are ALWAYS reserved, so the
-    // workspace size does not depend on the knob's value at query time
-    bool v_gn_fuse = true;
+    // (the buffers are reserved whatever gn_fuse says, so the workspace size does not depend on the knob's value at query time)
     void init_stats(size_t floats) {
-        v_gn_fuse = tune().gn_fuse != 0;
         st_floats = floats;
         for (auto& b : st_buf) b = (float*)alloc(floats * 2);           // (alloc counts halfs)
     }
     float* stats_for_output(const f16* out, int HW, int C) {
-        if (!v_gn_fuse || !st_buf[0] || HW % 64 || C % 2 || (size_t)B * (HW / 64) * C > st_floats) return nullptr;
+        if (!tune().gn_fuse || !st_buf[0] || HW % 64 || C % 2 || (size_t)B * (HW / 64) * C > st_floats) return nullptr;
         const int k = st_next; st_next = (st_next + 1) % 3;
         st_of[k] = out; st_S[k] = HW / 64;
         return st_buf[k];
@@ -211,8 +208,9 @@ struct Run {
         IgemmArgs a{};
         a.a0 = x; a.c0 = c.cin; a.B = B; a.Hi = H; a.Wi = W; a.Ho = up ? 2 * H : H; a.Wo = up ? 2 * W : W; a.taps = c.taps; a.stride = 1;
         a.upsample = up; a.N = c.cout; a.w = c.w; a.bias = c.b; a.res = res; a.out = out;
-        // the decoder's stream is one fp16 plane: its upsamplers run the sub-pixel form (16 instead of 36 multiplies per input pixel) unless up_fold is 0
-        if (up && c.w_sub && tune().up_fold != 0 && !res && H % 16 == 0 && W % 16 == 0) a.w_up_sub = c.w_sub;
+        // the decoder's stream is one fp16 plane: its upsamplers run the sub-pixel form (16 instead of 36 multiplies per input pixel, where the launcher's
+        // igemm_sub_pixel allows the shape) unless up_fold is 0
+        if (up && c.w_sub && tune().up_fold != 0 && !res) a.w_up_sub = c.w_sub;
         forget_stats(out);
         a.gn_stats = c.taps == 9 ? stats_for_output(out, a.Ho * a.Wo, c.cout) : nullptr;
         launch(igemm_flops(a), [&] { return launch_igemm(a, s); });             // (a kernel without a statistics epilogue is followed by a statistics pass in the same layout)
@@ -506,6 +504,8 @@ int cs_vae_decode(CsVae* v, const void* latents, int batch, float in_scale, floa
     if (batch < 0) CS_FAIL(CS_E_ARG, "negative batch");
     if (batch == 0) return CS_OK;
     if (!latents || !images || !workspace) CS_FAIL(CS_E_ARG, "null pointer");
+    const TuneSet k = tune_snapshot();           // one knob set for the whole decode (ops.h, TuneSet)
+    TuneScope scope(&k);
     return run_decode(v, false, (const f16*)latents, batch, in_scale, in_shift, (f16*)images, postprocess, (char*)workspace, workspace_bytes,
                       (hipStream_t)stream);
 }
@@ -525,6 +525,8 @@ int cs_vae_encode(CsVae* v, const void* images, int batch, float out_scale, floa
     if (batch < 0) CS_FAIL(CS_E_ARG, "negative batch");
     if (batch == 0) return CS_OK;
     if (!images || !latents || !workspace) CS_FAIL(CS_E_ARG, "null pointer");
+    const TuneSet k = tune_snapshot();
+    TuneScope scope(&k);
     return run_encode(v, false, (const f16*)images, batch, out_scale, out_shift, (f16*)latents, (char*)workspace, workspace_bytes, (hipStream_t)stream);
 }
 

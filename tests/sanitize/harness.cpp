@@ -11,6 +11,7 @@
 #include <string>
 #include <vector>
 
+extern "C" int g_stub_fail_memcpy_async;       // stubs.cpp
 static int g_fail = 0;
 #define EXPECT(cond) do { if (!(cond)) { fprintf(stderr, "FAIL %s:%d: %s  (last error: %s)\n", __FILE__, __LINE__, #cond, cs_last_error()); ++g_fail; } } while (0)
 
@@ -131,6 +132,23 @@ static void unet_part() {
         }
     }
     EXPECT(cs_unet_set_ln_unfold_mask(u, 0) == CS_OK);
+    // a failed device copy fails the forward: the CFG dual batch duplicates conv_in's output (conv_in_mfma) and, on the unfused cross-attention path, the
+    // shared prefix's residual stream; a half left uninitialised must not come back as CS_OK
+    for (int mode : {CS_RESIDUAL_F16, CS_RESIDUAL_F16X2}) {
+        EXPECT(cs_unet_set_residual_precision(u, mode) == CS_OK);
+        const size_t wsb = cs_unet_workspace_bytes(u, 2);
+        char* ws = (char*)malloc(wsb);
+        std::vector<char> lat(4 * S * S * 2), ctx(2 * 77 * 768 * 2), out(2 * 4 * S * S * 2); float t = 499.f;
+        for (bool prefix_copy_only : {false, true}) {
+            if (prefix_copy_only) EXPECT(cs_set_tuning("conv_in_mfma", 0) == CS_OK && cs_set_tuning("xattn_fused", 0) == CS_OK);
+            g_stub_fail_memcpy_async = 1;
+            EXPECT(cs_unet_forward(u, lat.data(), 1, 2, &t, 1, ctx.data(), out.data(), ws, wsb, 0, nullptr) == CS_E_HIP);
+            g_stub_fail_memcpy_async = 0;
+            EXPECT(cs_unet_forward(u, lat.data(), 1, 2, &t, 1, ctx.data(), out.data(), ws, wsb, 0, nullptr) == CS_OK);
+            EXPECT(cs_reset_tuning() == CS_OK);
+        }
+        free(ws);
+    }
     cs_unet_destroy(u);
     cs_unet_destroy(nullptr);
 }

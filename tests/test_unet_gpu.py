@@ -116,7 +116,7 @@ def test_full_sd15_unet_matches_oracle_cfg_batch():
 @pytest.mark.timeout(900)
 def test_cfg_shared_prefix_matches_full_dual_batch():
     """CFG dual batch (dup = 2, one timestep): the layers in front of the first cross attention are evaluated once for both
-    halves (unet.cpp `Run_xformer_cfg_shared`).  Same function of the same inputs -> the result must equal the full dual
+    halves (unet.cpp `Run::xformer` with `n_share`).  Same function of the same inputs -> the result must equal the full dual
     batch: bit for bit at the benchmark's shape (the per-sample kernels and their tile / split choices are the same at batch 16
     and 32), and to fp16 rounding on a reduced model where the smaller prefix batch may pick another split-K factor."""
     from consolver_amd import ops
