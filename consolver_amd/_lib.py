@@ -56,6 +56,12 @@ class CsClipConfig(C.Structure):
                 ("num_attention_heads", C.c_int), ("max_position_embeddings", C.c_int), ("layer_norm_eps", C.c_float)]
 
 
+class CsVitConfig(C.Structure):
+    _fields_ = [("hidden_size", C.c_int), ("num_hidden_layers", C.c_int), ("num_attention_heads", C.c_int), ("mlp_ratio", C.c_int),
+                ("image_size", C.c_int), ("patch_size", C.c_int), ("layer_norm_eps", C.c_float), ("resize_shortest_edge", C.c_int),
+                ("crop_size", C.c_int), ("image_mean", C.c_float * 3), ("image_std", C.c_float * 3), ("rescale_factor", C.c_double)]
+
+
 class CsGemm2Problem(C.Structure):
     _fields_ = [("x", C.c_void_p), ("M", C.c_int), ("K", C.c_int), ("w", C.c_void_p), ("bias", C.c_void_p), ("N", C.c_int),
                 ("res", C.c_void_p), ("gate", C.c_void_p), ("gate_stride", C.c_long), ("rows_per_sample", C.c_int), ("act", C.c_int),
@@ -101,6 +107,21 @@ SYMBOLS = {
     "cs_clip_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int]),
     "cs_clip_flops": (C.c_double, [C.c_void_p, C.c_int, C.c_int]),
     "cs_clip_encode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "cs_vit_create": (C.c_int, [C.POINTER(CsVitConfig), C.POINTER(C.c_void_p)]),
+    "cs_vit_destroy": (None, [C.c_void_p]),
+    "cs_vit_set_weight": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int]),
+    "cs_vit_num_weights": (C.c_int, [C.c_void_p]),
+    "cs_vit_weight_name": (C.c_char_p, [C.c_void_p, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int)]),
+    "cs_vit_finalize": (C.c_int, [C.c_void_p]),
+    "cs_vit_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int]),
+    "cs_vit_flops": (C.c_double, [C.c_void_p, C.c_int]),
+    "cs_vit_patch_cols": (C.c_int, [C.c_void_p]),
+    "cs_vit_num_tokens": (C.c_int, [C.c_void_p]),
+    "cs_vit_preprocess_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
+    "cs_vit_preprocess": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                    C.c_void_p]),
+    "cs_vit_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "cs_cosine_reward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p]),
     "cs_vae_create": (C.c_int, [C.POINTER(CsVaeConfig), C.POINTER(C.c_void_p)]),
     "cs_vae_destroy": (None, [C.c_void_p]),
     "cs_vae_set_weight": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int]),

@@ -29,6 +29,8 @@ SOURCES = {
     "unet.cpp": [],
     "vae.cpp": [],
     "clip.cpp": [],
+    "vit_ops.hip": [],
+    "vit.cpp": [],
     "ppo.hip": [],
     "ops_api.cpp": [],
 }

@@ -1,4 +1,4 @@
-// Fused (flash-style) attention forward for the SD1.5 head sizes 40 / 80 / 160 (+ 128 FLUX, + 64 causal CLIP) on gfx950.
+// Fused (flash-style) attention forward for the SD1.5 head sizes 40 / 80 / 160 (+ 128 FLUX, + 64: causal CLIP, biased T5, plain DINOv2) on gfx950.
 //
 //   out[b, q, h, :] = softmax(scale * Q K^T) V        (no mask; self and cross attention)
 //
@@ -1050,6 +1050,7 @@ int launch_attention(const AttnArgs& a, hipStream_t s) {
             if (qt == 4) return launch_attn<f16, 40, 4>(p, a.B, s);
             return launch_attn<f16, 40, 2>(p, a.B, s);
         }
+        case 64: if (a.dtype == CS_BF16) break; return launch_attn<f16, 64, 2>(p, a.B, s);      // DINOv2 encoder: unmasked, 257 tokens (ragged last key tile)
         case 80: if (a.dtype == CS_BF16) break; return launch_attn<f16, 80, 2>(p, a.B, s);
         case 160: if (a.dtype == CS_BF16) break; return launch_attn<f16, 160, 1>(p, a.B, s);
         case 128:
@@ -1057,5 +1058,5 @@ int launch_attention(const AttnArgs& a, hipStream_t s) {
             return launch_attn<f16, 128, 2>(p, a.B, s, a.split_ws, a.split_ws_bytes);
         default: break;
     }
-    CS_FAIL(CS_E_UNSUPPORTED, "attention: head dim %d / dtype %d not built (f16: 40/80/160/128, bf16: 128)", a.dh, a.dtype);
+    CS_FAIL(CS_E_UNSUPPORTED, "attention: head dim %d / dtype %d not built (f16: 40/64/80/160/128, bf16: 128)", a.dh, a.dtype);
 }

@@ -258,3 +258,25 @@ int launch_pixel_affine_nchw(const f16* x, int Cin, const f16* w, const f16* bia
 int launch_rms_norm(const void* x, const void* w, void* y, int M, int C, float eps, int dtype, hipStream_t s);
 int launch_gated_mul(const void* a, const void* b, void* out, long n, int dtype, hipStream_t s);
 int launch_embed_rows(const int64_t* ids, const void* table, void* out, long rows, int C, int vocab, hipStream_t s);
+
+// ---- DINOv2 reward (vit_ops.hip / vit.cpp) ----------------------------------------------------------------------------
+// PIL's fixed-point bicubic resize restricted to the center-crop window, as device tables built once per image size (vit.cpp): for every output column /
+// row of the window the first input index, the tap count and the taps (22 fractional bits).  The horizontal pass runs on input rows row0 .. row0 + nrows
+// only (what the window's vertical pass reads); col_lo / col_hi bound the input columns it touches.
+struct VitResizePlan {
+    const int *h_lo, *h_cnt, *h_kk; int h_ksize;
+    const int *v_lo, *v_cnt, *v_kk; int v_ksize;
+    int row0, nrows, col_lo, col_hi;
+};
+// images [B][3][H][W] (CS_F16 / CS_F32) in [0, 1] -> patches [B * G * G][Kpad] fp16 (the patch-embedding GEMM's A operand, k = c P P + ky P + kx, zero padded);
+// tmp: B * 3 * nrows * (P G) bytes; crop (optional): the resized + cropped uint8 image [B][3][P G][P G]
+int launch_vit_front_end(const void* images, int dtype, int B, int H, int W, const VitResizePlan& pl, const float* mean, const float* stdv, double rescale,
+                         int P, int G, int Kpad, unsigned char* tmp, f16* patches, unsigned char* crop, hipStream_t s);
+// x[b][0] = cls + pos[0], x[b][1 + p] = pe[b * NP + p] + pos[1 + p]
+int launch_vit_tokens(const f16* pe, const f16* cls, const f16* pos, f16* x, int B, int NP, int D, hipStream_t s);
+// x <- 0.5 x (1 + erf(x / sqrt 2)) in place
+int launch_gelu_erf(f16* x, long n, hipStream_t s);
+// LayerNorm of the first row of every sample (rows sample_stride halfs apart) -> out [B][D] fp32
+int launch_vit_cls_layer_norm(const f16* x, long sample_stride, const f16* g, const f16* b, float eps, int B, int D, float* out, hipStream_t s);
+// (cosine_similarity(normalize(pred), normalize(target)) + 1) * 50 -> out [B]; target rows target_stride floats apart (0 broadcasts one row)
+int launch_cosine_reward(const float* pred, const float* target, long target_stride, int B, int D, float* out, hipStream_t s);

@@ -1,0 +1,358 @@
+// DINOv2 image encoder + the image-similarity reward around it (reward_type "dino": edit_ppo/reward_model.py:59-64, 217-257; run_ppo.sh:30).
+//
+// Replaces, for a batch of decoded images [B,3,H,W] in [0,1]:  ToPILImage -> the facebook/dinov2-base processor (PIL bicubic resize to shortest edge 256, center
+// crop 224, rescale, normalise) -> transformers Dinov2Model (14 x 14 patch conv, CLS token, position table bicubically interpolated from its 37 x 37 training grid,
+// 12 pre-LN layers with LayerScale and exact GELU, final LayerNorm) -> CLS row -> F.normalize / cosine_similarity -> (cos + 1) * 50.
+// The encoder is clip.cpp's layer loop (implicit-GEMM MFMA linears, flash attention at head dim 64 -- here unmasked, 257 tokens) with the LayerScale vectors folded
+// into the out-projection / fc2 weights and biases at pack time (fp32 product, one rounding to fp16); the front end and the tail are vit_ops.hip.
+#include "ops.h"
+#include "consolver_hip.h"
+
+#include <map>
+#include <string>
+#include <vector>
+#include <algorithm>
+#include <cmath>
+
+namespace {
+struct HostT { std::vector<int64_t> shape; std::vector<float> data; };
+struct Layer { f16 *ln1g, *ln1b, *wqkv, *bqkv, *wo, *bo, *ln2g, *ln2b, *w1, *b1, *w2, *b2; };
+struct Plan { VitResizePlan dev; };
+}
+
+struct CsVit {
+    CsVitConfig cfg;
+    int G = 0, NP = 0, T = 0, K = 0, Kpad = 0, I = 0;      // patch grid of the crop, patches, tokens, patch-row length (and padded), MLP width
+    std::vector<std::string> names;
+    std::map<std::string, std::vector<int64_t>> expect;
+    std::map<std::string, HostT> host;
+    std::vector<void*> dev_allocs;
+    bool finalized = false;
+    f16 *wpatch = nullptr, *bpatch = nullptr, *cls = nullptr, *pos = nullptr, *lnfg = nullptr, *lnfb = nullptr;
+    std::vector<Layer> layers;
+    // resize tables per input (height, width), at most MAX_PLANS of them (a directory of many image sizes must not grow device memory without bound: when the
+    // cache is full it is emptied -- hipFree waits for the kernels that still read a table).  Like every handle here a CsVit serves one thread at a time, and the
+    // tables live on the device that is current when a size is first seen: callers run a handle on one device (the Python wrapper selects the tensor's).
+    static constexpr size_t MAX_PLANS = 16;
+    std::map<std::pair<int, int>, Plan> plans;
+    std::vector<void*> plan_allocs;
+};
+
+namespace {
+
+void expect_tensor(CsVit* c, const std::string& n, std::vector<int64_t> shape) { c->names.push_back(n); c->expect[n] = std::move(shape); }
+
+void build_manifest(CsVit* c) {          // transformers Dinov2Model.state_dict() order
+    const int D = c->cfg.hidden_size, I = c->I, P = c->cfg.patch_size, g = c->cfg.image_size / P;
+    expect_tensor(c, "embeddings.cls_token", {1, 1, D});
+    expect_tensor(c, "embeddings.mask_token", {1, D});                                   // in the published count; pre-training only, unused by the forward
+    expect_tensor(c, "embeddings.position_embeddings", {1, (int64_t)g * g + 1, D});
+    expect_tensor(c, "embeddings.patch_embeddings.projection.weight", {D, 3, P, P});
+    expect_tensor(c, "embeddings.patch_embeddings.projection.bias", {D});
+    for (int l = 0; l < c->cfg.num_hidden_layers; ++l) {
+        const std::string p = "encoder.layer." + std::to_string(l);
+        expect_tensor(c, p + ".norm1.weight", {D}); expect_tensor(c, p + ".norm1.bias", {D});
+        for (const char* q : {".attention.attention.query", ".attention.attention.key", ".attention.attention.value", ".attention.output.dense"}) {
+            expect_tensor(c, p + q + ".weight", {D, D}); expect_tensor(c, p + q + ".bias", {D});
+        }
+        expect_tensor(c, p + ".layer_scale1.lambda1", {D});
+        expect_tensor(c, p + ".norm2.weight", {D}); expect_tensor(c, p + ".norm2.bias", {D});
+        expect_tensor(c, p + ".mlp.fc1.weight", {I, D}); expect_tensor(c, p + ".mlp.fc1.bias", {I});
+        expect_tensor(c, p + ".mlp.fc2.weight", {D, I}); expect_tensor(c, p + ".mlp.fc2.bias", {D});
+        expect_tensor(c, p + ".layer_scale2.lambda1", {D});
+    }
+    expect_tensor(c, "layernorm.weight", {D}); expect_tensor(c, "layernorm.bias", {D});
+}
+
+f16* upload(CsVit* c, const std::vector<float>& h) {
+    std::vector<f16> t(h.size());
+    for (size_t i = 0; i < h.size(); ++i) t[i] = (f16)h[i];
+    void* d = nullptr;
+    if (hipMalloc(&d, std::max<size_t>(t.size() * sizeof(f16), 256)) != hipSuccess) return nullptr;
+    if (hipMemcpy(d, t.data(), t.size() * sizeof(f16), hipMemcpyHostToDevice) != hipSuccess) { hipFree(d); return nullptr; }
+    c->dev_allocs.push_back(d);
+    return (f16*)d;
+}
+const std::vector<float>& T(CsVit* c, const std::string& n) { return c->host.at(n).data; }
+
+// rows of w [N][K] (and b [N]) times lambda[N]: LayerScale folded into the linear layer in front of it
+std::vector<float> scale_rows(const std::vector<float>& w, const std::vector<float>& lam, int K) {
+    std::vector<float> o(w.size());
+    for (size_t i = 0; i < w.size(); ++i) o[i] = w[i] * lam[i / K];
+    return o;
+}
+
+// torch F.interpolate(mode="bicubic", align_corners=False) of the [s][s][D] position grid to [g][g][D] (cubic convolution, A = -0.75, clamped reads)
+void cubic_taps(double t, double* k) {
+    const double A = -0.75;
+    auto c1 = [&](double x) { return ((A + 2) * x - (A + 3)) * x * x + 1; };
+    auto c2 = [&](double x) { return ((A * x - 5 * A) * x + 8 * A) * x - 4 * A; };
+    k[0] = c2(t + 1); k[1] = c1(t); k[2] = c1(1 - t); k[3] = c2(2 - t);
+}
+std::vector<float> interpolate_positions(const float* grid, int s, int g, int D) {
+    std::vector<float> out((size_t)g * g * D);
+    const double scale = (double)s / g;
+    for (int oy = 0; oy < g; ++oy) {
+        const double sy = scale * (oy + 0.5) - 0.5; const int iy = (int)std::floor(sy); double ky[4]; cubic_taps(sy - iy, ky);
+        for (int ox = 0; ox < g; ++ox) {
+            const double sx = scale * (ox + 0.5) - 0.5; const int ix = (int)std::floor(sx); double kx[4]; cubic_taps(sx - ix, kx);
+            for (int d = 0; d < D; ++d) {
+                double acc = 0;
+                for (int a = 0; a < 4; ++a) {
+                    const int y = std::min(std::max(iy - 1 + a, 0), s - 1);
+                    double r = 0;
+                    for (int b = 0; b < 4; ++b) r += kx[b] * grid[((size_t)y * s + std::min(std::max(ix - 1 + b, 0), s - 1)) * D + d];
+                    acc += ky[a] * r;
+                }
+                out[((size_t)oy * g + ox) * D + d] = (float)acc;
+            }
+        }
+    }
+    return out;
+}
+
+// one pass of PIL's ImagingResample (BICUBIC: Keys cubic a = -0.5, support 2 * max(scale, 1)) for output indices win0 .. win0 + win: taps normalised in double,
+// converted as int(+-0.5 + k 2^22)
+struct Taps { std::vector<int> lo, cnt, kk; int ksize; };
+double pil_cubic(double x) {
+    const double a = -0.5;
+    x = std::fabs(x);
+    if (x < 1.0) return ((a + 2.0) * x - (a + 3.0)) * x * x + 1;
+    if (x < 2.0) return (((x - 5) * x + 8) * x - 4) * a;
+    return 0.0;
+}
+Taps pil_taps(int in, int out, int win0, int win) {
+    Taps t;
+    const double scale = (double)in / out, fs = std::max(scale, 1.0), support = 2.0 * fs, ww = 1.0 / fs;
+    t.ksize = (int)std::ceil(support) * 2 + 1;
+    t.lo.resize(win); t.cnt.resize(win); t.kk.assign((size_t)win * t.ksize, 0);
+    std::vector<double> w(t.ksize);
+    for (int i = 0; i < win; ++i) {
+        const double center = (win0 + i + 0.5) * scale;
+        const int xmin = std::max((int)(center - support + 0.5), 0), n = std::min((int)(center + support + 0.5), in) - xmin;
+        double tot = 0;
+        for (int x = 0; x < n; ++x) { w[x] = pil_cubic((x + xmin - center + 0.5) * ww); tot += w[x]; }
+        for (int x = 0; x < n; ++x) {
+            const double k = tot != 0.0 ? w[x] / tot : w[x];
+            t.kk[(size_t)i * t.ksize + x] = k < 0 ? (int)(-0.5 + k * (1 << 22)) : (int)(0.5 + k * (1 << 22));
+        }
+        t.lo[i] = xmin; t.cnt[i] = n;
+    }
+    return t;
+}
+
+int get_plan(CsVit* c, int H, int W, const Plan** out) {
+    auto it = c->plans.find({H, W});
+    if (it != c->plans.end()) { *out = &it->second; return CS_OK; }
+    const int edge = c->cfg.resize_shortest_edge, C = c->cfg.crop_size;
+    if (H < 1 || W < 1) CS_FAIL(CS_E_SHAPE, "vit: bad image size %d x %d", H, W);
+    // the processor's output-size rule (default_to_square = False): the short side becomes `edge`, the long side int(edge * long / short)
+    const int shrt = std::min(H, W), lng = std::max(H, W), nl = (int)((double)((int64_t)edge * lng) / shrt);
+    const int nh = H <= W ? edge : nl, nw = H <= W ? nl : edge;
+    if (nh < C || nw < C) CS_FAIL(CS_E_UNSUPPORTED, "vit: resized image %d x %d is smaller than the %d crop (the processor would pad)", nh, nw, C);
+    const Taps th = pil_taps(W, nw, (nw - C) / 2, C), tv = pil_taps(H, nh, (nh - C) / 2, C);
+    Plan p{};
+    int row0 = H, row1 = 0, col0 = W, col1 = 0;
+    for (int i = 0; i < C; ++i) {
+        row0 = std::min(row0, tv.lo[i]); row1 = std::max(row1, tv.lo[i] + tv.cnt[i]);
+        col0 = std::min(col0, th.lo[i]); col1 = std::max(col1, th.lo[i] + th.cnt[i]);
+    }
+    std::vector<int> all;
+    auto put = [&](const std::vector<int>& v) { const size_t o = all.size(); all.insert(all.end(), v.begin(), v.end()); return o; };
+    const size_t o0 = put(th.lo), o1 = put(th.cnt), o2 = put(th.kk), o3 = put(tv.lo), o4 = put(tv.cnt), o5 = put(tv.kk);
+    if (c->plans.size() >= CsVit::MAX_PLANS) {
+        for (void* q : c->plan_allocs) CS_CHECK_HIP(hipFree(q));
+        c->plan_allocs.clear(); c->plans.clear();
+    }
+    int* d = nullptr;
+    CS_CHECK_HIP(hipMalloc((void**)&d, all.size() * sizeof(int)));
+    if (hipMemcpy(d, all.data(), all.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(d); CS_FAIL(CS_E_HIP, "vit: resize table upload failed"); }
+    c->plan_allocs.push_back(d);
+    p.dev = VitResizePlan{d + o0, d + o1, d + o2, th.ksize, d + o3, d + o4, d + o5, tv.ksize, row0, row1 - row0, col0, col1};
+    *out = &(c->plans[{H, W}] = p);
+    return CS_OK;
+}
+
+int linear(const f16* x, int M, int K, const f16* w, const f16* b, int N, const f16* res, f16* out, hipStream_t s) {
+    IgemmArgs a{};
+    a.a0 = x; a.c0 = K; a.B = 1; a.Hi = M; a.Wi = 1; a.Ho = M; a.Wo = 1; a.taps = 1; a.stride = 1; a.N = N; a.w = w; a.bias = b; a.res = res; a.out = out;
+    return launch_igemm(a, s);
+}
+
+}  // namespace
+
+extern "C" {
+
+int cs_vit_create(const CsVitConfig* cfg, CsVit** out) {
+    if (!cfg || !out) CS_FAIL(CS_E_ARG, "cfg/out is NULL");
+    if (cfg->hidden_size < 128 || cfg->hidden_size % 128 || cfg->mlp_ratio < 1 || (cfg->hidden_size * cfg->mlp_ratio) % 128)
+        CS_FAIL(CS_E_SHAPE, "vit: hidden / MLP size must be multiples of 128");
+    if (cfg->num_attention_heads < 1 || cfg->hidden_size != cfg->num_attention_heads * 64) CS_FAIL(CS_E_UNSUPPORTED, "vit: built for heads of dim 64");
+    if (cfg->num_hidden_layers < 1 || cfg->patch_size < 1 || cfg->image_size < cfg->patch_size || cfg->image_size % cfg->patch_size) CS_FAIL(CS_E_ARG, "vit: bad config");
+    if (cfg->crop_size < cfg->patch_size || cfg->crop_size % cfg->patch_size || cfg->resize_shortest_edge < cfg->crop_size)
+        CS_FAIL(CS_E_ARG, "vit: crop_size must be a multiple of patch_size and at most resize_shortest_edge");
+    for (int i = 0; i < 3; ++i) if (!(cfg->image_std[i] > 0.f)) CS_FAIL(CS_E_ARG, "vit: image_std must be positive");
+    CsVit* c = new CsVit();
+    c->cfg = *cfg;
+    c->G = cfg->crop_size / cfg->patch_size; c->NP = c->G * c->G; c->T = c->NP + 1;
+    c->K = 3 * cfg->patch_size * cfg->patch_size; c->Kpad = (c->K + 63) / 64 * 64; c->I = cfg->hidden_size * cfg->mlp_ratio;
+    build_manifest(c);
+    *out = c;
+    return CS_OK;
+}
+
+void cs_vit_destroy(CsVit* c) {
+    if (!c) return;
+    for (void* p : c->dev_allocs) (void)hipFree(p);
+    for (void* p : c->plan_allocs) (void)hipFree(p);
+    delete c;
+}
+
+int cs_vit_num_weights(const CsVit* c) { return c ? (int)c->names.size() : 0; }
+
+const char* cs_vit_weight_name(const CsVit* c, int i, int64_t* shape4, int* ndim) {
+    if (!c || i < 0 || i >= (int)c->names.size()) return nullptr;
+    const auto& sh = c->expect.at(c->names[i]);
+    if (ndim) *ndim = (int)sh.size();
+    if (shape4) for (size_t k = 0; k < 4; ++k) shape4[k] = k < sh.size() ? sh[k] : 1;
+    return c->names[i].c_str();
+}
+
+int cs_vit_set_weight(CsVit* c, const char* name, const float* data, const int64_t* shape, int ndim) {
+    if (!c || !name || !data || !shape) CS_FAIL(CS_E_ARG, "null argument");
+    if (c->finalized) CS_FAIL(CS_E_STATE, "weights are already packed");
+    auto it = c->expect.find(name);
+    if (it == c->expect.end()) CS_FAIL(CS_E_ARG, "unexpected tensor name '%s'", name);
+    if ((int)it->second.size() != ndim) CS_FAIL(CS_E_SHAPE, "%s: rank %d, expected %zu", name, ndim, it->second.size());
+    int64_t n = 1;
+    for (int k = 0; k < ndim; ++k) {
+        if (shape[k] != it->second[k]) CS_FAIL(CS_E_SHAPE, "%s: dim %d is %lld, expected %lld", name, k, (long long)shape[k], (long long)it->second[k]);
+        n *= shape[k];
+    }
+    HostT t; t.shape.assign(shape, shape + ndim); t.data.assign(data, data + n);
+    c->host[name] = std::move(t);
+    return CS_OK;
+}
+
+int cs_vit_finalize(CsVit* c) {
+    if (!c) CS_FAIL(CS_E_ARG, "null");
+    if (c->finalized) return CS_OK;
+    for (auto& n : c->names) if (!c->host.count(n)) CS_FAIL(CS_E_STATE, "missing weight '%s'", n.c_str());
+    const int D = c->cfg.hidden_size, I = c->I, K = c->K, Kpad = c->Kpad, s = c->cfg.image_size / c->cfg.patch_size, G = c->G;
+    {   // patch projection [D][3 P P] -> [D][Kpad]
+        const auto& w = T(c, "embeddings.patch_embeddings.projection.weight");
+        std::vector<float> wp((size_t)D * Kpad, 0.f);
+        for (int n = 0; n < D; ++n) std::copy(w.begin() + (size_t)n * K, w.begin() + (size_t)(n + 1) * K, wp.begin() + (size_t)n * Kpad);
+        c->wpatch = upload(c, wp); c->bpatch = upload(c, T(c, "embeddings.patch_embeddings.projection.bias"));
+    }
+    {   // position table of the crop's grid: the class row as is (pre-added to the CLS token in fp32), the patch grid interpolated when the crop is not the training size
+        const auto& pos = T(c, "embeddings.position_embeddings");
+        const auto& cls = T(c, "embeddings.cls_token");
+        std::vector<float> cls0(D), table((size_t)c->T * D, 0.f);
+        for (int d = 0; d < D; ++d) cls0[d] = cls[d] + pos[d];
+        if (G == s) std::copy(pos.begin() + D, pos.end(), table.begin() + D);
+        else { const auto g = interpolate_positions(pos.data() + D, s, G, D); std::copy(g.begin(), g.end(), table.begin() + D); }
+        c->cls = upload(c, cls0); c->pos = upload(c, table);
+    }
+    c->lnfg = upload(c, T(c, "layernorm.weight")); c->lnfb = upload(c, T(c, "layernorm.bias"));
+    bool ok = c->wpatch && c->bpatch && c->cls && c->pos && c->lnfg && c->lnfb;
+    c->layers.resize(c->cfg.num_hidden_layers);
+    for (int l = 0; l < c->cfg.num_hidden_layers && ok; ++l) {
+        const std::string p = "encoder.layer." + std::to_string(l);
+        Layer& L = c->layers[l];
+        std::vector<float> w, b;
+        for (const char* q : {".attention.attention.query", ".attention.attention.key", ".attention.attention.value"}) {       // fused [3D, D]
+            const auto& tw = T(c, p + q + ".weight"); w.insert(w.end(), tw.begin(), tw.end());
+            const auto& tb = T(c, p + q + ".bias"); b.insert(b.end(), tb.begin(), tb.end());
+        }
+        L.wqkv = upload(c, w); L.bqkv = upload(c, b);
+        const auto& l1 = T(c, p + ".layer_scale1.lambda1");
+        const auto& l2 = T(c, p + ".layer_scale2.lambda1");
+        L.wo = upload(c, scale_rows(T(c, p + ".attention.output.dense.weight"), l1, D)); L.bo = upload(c, scale_rows(T(c, p + ".attention.output.dense.bias"), l1, 1));
+        L.ln1g = upload(c, T(c, p + ".norm1.weight")); L.ln1b = upload(c, T(c, p + ".norm1.bias"));
+        L.ln2g = upload(c, T(c, p + ".norm2.weight")); L.ln2b = upload(c, T(c, p + ".norm2.bias"));
+        L.w1 = upload(c, T(c, p + ".mlp.fc1.weight")); L.b1 = upload(c, T(c, p + ".mlp.fc1.bias"));
+        L.w2 = upload(c, scale_rows(T(c, p + ".mlp.fc2.weight"), l2, I)); L.b2 = upload(c, scale_rows(T(c, p + ".mlp.fc2.bias"), l2, 1));
+        ok = L.wqkv && L.bqkv && L.wo && L.bo && L.ln1g && L.ln1b && L.ln2g && L.ln2b && L.w1 && L.b1 && L.w2 && L.b2;
+    }
+    if (!ok) CS_FAIL(CS_E_HIP, "vit: weight upload failed (hipMalloc/hipMemcpy)");
+    c->host.clear();
+    c->finalized = true;
+    return CS_OK;
+}
+
+int cs_vit_patch_cols(const CsVit* c) { return c ? c->Kpad : 0; }
+int cs_vit_num_tokens(const CsVit* c) { return c ? c->T : 0; }
+
+size_t cs_vit_workspace_bytes(const CsVit* c, int batch) {
+    if (!c || batch <= 0) return 0;
+    const size_t rows = (size_t)batch * c->T, D = c->cfg.hidden_size;
+    return (rows * (D + D + 3 * D + c->I) + (size_t)batch * c->NP * D) * sizeof(f16) + 4096;       // x, normed, qkv (attention output reuses normed), mlp, patch embeddings
+}
+
+double cs_vit_flops(const CsVit* c, int batch) {
+    if (!c) return 0;
+    const double rows = (double)batch * c->T, D = c->cfg.hidden_size, I = c->I;
+    return 2.0 * batch * c->NP * (double)c->K * D + c->cfg.num_hidden_layers * (2.0 * rows * D * (4 * D + 2 * I) + 4.0 * batch * (double)c->T * c->T * D);
+}
+
+size_t cs_vit_preprocess_workspace_bytes(const CsVit* c, int batch, int height, int width) {
+    if (!c || batch <= 0 || height <= 0 || width <= 0) return 0;
+    return (size_t)batch * 3 * height * c->cfg.crop_size + 256;          // the horizontal pass's rows (at most every input row) x crop columns, uint8
+}
+
+int cs_vit_preprocess(CsVit* c, const void* images, int dtype, int batch, int height, int width, void* patches, unsigned char* crop_u8,
+                      void* workspace, size_t workspace_bytes, void* stream) {
+    if (!c) CS_FAIL(CS_E_ARG, "vit is NULL");
+    if (batch < 0) CS_FAIL(CS_E_ARG, "negative size");
+    if (batch == 0) return CS_OK;
+    if (!images || !patches || !workspace) CS_FAIL(CS_E_ARG, "null pointer");
+    const Plan* pl = nullptr;
+    const int rc = get_plan(c, height, width, &pl);
+    if (rc != CS_OK) return rc;
+    if (workspace_bytes < (size_t)batch * 3 * pl->dev.nrows * c->cfg.crop_size) CS_FAIL(CS_E_ARG, "vit: preprocess workspace too small");
+    return launch_vit_front_end(images, dtype, batch, height, width, pl->dev, c->cfg.image_mean, c->cfg.image_std, c->cfg.rescale_factor,
+                                c->cfg.patch_size, c->G, c->Kpad, (unsigned char*)workspace, (f16*)patches, crop_u8, (hipStream_t)stream);
+}
+
+int cs_vit_forward(CsVit* c, const void* patches, int batch, float* cls_out, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!c) CS_FAIL(CS_E_ARG, "vit is NULL");
+    if (!c->finalized) CS_FAIL(CS_E_STATE, "cs_vit_finalize has not been called");
+    if (batch < 0) CS_FAIL(CS_E_ARG, "negative size");
+    if (batch == 0) return CS_OK;
+    if (!patches || !cls_out || !workspace) CS_FAIL(CS_E_ARG, "null pointer");
+    if (workspace_bytes < cs_vit_workspace_bytes(c, batch)) CS_FAIL(CS_E_ARG, "vit: workspace too small");
+    if ((long)batch * c->T > 0x7fffffffL / std::max(c->I, 3 * c->cfg.hidden_size)) CS_FAIL(CS_E_SHAPE, "vit: batch too large for one call");
+    hipStream_t s = (hipStream_t)stream;
+    const int D = c->cfg.hidden_size, I = c->I, H = c->cfg.num_attention_heads, Tn = c->T;
+    const long rows = (long)batch * Tn;
+    f16* x = (f16*)workspace; f16* n = x + rows * D; f16* qkv = n + rows * D; f16* h = qkv + rows * 3 * D; f16* pe = h + rows * I;
+    int rc = linear((const f16*)patches, batch * c->NP, c->Kpad, c->wpatch, c->bpatch, D, nullptr, pe, s);
+    if (rc == CS_OK) rc = launch_vit_tokens(pe, c->cls, c->pos, x, batch, c->NP, D, s);
+    for (int l = 0; l < c->cfg.num_hidden_layers && rc == CS_OK; ++l) {
+        const Layer& L = c->layers[l];
+        rc = launch_layer_norm(x, L.ln1g, L.ln1b, n, (int)rows, D, c->cfg.layer_norm_eps, s);
+        if (rc == CS_OK) rc = linear(n, (int)rows, D, L.wqkv, L.bqkv, 3 * D, nullptr, qkv, s);
+        if (rc == CS_OK) {
+            AttnArgs a{};
+            a.q = qkv; a.q_stride = 3 * D; a.k = qkv + D; a.k_stride = 3 * D; a.v = qkv + 2 * D; a.v_stride = 3 * D; a.out = n; a.out_stride = D;
+            a.B = batch; a.H = H; a.Nq = Tn; a.Nk = Tn; a.dh = 64; a.scale = 0.125f;
+            rc = launch_attention(a, s);
+        }
+        if (rc == CS_OK) rc = linear(n, (int)rows, D, L.wo, L.bo, D, x, x, s);                          // lambda1 folded; + residual
+        if (rc == CS_OK) rc = launch_layer_norm(x, L.ln2g, L.ln2b, n, (int)rows, D, c->cfg.layer_norm_eps, s);
+        if (rc == CS_OK) rc = linear(n, (int)rows, D, L.w1, L.b1, I, nullptr, h, s);
+        if (rc == CS_OK) rc = launch_gelu_erf(h, rows * I, s);
+        if (rc == CS_OK) rc = linear(h, (int)rows, I, L.w2, L.b2, D, x, x, s);                          // lambda2 folded; + residual
+    }
+    if (rc == CS_OK) rc = launch_vit_cls_layer_norm(x, (long)Tn * D, c->lnfg, c->lnfb, c->cfg.layer_norm_eps, batch, D, cls_out, s);
+    return rc;
+}
+
+int cs_cosine_reward(const float* pred, const float* target, int batch, int dim, int64_t target_stride, float* out, void* stream) {
+    if (batch < 0 || dim <= 0 || target_stride < 0) CS_FAIL(CS_E_ARG, "cosine reward: bad size");
+    if (batch == 0) return CS_OK;
+    return launch_cosine_reward(pred, target, (long)target_stride, batch, dim, out, (hipStream_t)stream);
+}
+
+}  // extern "C"

@@ -1,0 +1,193 @@
+// Kernels of the DINOv2 image-similarity reward (vit.cpp; edit_ppo/reward_model.py:217-257) that are not GEMM / attention / LayerNorm:
+//
+//   * the image front end: ToPILImage's quantisation, PIL's two-pass fixed-point bicubic resize restricted to the center-crop window, the processor's
+//     rescale + normalise, written straight as the patch-embedding GEMM's A operand [B * tokens][K padded to 64];
+//   * token assembly (CLS row + position table), exact (erf) GELU, the final LayerNorm on the CLS rows only, and the reward tail
+//     F.normalize -> F.cosine_similarity -> (cos + 1) * 50.
+//
+// Everything here is bandwidth- or latency-trivial next to the encoder's GEMMs (one image = 46 GFLOP): plain one-thread-per-output kernels, integer
+// arithmetic identical to PIL's (22 fractional bits, accumulator seeded with 2^21, arithmetic shift, clip to 8 bits), so the uint8 crop is bit-exact.
+#include "ops.h"
+
+namespace {
+
+constexpr int RS_BITS = 22;
+
+// ToPILImage on a float tensor: x.mul(255).byte() -- the product is rounded in the tensor's OWN dtype, the conversion truncates.  The clamp to [0, 1]
+// in front is unconditional here (the reference clamps when min < 0; decode_latents never leaves [0, 1]); NaN -> 0.
+__device__ __forceinline__ int quant255(f16 v) {
+    f16 x = v > (f16)0.0f ? v : (f16)0.0f;
+    x = x < (f16)1.0f ? x : (f16)1.0f;
+    const f16 p = x * (f16)255.0f;        // v_mul_f16: one rounding to fp16, as torch's half multiply
+    return (int)(float)p;
+}
+__device__ __forceinline__ int quant255(float v) {
+    float x = v > 0.0f ? v : 0.0f;
+    x = x < 1.0f ? x : 1.0f;
+    return (int)(x * 255.0f);
+}
+__device__ __forceinline__ int clip8(int acc) {
+    const int v = acc >> RS_BITS;
+    return v < 0 ? 0 : (v > 255 ? 255 : v);
+}
+
+struct ResizeTab { const int* lo; const int* cnt; const int* kk; int ksize; };     // per output index of the crop window: first input index, taps, fixed-point taps
+
+// horizontal pass: tmp[bc][r][x] for input rows row0 .. row0 + nrows (the rows the vertical pass of the crop window reads), x in the crop window
+template <typename T>
+__global__ __launch_bounds__(256) void vit_hresize_kernel(const T* __restrict__ src, int BC, int H, int W, int row0, int nrows, int cw, ResizeTab th,
+                                                          unsigned char* __restrict__ tmp) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (long)BC * nrows * cw) return;
+    const int x = (int)(i % cw);
+    const long t = i / cw;
+    const int r = (int)(t % nrows), bc = (int)(t / nrows);
+    const T* row = src + ((long)bc * H + (row0 + r)) * W + th.lo[x];
+    const int* kk = th.kk + (long)x * th.ksize;
+    const int n = th.cnt[x];
+    int acc = 1 << (RS_BITS - 1);
+    for (int j = 0; j < n; ++j) acc += quant255(row[j]) * kk[j];
+    tmp[i] = (unsigned char)clip8(acc);
+}
+
+// vertical pass + normalise + patch rows: A[(b * G * G + py * G + px)][c * P * P + ky * P + kx], columns K .. Kpad zero
+__global__ __launch_bounds__(256) void vit_vresize_patch_kernel(const unsigned char* __restrict__ tmp, int B, int row0, int nrows, int cw, ResizeTab tv, int P, int G,
+                                                                int K, int Kpad, float m0, float m1, float m2, float s0, float s1, float s2, double rescale,
+                                                                f16* __restrict__ patches, unsigned char* __restrict__ crop) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (long)B * G * G * Kpad) return;
+    const int k = (int)(i % Kpad);
+    if (k >= K) { patches[i] = (f16)0.0f; return; }
+    const long t = i / Kpad;
+    const int p = (int)(t % (G * G)), b = (int)(t / (G * G));
+    const int c = k / (P * P), r = k - c * P * P, ky = r / P, kx = r - ky * P;
+    const int y = (p / G) * P + ky, x = (p % G) * P + kx;
+    const unsigned char* col = tmp + ((long)(b * 3 + c) * nrows + (tv.lo[y] - row0)) * cw + x;
+    const int* kk = tv.kk + (long)y * tv.ksize;
+    const int n = tv.cnt[y];
+    int acc = 1 << (RS_BITS - 1);
+    for (int j = 0; j < n; ++j) acc += (int)col[(long)j * cw] * kk[j];
+    const int u = clip8(acc);
+    if (crop) crop[((long)(b * 3 + c) * cw + y) * cw + x] = (unsigned char)u;
+    const float mean = c == 0 ? m0 : (c == 1 ? m1 : m2), sd = c == 0 ? s0 : (c == 1 ? s1 : s2);
+    const float v = (float)((double)u * rescale);        // the processor rescales in double and rounds to fp32, then normalises in fp32
+    patches[i] = (f16)((v - mean) / sd);
+}
+
+// x[b][0] = cls + pos[0]; x[b][1 + p] = pe[b * NP + p] + pos[1 + p]   (fp32 add, one rounding); 8 channels per thread
+__global__ __launch_bounds__(256) void vit_tokens_kernel(const f16* __restrict__ pe, const f16* __restrict__ cls, const f16* __restrict__ pos, f16* __restrict__ x,
+                                                         int B, int NP, int D) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    const int D8 = D / 8;
+    if (i >= (long)B * (NP + 1) * D8) return;
+    const int d = (int)(i % D8) * 8;
+    const long row = i / D8;
+    const int t = (int)(row % (NP + 1)), b = (int)(row / (NP + 1));
+    const f16x8 a = t == 0 ? *reinterpret_cast<const f16x8*>(cls + d) : *reinterpret_cast<const f16x8*>(pe + ((long)b * NP + t - 1) * D + d);
+    const f16x8 q = *reinterpret_cast<const f16x8*>(pos + (long)t * D + d);
+    f16x8 o;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) o[e] = (f16)((float)a[e] + (float)q[e]);
+    *reinterpret_cast<f16x8*>(x + row * D + d) = o;
+}
+
+// x <- 0.5 x (1 + erf(x / sqrt 2)) in place (nn.GELU, the "gelu" activation of the Dinov2 MLP)
+__global__ __launch_bounds__(256) void gelu_erf_kernel(f16* __restrict__ x, long n8) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n8) return;
+    f16x8 v = *reinterpret_cast<const f16x8*>(x + i * 8);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        const float f = (float)v[e];
+        v[e] = (f16)(0.5f * f * (1.0f + erff(f * 0.70710678118654752f)));
+    }
+    *reinterpret_cast<f16x8*>(x + i * 8) = v;
+}
+
+// final LayerNorm on row 0 of every sample only: out[b][D] fp32 (one wave per sample, two passes over the row in fp32)
+__global__ __launch_bounds__(64) void vit_cls_layer_norm_kernel(const f16* __restrict__ x, long sample_stride, const f16* __restrict__ g, const f16* __restrict__ be,
+                                                                float eps, int D, float* __restrict__ out) {
+    const int b = blockIdx.x, lane = threadIdx.x;
+    const f16* row = x + (long)b * sample_stride;
+    float s = 0.f;
+    for (int d = lane; d < D; d += 64) s += (float)row[d];
+    const float mean = wave_sum(s) / (float)D;
+    float q = 0.f;
+    for (int d = lane; d < D; d += 64) { const float c = (float)row[d] - mean; q += c * c; }
+    const float rstd = 1.0f / sqrtf(wave_sum(q) / (float)D + eps);
+    for (int d = lane; d < D; d += 64) out[(long)b * D + d] = ((float)row[d] - mean) * rstd * (float)g[d] + (float)be[d];
+}
+
+// reward tail: a = F.normalize(pred), t = F.normalize(target) (eps 1e-12); cos = a.t / (max(|a|, 1e-8) max(|t|, 1e-8)); out = (cos + 1) * 50
+__global__ __launch_bounds__(64) void cosine_reward_kernel(const float* __restrict__ pred, const float* __restrict__ tgt, long tgt_stride, int D, float* __restrict__ out) {
+    const int b = blockIdx.x, lane = threadIdx.x;
+    const float* a = pred + (long)b * D;
+    const float* t = tgt + (long)b * tgt_stride;
+    float na = 0.f, nt = 0.f;
+    for (int d = lane; d < D; d += 64) { na += a[d] * a[d]; nt += t[d] * t[d]; }
+    const float ia = 1.0f / fmaxf(sqrtf(wave_sum(na)), 1e-12f), it = 1.0f / fmaxf(sqrtf(wave_sum(nt)), 1e-12f);
+    float dot = 0.f, ma = 0.f, mt = 0.f;
+    for (int d = lane; d < D; d += 64) {
+        const float u = a[d] * ia, v = t[d] * it;
+        dot += u * v; ma += u * u; mt += v * v;
+    }
+    dot = wave_sum(dot); ma = wave_sum(ma); mt = wave_sum(mt);
+    if (lane == 0) out[b] = (dot / (fmaxf(sqrtf(ma), 1e-8f) * fmaxf(sqrtf(mt), 1e-8f)) + 1.0f) * 50.0f;
+}
+
+inline unsigned blocks_for(long n) { return (unsigned)((n + 255) / 256); }
+
+}  // namespace
+
+int launch_vit_front_end(const void* images, int dtype, int B, int H, int W, const VitResizePlan& pl, const float* mean, const float* stdv, double rescale,
+                         int P, int G, int Kpad, unsigned char* tmp, f16* patches, unsigned char* crop, hipStream_t s) {
+    if (!images || !tmp || !patches || !mean || !stdv) CS_FAIL(CS_E_ARG, "vit front end: null pointer");
+    if (dtype != CS_F16 && dtype != CS_F32) CS_FAIL(CS_E_UNSUPPORTED, "vit front end: images must be fp16 or fp32");
+    if (B <= 0) return B < 0 ? CS_E_SHAPE : CS_OK;
+    const int cw = P * G, K = 3 * P * P;
+    // bounds of everything the two kernels index, checked on the host copy of the plan (vit.cpp builds both from one table)
+    if (pl.row0 < 0 || pl.nrows <= 0 || pl.row0 + pl.nrows > H || pl.col_hi > W || pl.col_lo < 0 || Kpad < K || Kpad % 8)
+        CS_FAIL(CS_E_SHAPE, "vit front end: resize plan does not fit a %d x %d image", H, W);
+    const ResizeTab th{pl.h_lo, pl.h_cnt, pl.h_kk, pl.h_ksize}, tv{pl.v_lo, pl.v_cnt, pl.v_kk, pl.v_ksize};
+    const long n1 = (long)B * 3 * pl.nrows * cw, n2 = (long)B * G * G * Kpad;
+    if (n1 > 0x7fffffffL * 256 || n2 > 0x7fffffffL * 256) CS_FAIL(CS_E_SHAPE, "vit front end: batch too large");
+    if (dtype == CS_F16) hipLaunchKernelGGL(vit_hresize_kernel<f16>, dim3(blocks_for(n1)), dim3(256), 0, s, (const f16*)images, B * 3, H, W, pl.row0, pl.nrows, cw, th, tmp);
+    else hipLaunchKernelGGL(vit_hresize_kernel<float>, dim3(blocks_for(n1)), dim3(256), 0, s, (const float*)images, B * 3, H, W, pl.row0, pl.nrows, cw, th, tmp);
+    CS_CHECK_LAUNCH();
+    hipLaunchKernelGGL(vit_vresize_patch_kernel, dim3(blocks_for(n2)), dim3(256), 0, s, tmp, B, pl.row0, pl.nrows, cw, tv, P, G, K, Kpad, mean[0], mean[1], mean[2],
+                       stdv[0], stdv[1], stdv[2], rescale, patches, crop);
+    CS_CHECK_LAUNCH();
+    return CS_OK;
+}
+
+int launch_vit_tokens(const f16* pe, const f16* cls, const f16* pos, f16* x, int B, int NP, int D, hipStream_t s) {
+    if (!pe || !cls || !pos || !x || D % 8) CS_FAIL(CS_E_ARG, "vit tokens: pointers required, D %% 8 == 0");
+    if (B <= 0) return B < 0 ? CS_E_SHAPE : CS_OK;
+    hipLaunchKernelGGL(vit_tokens_kernel, dim3(blocks_for((long)B * (NP + 1) * (D / 8))), dim3(256), 0, s, pe, cls, pos, x, B, NP, D);
+    CS_CHECK_LAUNCH();
+    return CS_OK;
+}
+
+int launch_gelu_erf(f16* x, long n, hipStream_t s) {
+    if (!x || n % 8) CS_FAIL(CS_E_ARG, "gelu: x required, n %% 8 == 0");
+    if (n <= 0) return CS_OK;
+    hipLaunchKernelGGL(gelu_erf_kernel, dim3(blocks_for(n / 8)), dim3(256), 0, s, x, n / 8);
+    CS_CHECK_LAUNCH();
+    return CS_OK;
+}
+
+int launch_vit_cls_layer_norm(const f16* x, long sample_stride, const f16* g, const f16* b, float eps, int B, int D, float* out, hipStream_t s) {
+    if (!x || !g || !b || !out) CS_FAIL(CS_E_ARG, "vit cls layer norm: null pointer");
+    if (B <= 0) return B < 0 ? CS_E_SHAPE : CS_OK;
+    hipLaunchKernelGGL(vit_cls_layer_norm_kernel, dim3(B), dim3(64), 0, s, x, sample_stride, g, b, eps, D, out);
+    CS_CHECK_LAUNCH();
+    return CS_OK;
+}
+
+int launch_cosine_reward(const float* pred, const float* target, long target_stride, int B, int D, float* out, hipStream_t s) {
+    if (!pred || !target || !out || D <= 0) CS_FAIL(CS_E_ARG, "cosine reward: null pointer");
+    if (B <= 0) return B < 0 ? CS_E_SHAPE : CS_OK;
+    hipLaunchKernelGGL(cosine_reward_kernel, dim3(B), dim3(64), 0, s, pred, target, target_stride, D, out);
+    CS_CHECK_LAUNCH();
+    return CS_OK;
+}

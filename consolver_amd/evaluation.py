@@ -4,8 +4,9 @@ Mirrors, by name and output schema:
 * gen_ppo.py:205-212,318-325 -- ``{device_id}_{index:08d}.png`` + ``.txt`` (prompt) per generated image;
 * compute_reward.py:52-78 ``find_image_pairs``, :81-95 ``load_image_tensor``, :332-365 ``calculate_statistics``,
   :447-462 the results JSON (``statistics`` / ``raw_scores`` / ``config``).
-Only the arithmetic-only reward (``image_psnr``, edit_ppo/reward_model.py:484-509) is scored, on the GPU (cs_image_psnr);
-the backbone rewards are third-party networks (out of scope).  PNG encode/decode is PIL (host I/O).
+Scored on the GPU: the arithmetic-only reward (``image_psnr``, edit_ppo/reward_model.py:484-509; cs_image_psnr) and, given a model,
+the DINOv2 image-similarity reward (``dino``, :217-257; consolver_amd/reward_model.py).  The other backbone rewards are third-party
+networks that are not implemented.  PNG encode/decode is PIL (host I/O).
 """
 import json
 import os
@@ -71,16 +72,19 @@ def calculate_statistics(results):
     return stats
 
 
-def score_image_pairs(image_pairs, reward_types=("image_psnr",), batch_size=16, device="cuda:0"):
-    """-> {reward_type: [score per pair]} (compute_reward.py:98-330 reduced to the arithmetic-only reward)."""
+def score_image_pairs(image_pairs, reward_types=("image_psnr",), batch_size=16, device="cuda:0", reward_models=None):
+    """-> {reward_type: [score per pair]} (compute_reward.py:98-330).  ``reward_models``: {reward_type: (model, processor)} as returned by
+    ``reward_model.load_reward_model`` for the rewards that need a network ("dino")."""
     results = {}
+    reward_models = reward_models or {}
     for rt in reward_types:
         scores = []
         for s in range(0, len(image_pairs), batch_size):
             chunk = image_pairs[s:s + batch_size]
             a = torch.stack([load_image_tensor(p, device) for p, _ in chunk])
             b = torch.stack([load_image_tensor(q, device) for _, q in chunk])
-            scores.extend(float(v) for v in ppo.calculate_reward(rt, None, None, a, b, device).flatten().cpu())
+            model, processor = reward_models.get(rt, (None, None))
+            scores.extend(float(v) for v in ppo.calculate_reward(rt, model, processor, a, b, device).flatten().cpu())
         results[rt] = scores
     return results
 

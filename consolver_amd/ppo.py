@@ -4,14 +4,14 @@ Mirror of the body of the training loop in train_ppo.py:352-427 up to (not inclu
 step, with the reference's names:
 
 * ``calculate_reward(reward_type, reward_model, reward_model_processor, model_pred, target, device)``
-  (edit_ppo/reward_model.py:138-161).  Only the arithmetic-only rewards are on the path
-  (SURVEY 8 a21): ``"image_psnr"`` (:484-509).  The backbone rewards (depth / inception / clip / ...)
-  are third-party networks and out of scope; they raise.
+  (edit_ppo/reward_model.py:138-161): ``"image_psnr"`` (:484-509, arithmetic only) and ``"dino"`` (:217-257, the DINOv2
+  image-similarity reward the reference's run scripts train with; consolver_amd/reward_model.py).  The other backbone
+  rewards (depth / inception / clip / ...) are third-party networks that are not implemented; they raise.
 * ``compute_advantages`` = train_ppo.py:376-390, ``ppo_loss`` = :408-421 (value), ``PolicyTrainer`` = the
   optimisation step :404-437 (gradients, clip_grad_norm_, AdamW) and the checkpoint format.
 * ``collect_rollout`` = :352-403 for one batch of teacher pairs.
 
-Everything runs in the HIP library (cs_image_psnr / cs_ppo_advantages / cs_ppo_loss); there is no
+Everything runs in the HIP library (cs_image_psnr / cs_vit_* / cs_ppo_advantages / cs_ppo_loss); there is no
 CPU fallback.
 """
 import ctypes as C
@@ -59,10 +59,14 @@ def depth_psnr_tail(pred_depth, target_depth):
 
 
 def calculate_reward(reward_type, reward_model, reward_model_processor, model_pred, target, device=None):
-    """edit_ppo/reward_model.py:138-161.  decode_latents already maps to [0, 1], so the clamp at :141-142 is a no-op here."""
+    """edit_ppo/reward_model.py:138-161.  decode_latents already maps to [0, 1], so the clamp at :141-142 is a no-op here (the "dino"
+    front end clamps to [0, 1] unconditionally)."""
     if reward_type == "image_psnr":
         return calculate_image_psnr_reward(reward_model_processor, model_pred, target, device)
-    if reward_type in ("depth", "inception", "segmentation", "clip", "llava", "qwen_vl", "dino"):
+    if reward_type == "dino":
+        from .reward_model import calculate_dino_reward
+        return calculate_dino_reward(reward_model, reward_model_processor, model_pred, target, device)
+    if reward_type in ("depth", "inception", "segmentation", "clip", "llava", "qwen_vl"):
         raise NotImplementedError(f"reward_type '{reward_type}' needs a third-party backbone network (out of scope, SURVEY 8 a21)")
     raise ValueError(f"Unknown reward_type: {reward_type}")
 
@@ -97,14 +101,17 @@ def collect_rollout(text_encoder, noise_scheduler, unet, vae, noise, text, token
     """train_ppo.py:352-403 for one batch: rollout, decode pred and teacher latents, reward, advantages, and the
     records flattened to [B (n-1), ...].  Returns a dict(conds, actions, probs, masks, advantages, rewards, model_pred).
     ``identical_inputs=True``: the B rows are copies of one (prompt, noise, teacher latent) sample (``repeat_random_sample``):
-    the rollout shares the denoiser calls whose inputs cannot differ yet, and the teacher image is decoded once."""
+    the rollout shares the denoiser calls whose inputs cannot differ yet, and the teacher image is decoded once (and, for the "dino"
+    reward, encoded once)."""
     n = num_inference_steps
     model_pred, conds, probs, actions, masks, _ = denoise_diffusion(
         text_encoder, noise_scheduler, unet, noise, text, tokenizer, cfg=float(cfg), num_inference_steps=n,
         prompt_embeds=prompt_embeds, negative_prompt_embeds=negative_prompt_embeds, identical_inputs=identical_inputs)
     model_pred_decoded = decode_latents(vae, model_pred, batch_size=decode_batch_size)
     if identical_inputs and target_latents.shape[0] > 1:
-        target_decoded = decode_latents(vae, target_latents[:1], batch_size=1).expand(target_latents.shape[0], -1, -1, -1).contiguous()
+        target_decoded = decode_latents(vae, target_latents[:1], batch_size=1)
+        if reward_type != "dino":               # calculate_dino_reward takes one shared target as [1,3,H,W]
+            target_decoded = target_decoded.expand(target_latents.shape[0], -1, -1, -1).contiguous()
     else:
         target_decoded = decode_latents(vae, target_latents, batch_size=decode_batch_size)
     rewards = calculate_reward(reward_type, reward_model, reward_model_processor, model_pred_decoded, target_decoded, noise.device)
@@ -214,7 +221,8 @@ class PolicyTrainer:
 
 
 def train_iteration(trainer, text_encoder, noise_scheduler, unet, vae, batch, tokenizer, cfg=3.0, num_inference_steps=None, ppo_epochs=4,
-                    reward_type="image_psnr", dist=None, prompt_embeds=None, negative_prompt_embeds=None, rng=None, share_identical=True):
+                    reward_type="image_psnr", dist=None, prompt_embeds=None, negative_prompt_embeds=None, rng=None, share_identical=True,
+                    reward_model=None, reward_model_processor=None):
     """One iteration of the training loop body (train_ppo.py:322-437): ``repeat_random_sample`` -> random step count in [2, 15]
     (:345) -> rollout, decode, reward, advantages (``collect_rollout``) -> ``ppo_epochs`` optimisation steps on the collected
     batch.  ``batch`` = (text list, noise [B,4,64,64], teacher latents [B,4,64,64]) already on the GPU.
@@ -231,8 +239,8 @@ def train_iteration(trainer, text_encoder, noise_scheduler, unet, vae, batch, to
     n = num_inference_steps or rng.choice(list(range(2, 16)))
     # the B rows are copies of one sample by construction (data_processing.py:65-83): share what cannot differ
     roll = collect_rollout(text_encoder, noise_scheduler, unet, vae, noise, text, tokenizer, tch, cfg=cfg, num_inference_steps=n,
-                           reward_type=reward_type, prompt_embeds=prompt_embeds, negative_prompt_embeds=negative_prompt_embeds,
-                           identical_inputs=share_identical)
+                           reward_type=reward_type, reward_model=reward_model, reward_model_processor=reward_model_processor,
+                           prompt_embeds=prompt_embeds, negative_prompt_embeds=negative_prompt_embeds, identical_inputs=share_identical)
     loss = norm = None
     for _ in range(ppo_epochs):
         loss, norm = trainer.step(roll["conds"], roll["actions"], roll["probs"], roll["advantages"], dist=dist)

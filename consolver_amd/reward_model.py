@@ -1,0 +1,242 @@
+"""DINOv2 image-similarity reward on the HIP library (``--reward_type="dino"``, edit_ppo/run_ppo.sh:30).
+
+Mirror of edit_ppo/reward_model.py by name:
+
+* ``load_reward_model("dino")`` (:25-57, :59-64) -> ``(model, processor)``: a ``HipDinov2Model`` of the ``facebook/dinov2-base`` shape and a
+  ``DinoImageProcessor`` holding that checkpoint's published preprocessing constants.  No hub access: weights are loaded by the caller with
+  ``model.load_state_dict`` under their ``transformers.Dinov2Model`` names.
+* ``calculate_dino_reward(reward_model, reward_model_processor, model_pred, target, device)`` (:217-257) -> rewards ``[B,1]`` fp32 in [0, 100].
+
+What the reference does per image on the host -- ``ToPILImage`` (``x.mul(255).byte()``: product in the tensor's dtype, truncation), PIL's fixed-point
+bicubic resize to shortest edge 256, center crop 224, rescale, normalise -- runs here as two HIP kernels on the whole batch, bit-identical on the uint8
+image; the encoder runs in fp16 with fp32 accumulation (cs_vit_forward) and returns the CLS features in fp32; the tail (normalize, cosine, (cos + 1) * 50)
+is one kernel.  Inputs are clamped to [0, 1] unconditionally (the reference clamps when ``min < 0``; ``decode_latents`` never leaves [0, 1]).
+There is no CPU fallback; the fp32 restatement lives in tests/vit_oracle.py.
+"""
+import ctypes as C
+
+import torch
+
+from . import _lib as L
+
+DINOV2_BASE_CONFIG = dict(hidden_size=768, num_hidden_layers=12, num_attention_heads=12, mlp_ratio=4, image_size=518, patch_size=14,
+                          layer_norm_eps=1e-6)
+_DT = {torch.float32: L.CS_F32, torch.float16: L.CS_F16}
+
+
+class DinoImageProcessor:
+    """The preprocessing constants of ``facebook/dinov2-base`` (its preprocessor_config.json): resize to shortest edge 256 with PIL BICUBIC, center crop
+    224, rescale 1/255, normalise with the ImageNet mean / std.  A plain holder: the arithmetic runs in ``HipDinov2Model.preprocess``."""
+    do_resize = do_center_crop = do_rescale = do_normalize = True
+    resample = 3                                   # PIL.Image.BICUBIC
+
+    def __init__(self, size=None, crop_size=None, rescale_factor=1 / 255, image_mean=(0.485, 0.456, 0.406), image_std=(0.229, 0.224, 0.225)):
+        self.size = dict(size or {"shortest_edge": 256})
+        self.crop_size = dict(crop_size or {"height": 224, "width": 224})
+        if set(self.size) != {"shortest_edge"} or self.crop_size["height"] != self.crop_size["width"]:
+            raise ValueError("the HIP front end implements the shortest-edge resize and a square center crop")
+        self.rescale_factor, self.image_mean, self.image_std = float(rescale_factor), tuple(image_mean), tuple(image_std)
+
+    def constants(self):
+        return (self.size["shortest_edge"], self.crop_size["height"], self.rescale_factor, self.image_mean, self.image_std)
+
+
+class _VitOutput(tuple):
+    """(last_hidden_state, pooler_output).  Only the CLS row is materialised: ``last_hidden_state`` is ``[B, 1, hidden]`` so that the reference's
+    ``outputs.last_hidden_state[:, 0, :]`` reads the CLS features; ``pooler_output`` is the same ``[B, hidden]`` tensor (as in transformers)."""
+    last_hidden_state = property(lambda self: self[0])
+    pooler_output = property(lambda self: self[1])
+
+
+class HipDinov2Model:
+    is_consolver_hip = True
+    dtype = torch.float16
+    max_batch = 64             # images per encoder call (bounds the workspace: 7.6 MB per image at the base size)
+
+    def __init__(self, config=None, device="cuda:0", processor=None):
+        cfg = dict(DINOV2_BASE_CONFIG)
+        cfg.update(config or {})
+        self.config = cfg
+        self.device = torch.device(device)
+        self.processor = processor or DinoImageProcessor()
+        edge, crop, rescale, mean, std = self.processor.constants()
+        c = L.CsVitConfig(cfg["hidden_size"], cfg["num_hidden_layers"], cfg["num_attention_heads"], cfg["mlp_ratio"], cfg["image_size"], cfg["patch_size"],
+                          cfg["layer_norm_eps"], edge, crop, (C.c_float * 3)(*mean), (C.c_float * 3)(*std), rescale)
+        h = C.c_void_p()
+        L.check(L.lib().cs_vit_create(C.byref(c), C.byref(h)))
+        self._h = h
+        self._ws = None
+        self._pws = None
+        self._finalized = False
+        self.crop, self.patch = crop, cfg["patch_size"]
+        self.patch_cols, self.num_tokens = int(L.lib().cs_vit_patch_cols(h)), int(L.lib().cs_vit_num_tokens(h))
+
+    def __del__(self):
+        try:
+            if getattr(self, "_h", None):
+                L.lib().cs_vit_destroy(self._h)
+                self._h = None
+        except Exception:
+            pass
+
+    # reference call sites: reward_model.eval(); reward_model.to(device)
+    def eval(self):
+        return self
+
+    def to(self, device=None, *args, **kwargs):
+        if device is not None:
+            d = torch.device(device)
+            if d.type == "cuda" and d.index is None:
+                d = torch.device("cuda", self.device.index if self.device.type == "cuda" else torch.cuda.current_device())
+            if d != self.device:
+                raise RuntimeError(f"HipDinov2Model lives on {self.device} (its weights are packed there); cannot move it to {d}")
+        return self
+
+    def manifest(self):
+        lib = L.lib()
+        out, shape, nd = [], (C.c_int64 * 4)(), C.c_int()
+        for i in range(lib.cs_vit_num_weights(self._h)):
+            name = lib.cs_vit_weight_name(self._h, i, shape, C.byref(nd)).decode()
+            out.append((name, tuple(shape[k] for k in range(nd.value))))
+        return out
+
+    def load_state_dict(self, sd, strict=True):
+        lib = L.lib()
+        want = dict(self.manifest())
+        missing = [k for k in want if k not in sd]
+        if missing:
+            raise KeyError(f"missing {len(missing)} tensors, e.g. {missing[:3]}")
+        for name, shape in want.items():
+            t = sd[name].detach().to("cpu", torch.float32).contiguous()
+            if tuple(t.shape) != shape:
+                raise ValueError(f"{name}: shape {tuple(t.shape)} != {shape}")
+            sh = (C.c_int64 * len(shape))(*shape)
+            L.check(lib.cs_vit_set_weight(self._h, name.encode(), C.c_void_p(t.data_ptr()), sh, len(shape)))
+        torch.cuda.set_device(self.device)
+        L.check(lib.cs_vit_finalize(self._h))
+        self._finalized = True
+        return self
+
+    def flops(self, batch):
+        return float(L.lib().cs_vit_flops(self._h, batch))
+
+    # ---- front end ------------------------------------------------------------------------------------------------
+    def preprocess(self, images, return_crop=False):
+        """[B,3,H,W] fp16 / fp32 in [0,1] -> patch rows [B * (crop/patch)^2, patch_cols] fp16 (the encoder's input) and, with ``return_crop``, the resized
+        and center-cropped uint8 image [B,3,crop,crop] (what PIL hands the processor's rescale)."""
+        L.require_cuda(images, "images")
+        if images.dim() != 4 or images.shape[1] != 3:
+            raise ValueError(f"images must be [B,3,H,W], got {tuple(images.shape)}")
+        if images.dtype not in _DT:
+            # ToPILImage multiplies in the tensor's own dtype: a bf16 / fp64 image quantises differently from its fp32 copy, so no silent conversion
+            raise TypeError(f"images must be float16 or float32 (the two quantisation paths that are built), got {images.dtype}")
+        images = images.contiguous()
+        B, _, H, W = images.shape
+        g = self.crop // self.patch
+        patches = torch.empty(B * g * g, self.patch_cols, dtype=torch.float16, device=images.device)
+        crop = torch.empty(B, 3, self.crop, self.crop, dtype=torch.uint8, device=images.device) if return_crop else None
+        if B:
+            lib = L.lib()
+            need = int(lib.cs_vit_preprocess_workspace_bytes(self._h, B, H, W))
+            if self._pws is None or self._pws.numel() < need or self._pws.device != images.device:
+                self._pws = torch.empty(need, dtype=torch.uint8, device=images.device)
+            with torch.cuda.device(images.device):          # the resize tables of a new image size are allocated on the current device
+                L.check(lib.cs_vit_preprocess(self._h, L.ptr(images), _DT[images.dtype], B, H, W, L.ptr(patches), L.ptr(crop), L.ptr(self._pws),
+                                              self._pws.numel(), L.stream_ptr(images.device)))
+        return (patches, crop) if return_crop else patches
+
+    def patches_to_pixel_values(self, patches):
+        """the patch rows back in the processor's layout: ``pixel_values`` [B,3,crop,crop] fp16"""
+        g, P = self.crop // self.patch, self.patch
+        B = patches.shape[0] // (g * g)
+        return patches[:, :3 * P * P].reshape(B, g, g, 3, P, P).permute(0, 3, 1, 4, 2, 5).reshape(B, 3, g * P, g * P)
+
+    def pixel_values_to_patches(self, pixel_values):
+        g, P = self.crop // self.patch, self.patch
+        B = pixel_values.shape[0]
+        if tuple(pixel_values.shape[1:]) != (3, g * P, g * P):
+            raise ValueError(f"pixel_values must be [B,3,{g * P},{g * P}] (the processor's crop), got {tuple(pixel_values.shape)}")
+        rows = pixel_values.to(torch.float16).reshape(B, 3, g, P, g, P).permute(0, 2, 4, 1, 3, 5).reshape(B * g * g, 3 * P * P)
+        out = rows.new_zeros(B * g * g, self.patch_cols)
+        out[:, :3 * P * P] = rows
+        return out
+
+    # ---- encoder --------------------------------------------------------------------------------------------------
+    def encode_patches(self, patches):
+        """patch rows -> CLS features [B, hidden] fp32 (``last_hidden_state[:, 0]`` after the final LayerNorm)"""
+        if not self._finalized:
+            raise RuntimeError("weights not loaded")
+        L.require_cuda(patches, "patches")
+        g = self.crop // self.patch
+        B = patches.shape[0] // (g * g)
+        out = torch.empty(B, self.config["hidden_size"], dtype=torch.float32, device=patches.device)
+        lib = L.lib()
+        for s in range(0, B, self.max_batch):
+            n = min(self.max_batch, B - s)
+            need = int(lib.cs_vit_workspace_bytes(self._h, n))
+            if self._ws is None or self._ws.numel() < need or self._ws.device != patches.device:
+                self._ws = torch.empty(need, dtype=torch.uint8, device=patches.device)
+            L.check(lib.cs_vit_forward(self._h, L.ptr(patches[s * g * g:]), n, L.ptr(out[s:]), L.ptr(self._ws), self._ws.numel(),
+                                       L.stream_ptr(patches.device)))
+        return out
+
+    def image_features(self, images):
+        """[B,3,H,W] in [0,1] -> CLS features [B, hidden] fp32: the whole per-image path of calculate_dino_reward up to F.normalize"""
+        return self.encode_patches(self.preprocess(images))
+
+    @torch.no_grad()
+    def __call__(self, pixel_values=None, **_ignored):
+        """``reward_model(**inputs)`` with the processor's ``pixel_values`` [B,3,crop,crop] -> see ``_VitOutput``"""
+        if pixel_values is None:
+            raise ValueError("You have to specify pixel_values")
+        L.require_cuda(pixel_values, "pixel_values")
+        cls = self.encode_patches(self.pixel_values_to_patches(pixel_values))
+        return _VitOutput((cls.unsqueeze(1), cls))
+
+
+def load_dino_reward(device="cuda:0", config=None):
+    """edit_ppo/reward_model.py:59-64 without the hub: the dinov2-base shapes and processor constants; the caller loads the weights."""
+    processor = DinoImageProcessor()
+    return HipDinov2Model(config, device=device, processor=processor), processor
+
+
+def load_reward_model(reward_type, device="cuda:0", config=None):
+    """edit_ppo/reward_model.py:25-57.  ``image_psnr`` needs no model; ``dino`` is built here; the other backbones are not implemented."""
+    if reward_type == "image_psnr":
+        return None, None
+    if reward_type == "dino":
+        return load_dino_reward(device, config)
+    if reward_type in ("depth", "inception", "segmentation", "clip", "llava", "qwen_vl"):
+        raise NotImplementedError(f"reward_type '{reward_type}' needs a third-party backbone network that is not implemented")
+    raise ValueError(f"Unknown reward_type: {reward_type}")
+
+
+def cosine_reward(pred_features, target_features):
+    """[B,D] fp32 x ([B,D] or [1,D]) -> (cosine_similarity(normalize(a), normalize(b)) + 1) * 50, [B,1] fp32"""
+    L.require_cuda(pred_features, "pred_features")
+    a, b = pred_features.to(torch.float32).contiguous(), target_features.to(torch.float32).contiguous()
+    B, D = a.shape
+    if b.shape not in ((B, D), (1, D)):
+        raise ValueError(f"feature shapes {tuple(a.shape)} vs {tuple(b.shape)}")
+    out = torch.empty(B, 1, dtype=torch.float32, device=a.device)
+    if B:
+        L.check(L.lib().cs_cosine_reward(L.ptr(a), L.ptr(b), B, D, D if (b.shape[0] == B and B > 1) else 0, L.ptr(out), L.stream_ptr(a.device)))
+    return out
+
+
+def calculate_dino_reward(reward_model, reward_model_processor, model_pred, target, device=None):
+    """edit_ppo/reward_model.py:217-257 for the whole batch in one pass: ``model_pred`` [B,3,H,W] and ``target`` [B,3,H,W] (or [1,3,H,W]: one
+    target shared by the batch, its features computed once) in [0,1] -> rewards [B,1] fp32 in [0, 100].  Values outside [0,1] are clamped."""
+    if not isinstance(reward_model, HipDinov2Model):
+        raise TypeError("reward_type 'dino' needs a HipDinov2Model (load_reward_model('dino')); there is no CPU or eager path")
+    if reward_model_processor is not None and reward_model_processor.constants() != reward_model.processor.constants():
+        raise ValueError("the processor's constants differ from the ones the model's front end was built with")
+    L.require_cuda(model_pred, "model_pred")
+    L.require_cuda(target, "target")
+    B = model_pred.shape[0]
+    if target.shape[0] not in (B, 1) or target.shape[1:] != model_pred.shape[1:]:
+        raise ValueError(f"shape mismatch {tuple(model_pred.shape)} vs {tuple(target.shape)}")
+    if target.dtype != model_pred.dtype or target.shape[0] != B:
+        return cosine_reward(reward_model.image_features(model_pred), reward_model.image_features(target))
+    feats = reward_model.image_features(torch.cat([model_pred, target]))            # one front-end and one encoder pass for the 2 B images
+    return cosine_reward(feats[:B], feats[B:])

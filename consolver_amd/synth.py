@@ -47,6 +47,30 @@ def synthetic_clip_state_dict(manifest, seed=20251228):
     return sd
 
 
+def synthetic_dinov2_state_dict(manifest, seed=20251229):
+    """DINOv2 encoder: matrices (the patch projection included) ~ N(0, 1/fan_in), biases and the mask token 0.05 N, LayerScale lambda uniform in
+    [0.05, 1] (trained checkpoints spread over that range; the init value 1.0 would hide a LayerScale that is dropped), CLS token and position
+    table 0.5 N, norm gains 1 + 0.1 N."""
+    g = torch.Generator().manual_seed(seed)
+    sd = {}
+    for name, shape in manifest:
+        if name.endswith("lambda1"):
+            w = 0.05 + 0.95 * torch.rand(shape, generator=g)
+        elif name.endswith("cls_token") or name.endswith("position_embeddings"):
+            w = 0.5 * torch.randn(shape, generator=g)
+        elif name.endswith(".weight") and len(shape) >= 2:
+            fan_in = 1
+            for s in shape[1:]:
+                fan_in *= s
+            w = torch.randn(shape, generator=g) * (1.0 / fan_in) ** 0.5
+        elif "norm" in name and name.endswith(".weight"):
+            w = 1.0 + 0.1 * torch.randn(shape, generator=g)
+        else:
+            w = 0.05 * torch.randn(shape, generator=g)
+        sd[name] = w
+    return sd
+
+
 def synthetic_prompt_embeds(batch, ctx_len=77, dim=768, seed=1001):
     g = torch.Generator().manual_seed(seed)
     x = torch.randn(batch, ctx_len, dim, generator=g)

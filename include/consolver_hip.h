@@ -415,6 +415,59 @@ double cs_clip_flops(const CsClip* c, int batch, int seq_len);
 int cs_clip_encode(CsClip* c, const int64_t* input_ids, int batch, int seq_len, void* out,
                    void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------
+ * DINOv2 image-similarity reward (reward_type "dino": edit_ppo/reward_model.py:217-257;
+ * third-party transformers Dinov2Model + the facebook/dinov2-base image processor).
+ * ---------------------------------------------------------------------- */
+typedef struct CsVitConfig {
+    int hidden_size;               /* 768   */
+    int num_hidden_layers;         /* 12    */
+    int num_attention_heads;       /* 12 (head dim 64) */
+    int mlp_ratio;                 /* 4     */
+    int image_size;                /* 518: the position table's training grid is (image_size / patch_size)^2 */
+    int patch_size;                /* 14    */
+    float layer_norm_eps;          /* 1e-6  */
+    /* the processor's constants */
+    int resize_shortest_edge;      /* 256 (PIL BICUBIC) */
+    int crop_size;                 /* 224 (center crop; the encoder then sees (crop_size / patch_size)^2 + 1 tokens) */
+    float image_mean[3];           /* 0.485, 0.456, 0.406 */
+    float image_std[3];            /* 0.229, 0.224, 0.225 */
+    double rescale_factor;         /* 1 / 255: the processor rescales in double, rounds to fp32, then normalises in fp32 */
+} CsVitConfig;
+
+typedef struct CsVit CsVit;
+
+/* host only: builds the weight manifest, touches no GPU */
+int cs_vit_create(const CsVitConfig* cfg, CsVit** out);
+void cs_vit_destroy(CsVit* v);
+/* tensors by their transformers Dinov2Model state-dict names ("embeddings.cls_token", "encoder.layer.0.attention.attention.query.weight",
+ * "encoder.layer.0.layer_scale1.lambda1", ..., "embeddings.mask_token" included: it is part of the checkpoint, unused by the forward); fp32 host memory */
+int cs_vit_set_weight(CsVit* v, const char* name, const float* data_host, const int64_t* shape, int ndim);
+int cs_vit_num_weights(const CsVit* v);
+const char* cs_vit_weight_name(const CsVit* v, int i, int64_t* shape4, int* ndim);
+int cs_vit_finalize(CsVit* v);
+size_t cs_vit_workspace_bytes(const CsVit* v, int batch);
+double cs_vit_flops(const CsVit* v, int batch);
+/* row length of the patch matrix (3 * patch_size^2 padded to a multiple of 64) and tokens per image */
+int cs_vit_patch_cols(const CsVit* v);
+int cs_vit_num_tokens(const CsVit* v);
+size_t cs_vit_preprocess_workspace_bytes(const CsVit* v, int batch, int height, int width);
+/* images: [batch, 3, height, width] CS_F16 or CS_F32 (device), values clamped to [0, 1].  ToPILImage (x * 255 in the tensor's dtype,
+ * truncated) -> PIL's fixed-point bicubic resize to shortest edge resize_shortest_edge -> center crop -> rescale, normalise.
+ * patches: [batch * (crop/patch)^2, cs_vit_patch_cols] fp16, the encoder's input.  crop_u8 (may be NULL): the resized and cropped
+ * uint8 image [batch, 3, crop, crop], bit-identical to PIL's.  Sizes whose resized image is smaller than the crop: CS_E_UNSUPPORTED.
+ * The first call with a new (height, width) builds that size's tap tables on the host and uploads them (hipMalloc + a synchronous copy on the
+ * current device; not capturable into a graph); the handle keeps the tables of the last 16 sizes at most.  One thread per handle. */
+int cs_vit_preprocess(CsVit* v, const void* images, int dtype, int batch, int height, int width, void* patches,
+                      unsigned char* crop_u8, void* workspace, size_t workspace_bytes, void* stream);
+/* patches from cs_vit_preprocess -> cls_out [batch, hidden] fp32 = last_hidden_state[:, 0] (after the final LayerNorm) */
+int cs_vit_forward(CsVit* v, const void* patches, int batch, float* cls_out, void* workspace, size_t workspace_bytes,
+                   void* stream);
+/* out[b] = (cosine_similarity(normalize(pred[b]), normalize(target[b])) + 1) * 50, all fp32; target rows are target_stride floats
+ * apart (0: one target row for the whole batch) */
+int cs_cosine_reward(const float* pred, const float* target, int batch, int dim, int64_t target_stride, float* out,
+                     void* stream);
+
 #ifdef __cplusplus
 }
 #endif
