@@ -295,6 +295,45 @@ def check(code):
         raise RuntimeError(f"libconsolver_hip: {l.cs_error_string(code).decode()}: {l.cs_last_error().decode()}")
 
 
+# ---- the weight-loading protocol every model handle shares: cs_<prefix>_num_weights / _weight_name / _set_weight / _finalize / _destroy ----
+def manifest(prefix, handle, cap=4):
+    """[(name, shape)] in the handle's state-dict naming; ``cap``: the dims cs_<prefix>_weight_name writes (2 for flux)."""
+    l = lib()
+    out, shape, nd = [], (C.c_int64 * cap)(), C.c_int()
+    for i in range(getattr(l, f"cs_{prefix}_num_weights")(handle)):
+        name = getattr(l, f"cs_{prefix}_weight_name")(handle, i, shape, C.byref(nd)).decode()
+        out.append((name, tuple(shape[k] for k in range(nd.value))))
+    return out
+
+
+def load_float_weights(prefix, handle, state_dict, device, strict=True):
+    """every tensor of the manifest from ``state_dict`` as host fp32 through cs_<prefix>_set_weight, then cs_<prefix>_finalize on ``device``."""
+    l = lib()
+    want = dict(manifest(prefix, handle))
+    missing = [k for k in want if k not in state_dict]
+    if missing and strict:
+        raise KeyError(f"missing {len(missing)} tensors, e.g. {missing[:3]}")
+    set_weight = getattr(l, f"cs_{prefix}_set_weight")
+    for name, shape in want.items():
+        t = state_dict[name].detach().to("cpu", torch.float32).contiguous()
+        if tuple(t.shape) != shape:
+            raise ValueError(f"{name}: shape {tuple(t.shape)} != {shape}")
+        sh = (C.c_int64 * len(shape))(*shape)
+        check(set_weight(handle, name.encode(), C.c_void_p(t.data_ptr()), sh, len(shape)))
+    torch.cuda.set_device(device)
+    check(getattr(l, f"cs_{prefix}_finalize")(handle))
+
+
+def destroy(prefix, obj):
+    """__del__ of a handle-owning object: cs_<prefix>_destroy of ``obj._h``, once; never raises (interpreter shutdown)."""
+    try:
+        if getattr(obj, "_h", None):
+            getattr(lib(), f"cs_{prefix}_destroy")(obj._h)
+            obj._h = None
+    except Exception:
+        pass
+
+
 def dtype_code(dt):
     try:
         return _DT[dt]

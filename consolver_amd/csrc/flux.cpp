@@ -11,12 +11,8 @@
 // torch.cat / split around attention never materialises; in the single-stream blocks attention output and
 // the MLP activation are written side by side (ldc = 5 * hidden) so the cat before proj_out is free as well.
 // All adaLN modulation linears of the 57 blocks are evaluated up front by one weight-streaming tiny-M kernel.
-#include "ops.h"
+#include "weights.h"
 
-#include <map>
-#include <string>
-#include <vector>
-#include <algorithm>
 #include <cstring>
 #include <cmath>
 
@@ -48,11 +44,9 @@ struct Arena2 {
 struct CsFlux {
     CsFluxConfig cfg;
     int D = 0;   // hidden = heads * head_dim
-    std::vector<std::string> names;
-    std::map<std::string, std::vector<int64_t>> expect;
-    std::map<std::string, DevT> raw;
+    WeightManifest manifest;
+    std::map<std::string, DevT> raw;                   // tensors as set, in the model dtype on the device: packed by device-to-device copies
     std::vector<void*> owned;
-    bool finalized = false;
     Lin x_emb, c_emb, proj_out;
     Lin t1, t2, g1, g2, p1, p2;
     u16* mod_w = nullptr; u16* mod_b = nullptr; long mod_total = 0; long mod_final = 0;
@@ -64,7 +58,7 @@ struct CsFlux {
 
 namespace {
 
-void expect(CsFlux* f, const std::string& n, std::vector<int64_t> s) { f->names.push_back(n); f->expect[n] = std::move(s); }
+void expect(CsFlux* f, const std::string& n, std::vector<int64_t> s) { f->manifest.expect(n, std::move(s)); }
 void expect_lin(CsFlux* f, const std::string& p, int n, int k, bool bias = true) { expect(f, p + ".weight", {n, k}); if (bias) expect(f, p + ".bias", {n}); }
 
 void build_manifest(CsFlux* f) {
@@ -94,12 +88,7 @@ void build_manifest(CsFlux* f) {
     expect_lin(f, "proj_out", c.in_channels, D);
 }
 
-u16* dev_alloc(CsFlux* f, size_t elems) {
-    void* d = nullptr;
-    if (hipMalloc(&d, std::max<size_t>(elems * 2, 256)) != hipSuccess) return nullptr;
-    f->owned.push_back(d);
-    return (u16*)d;
-}
+u16* dev_alloc(CsFlux* f, size_t elems) { return (u16*)device_alloc(elems * 2, f->owned); }
 const DevT& R(CsFlux* f, const std::string& n) { return f->raw.at(n); }
 
 // concat rows of several [n_i, k] tensors (and their biases) into one packed Lin, zero padding rows to a multiple of 256
@@ -362,23 +351,14 @@ void cs_flux_destroy(CsFlux* f) {
     delete f;
 }
 
-int cs_flux_num_weights(const CsFlux* f) { return f ? (int)f->names.size() : 0; }
-const char* cs_flux_weight_name(const CsFlux* f, int i, int64_t* shape2, int* ndim) {
-    if (!f || i < 0 || i >= (int)f->names.size()) return nullptr;
-    const auto& sh = f->expect.at(f->names[i]);
-    if (ndim) *ndim = (int)sh.size();
-    if (shape2) for (size_t k = 0; k < 2; ++k) shape2[k] = k < sh.size() ? sh[k] : 1;
-    return f->names[i].c_str();
-}
+int cs_flux_num_weights(const CsFlux* f) { return f ? f->manifest.count() : 0; }
+const char* cs_flux_weight_name(const CsFlux* f, int i, int64_t* shape2, int* ndim) { return f ? f->manifest.name_at(i, shape2, 2, ndim) : nullptr; }
 
 int cs_flux_set_weight(CsFlux* f, const char* name, const void* data, int on_device, const int64_t* shape, int ndim) {
-    if (!f || !name || !data || !shape) CS_FAIL(CS_E_ARG, "null argument");
-    if (f->finalized) CS_FAIL(CS_E_STATE, "weights are already packed");
-    auto it = f->expect.find(name);
-    if (it == f->expect.end()) CS_FAIL(CS_E_ARG, "unexpected tensor name '%s'", name);
-    if ((int)it->second.size() != ndim) CS_FAIL(CS_E_SHAPE, "%s: rank %d, expected %zu", name, ndim, it->second.size());
-    size_t n = 1;
-    for (int k = 0; k < ndim; ++k) { if (shape[k] != it->second[k]) CS_FAIL(CS_E_SHAPE, "%s: dim %d is %lld, expected %lld", name, k, (long long)shape[k], (long long)it->second[k]); n *= (size_t)shape[k]; }
+    if (!f) CS_FAIL(CS_E_ARG, "null argument");
+    size_t n = 0;
+    const int rc = f->manifest.check(name, data, shape, ndim, &n);
+    if (rc != CS_OK) return rc;
     DevT t; t.shape.assign(shape, shape + ndim); t.elems = n;
     CS_CHECK_HIP(hipMalloc(&t.p, std::max<size_t>(n * 2, 256)));
     CS_CHECK_HIP(hipMemcpy(t.p, data, n * 2, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
@@ -390,8 +370,8 @@ int cs_flux_set_weight(CsFlux* f, const char* name, const void* data, int on_dev
 
 int cs_flux_finalize(CsFlux* f) {
     if (!f) CS_FAIL(CS_E_ARG, "null");
-    if (f->finalized) return CS_OK;
-    for (auto& n : f->names) if (!f->raw.count(n)) CS_FAIL(CS_E_STATE, "missing weight '%s'", n.c_str());
+    if (f->manifest.finalized) return CS_OK;
+    if (const std::string* n = f->manifest.first_missing(f->raw)) CS_FAIL(CS_E_STATE, "missing weight '%s'", n->c_str());
     const CsFluxConfig& c = f->cfg; const int D = f->D;
     bool ok = make_lin(f, {"x_embedder"}, f->x_emb) && make_lin(f, {"context_embedder"}, f->c_emb) && make_lin(f, {"proj_out"}, f->proj_out) &&
               make_lin(f, {"time_text_embed.timestep_embedder.linear_1"}, f->t1) && make_lin(f, {"time_text_embed.timestep_embedder.linear_2"}, f->t2) &&
@@ -441,20 +421,20 @@ int cs_flux_finalize(CsFlux* f) {
     if (!ok) CS_FAIL(CS_E_HIP, "flux: weight packing failed (hipMalloc/hipMemcpy)");
     for (auto& kv : f->raw) if (kv.second.p) { hipFree(kv.second.p); kv.second.p = nullptr; }
     f->raw.clear();
-    f->finalized = true;
+    f->manifest.finalized = true;
     return CS_OK;
 }
 
 size_t cs_flux_workspace_bytes(const CsFlux* cf, int batch, int txt_len, int img_len) {
     CsFlux* f = const_cast<CsFlux*>(cf);
-    if (!f || !f->finalized || batch <= 0) return 0;
+    if (!f || !f->manifest.finalized || batch <= 0) return 0;
     flux_forward(f, true, nullptr, batch, img_len, nullptr, txt_len, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr);
     return f->arena.peak + 4096;
 }
 
 double cs_flux_flops(const CsFlux* cf, int batch, int txt_len, int img_len) {
     CsFlux* f = const_cast<CsFlux*>(cf);
-    if (!f || !f->finalized || batch <= 0) return 0;
+    if (!f || !f->manifest.finalized || batch <= 0) return 0;
     flux_forward(f, true, nullptr, batch, img_len, nullptr, txt_len, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr);
     return f->dry_flops;
 }
@@ -463,7 +443,7 @@ int cs_flux_forward(CsFlux* f, const void* hidden_states, int batch, int img_len
                     const float* pooled_f32, const float* timestep, const float* guidance, const float* rope_cos, const float* rope_sin,
                     void* out, void* workspace, size_t workspace_bytes, void* stream) {
     if (!f) CS_FAIL(CS_E_ARG, "flux is NULL");
-    if (!f->finalized) CS_FAIL(CS_E_STATE, "cs_flux_finalize has not been called");
+    if (!f->manifest.finalized) CS_FAIL(CS_E_STATE, "cs_flux_finalize has not been called");
     if (batch <= 0) return batch < 0 ? CS_E_SHAPE : CS_OK;
     if (!hidden_states || !encoder_hidden_states || !pooled_f32 || !timestep || !rope_cos || !rope_sin || !out || !workspace) CS_FAIL(CS_E_ARG, "null pointer");
     if (f->cfg.guidance_embeds && !guidance) CS_FAIL(CS_E_ARG, "guidance is required (guidance_embeds)");
@@ -495,7 +475,7 @@ int cs_flux_forward_joint(CsFlux* f, const void* latents, int lat_len, const voi
                           const void* encoder_hidden_states, int txt_len, const float* pooled_f32, const float* timestep, const float* guidance,
                           const float* rope_cos, const float* rope_sin, void* out, void* workspace, size_t workspace_bytes, void* stream) {
     if (!f) CS_FAIL(CS_E_ARG, "flux is NULL");
-    if (!f->finalized) CS_FAIL(CS_E_STATE, "cs_flux_finalize has not been called");
+    if (!f->manifest.finalized) CS_FAIL(CS_E_STATE, "cs_flux_finalize has not been called");
     if (batch <= 0) return batch < 0 ? CS_E_SHAPE : CS_OK;
     if (!latents || !encoder_hidden_states || !pooled_f32 || !timestep || !rope_cos || !rope_sin || !out || !workspace) CS_FAIL(CS_E_ARG, "null pointer");
     if (f->out_f32 && f->residual != CS_RESIDUAL_F16X2) CS_FAIL(CS_E_STATE, "flux: an fp32 output (cs_flux_set_output_dtype) is the split stream's (CS_RESIDUAL_F16X2)");

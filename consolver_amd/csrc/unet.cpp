@@ -14,12 +14,8 @@
 //   * q/k/v projections fused into one GEMM; cross-attention K/V of the text context (independent of
 //     latents and timestep) cached across solver steps;
 //   * all 22 time_emb_proj layers evaluated by one tiny-M linear over concatenated weights.
-#include "ops.h"
+#include "weights.h"
 
-#include <map>
-#include <string>
-#include <vector>
-#include <algorithm>
 #include <memory>
 #include <cstring>
 #include <cmath>
@@ -67,10 +63,6 @@ void ln_fold_pack_host(const f16* w, const f16* bias, const f16* gamma, const f1
 
 namespace {
 
-struct HostTensor { std::vector<int64_t> shape; std::vector<f16> data; };
-
-struct Conv { f16* w = nullptr; f16* b = nullptr; int cin = 0, cout = 0, taps = 1; f16* w_sub = nullptr; };     // w_sub: an upsampler's sub-pixel filters (IgemmArgs::w_up_sub)
-struct Norm { f16* g = nullptr; f16* b = nullptr; int c = 0; float eps = 1e-5f; };
 struct Resnet { Norm n1, n2; Conv c1, c2, sc; bool has_sc = false; int cin = 0, cout = 0, temb_off = 0; int sc_index = -1; };      // sc_index: position among the shortcut convs in creation order (knob x2_sc_skip)
 struct LnLinear { f16* w = nullptr; float* s = nullptr; float* b = nullptr; };     // a linear layer with the LayerNorm in front of it folded in (IgemmArgs::ln_*)
 struct Xformer {
@@ -137,11 +129,7 @@ const char* kProfNames[P_COUNT] = {"conv3x3_igemm", "gemm_1x1_linear", "attentio
 
 struct CsUNet {
     CsUNetConfig cfg;
-    std::vector<std::string> names;
-    std::map<std::string, std::vector<int64_t>> expect;
-    std::map<std::string, HostTensor> host;
-    std::vector<void*> dev_allocs;
-    bool finalized = false;
+    F16Store weights;                  // host staging in fp16: a tensor is rounded once, when it is set
     // packed
     Conv conv_in, conv_out; Norm norm_out;
     Conv conv_in64;                    // conv_in with the input channels zero-padded to 64 ([Cout][9][64]) for the MFMA path
@@ -170,7 +158,7 @@ struct CsUNet {
 
 namespace {
 
-void expect_tensor(CsUNet* u, const std::string& n, std::vector<int64_t> shape) { u->names.push_back(n); u->expect[n] = std::move(shape); }
+void expect_tensor(CsUNet* u, const std::string& n, std::vector<int64_t> shape) { u->weights.expect(n, std::move(shape)); }
 
 void expect_resnet(CsUNet* u, const std::string& p, int cin, int cout) {
     expect_tensor(u, p + ".norm1.weight", {cin}); expect_tensor(u, p + ".norm1.bias", {cin});
@@ -257,85 +245,51 @@ void build_manifest(CsUNet* u) {
 }
 
 // ------------------------------------------------------------------------- packing helpers
-f16* upload(CsUNet* u, const std::vector<f16>& v) {
-    void* d = nullptr;
-    if (hipMalloc(&d, std::max<size_t>(v.size() * sizeof(f16), 256)) != hipSuccess) return nullptr;
-    if (hipMemcpy(d, v.data(), v.size() * sizeof(f16), hipMemcpyHostToDevice) != hipSuccess) { hipFree(d); return nullptr; }
-    u->dev_allocs.push_back(d);
-    return (f16*)d;
-}
-const HostTensor& T(CsUNet* u, const std::string& n) { return u->host.at(n); }
-
-// [Cout][Cin][kh][kw] -> [Cout][kh*kw][Cin]
-std::vector<f16> pack_conv(const HostTensor& t) {
-    const int64_t co = t.shape[0], ci = t.shape[1], kk = t.shape.size() == 4 ? t.shape[2] * t.shape[3] : 1;
-    std::vector<f16> o((size_t)co * ci * kk);
-    for (int64_t n = 0; n < co; ++n)
-        for (int64_t c = 0; c < ci; ++c)
-            for (int64_t k = 0; k < kk; ++k) o[(n * kk + k) * ci + c] = t.data[(n * ci + c) * kk + k];
-    return o;
-}
-bool make_conv(CsUNet* u, const std::string& p, Conv& c) {
-    const HostTensor& w = T(u, p + ".weight");
-    c.cout = (int)w.shape[0]; c.cin = (int)w.shape[1]; c.taps = w.shape.size() == 4 ? (int)(w.shape[2] * w.shape[3]) : 1;
-    c.w = upload(u, pack_conv(w)); c.b = upload(u, T(u, p + ".bias").data);
-    return c.w && c.b;
-}
-bool make_norm(CsUNet* u, const std::string& p, Norm& n, float eps) {
-    n.c = (int)T(u, p + ".weight").shape[0]; n.eps = eps;
-    n.g = upload(u, T(u, p + ".weight").data); n.b = upload(u, T(u, p + ".bias").data);
-    return n.g && n.b;
-}
-std::vector<f16> concat_rows(std::initializer_list<const HostTensor*> ts) {
+std::vector<f16> concat_rows(std::initializer_list<const HostTensor<f16>*> ts) {
     std::vector<f16> o;
     for (auto t : ts) o.insert(o.end(), t->data.begin(), t->data.end());
     return o;
 }
 bool make_resnet(CsUNet* u, const std::string& p, Resnet& r, std::vector<f16>& tpw, std::vector<f16>& tpb) {
-    bool ok = make_norm(u, p + ".norm1", r.n1, 1e-5f) && make_conv(u, p + ".conv1", r.c1) && make_norm(u, p + ".norm2", r.n2, 1e-5f) &&
-              make_conv(u, p + ".conv2", r.c2);
+    F16Store& W = u->weights;
+    bool ok = make_norm(W, p + ".norm1", r.n1, 1e-5f) && make_conv(W, p + ".conv1", r.c1) && make_norm(W, p + ".norm2", r.n2, 1e-5f) &&
+              make_conv(W, p + ".conv2", r.c2);
     r.cin = r.c1.cin; r.cout = r.c1.cout;
-    r.has_sc = u->host.count(p + ".conv_shortcut.weight") > 0;
-    if (r.has_sc) { ok = ok && make_conv(u, p + ".conv_shortcut", r.sc); r.sc_index = u->n_shortcuts++; }
+    r.has_sc = W.host.count(p + ".conv_shortcut.weight") > 0;
+    if (r.has_sc) { ok = ok && make_conv(W, p + ".conv_shortcut", r.sc); r.sc_index = u->n_shortcuts++; }
     r.temb_off = (int)tpb.size();
-    const HostTensor& tw = T(u, p + ".time_emb_proj.weight");
+    const HostTensor<f16>& tw = W.at(p + ".time_emb_proj.weight");
     tpw.insert(tpw.end(), tw.data.begin(), tw.data.end());
-    const HostTensor& tb = T(u, p + ".time_emb_proj.bias");
+    const HostTensor<f16>& tb = W.at(p + ".time_emb_proj.bias");
     tpb.insert(tpb.end(), tb.data.begin(), tb.data.end());
     return ok;
 }
-float* upload_f32(CsUNet* u, const std::vector<float>& v) {
-    void* d = nullptr;
-    if (hipMalloc(&d, std::max<size_t>(v.size() * sizeof(float), 256)) != hipSuccess) return nullptr;
-    if (hipMemcpy(d, v.data(), v.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) { hipFree(d); return nullptr; }
-    u->dev_allocs.push_back(d);
-    return (float*)d;
-}
 // LN(h) W^T + b = rstd (h W'^T - mean s) + b':  W' = fp16(W diag(gamma)), s = row sums of W' (of the ROUNDED values: it cancels exactly what the MFMAs summed),
 // b' = W beta + b.  w: [N][K] fp16 rows, bias may be empty.
-bool make_ln_linear(CsUNet* u, const std::vector<f16>& w, const std::vector<f16>& bias, const HostTensor& gamma, const HostTensor& beta, int N, int K, LnLinear& out) {
+bool make_ln_linear(F16Store& W, const std::vector<f16>& w, const std::vector<f16>& bias, const HostTensor<f16>& gamma, const HostTensor<f16>& beta, int N, int K, LnLinear& out) {
     std::vector<f16> wf((size_t)N * K);
     std::vector<float> sv(N), bv(N);
     ln_fold_pack_host(w.data(), bias.empty() ? nullptr : bias.data(), gamma.data.data(), beta.data.data(), N, K, wf.data(), sv.data(), bv.data());
-    out.w = upload(u, wf); out.s = upload_f32(u, sv); out.b = upload_f32(u, bv);
+    out.w = W.upload(wf); out.s = W.upload_f32(sv); out.b = W.upload_f32(bv);
     return out.w && out.s && out.b;
 }
 
 bool make_xformer(CsUNet* u, const std::string& p, Xformer& x) {
+    F16Store& W = u->weights;
     const std::string t = p + ".transformer_blocks.0";
-    bool ok = make_norm(u, p + ".norm", x.gn, 1e-6f) && make_conv(u, p + ".proj_in", x.proj_in) && make_conv(u, p + ".proj_out", x.proj_out) &&
-              make_norm(u, t + ".norm1", x.ln1, 1e-5f) && make_norm(u, t + ".norm2", x.ln2, 1e-5f) && make_norm(u, t + ".norm3", x.ln3, 1e-5f);
+    bool ok = make_norm(W, p + ".norm", x.gn, 1e-6f) && make_conv(W, p + ".proj_in", x.proj_in) && make_conv(W, p + ".proj_out", x.proj_out) &&
+              make_norm(W, t + ".norm1", x.ln1, 1e-5f) && make_norm(W, t + ".norm2", x.ln2, 1e-5f) && make_norm(W, t + ".norm3", x.ln3, 1e-5f);
     x.c = x.gn.c;
-    const std::vector<f16> wqkv_h = concat_rows({&T(u, t + ".attn1.to_q.weight"), &T(u, t + ".attn1.to_k.weight"), &T(u, t + ".attn1.to_v.weight")});
-    x.wqkv = upload(u, wqkv_h);
-    ok = ok && make_ln_linear(u, wqkv_h, {}, T(u, t + ".norm1.weight"), T(u, t + ".norm1.bias"), 3 * x.c, x.c, x.f_qkv) &&
-         make_ln_linear(u, T(u, t + ".attn2.to_q.weight").data, {}, T(u, t + ".norm2.weight"), T(u, t + ".norm2.bias"), x.c, x.c, x.f_q2);
-    x.wo1 = upload(u, T(u, t + ".attn1.to_out.0.weight").data); x.bo1 = upload(u, T(u, t + ".attn1.to_out.0.bias").data);
-    x.wq2 = upload(u, T(u, t + ".attn2.to_q.weight").data);
-    x.wkv2 = upload(u, concat_rows({&T(u, t + ".attn2.to_k.weight"), &T(u, t + ".attn2.to_v.weight")}));
-    x.wo2 = upload(u, T(u, t + ".attn2.to_out.0.weight").data); x.bo2 = upload(u, T(u, t + ".attn2.to_out.0.bias").data);
+    const std::vector<f16> wqkv_h = concat_rows({&W.at(t + ".attn1.to_q.weight"), &W.at(t + ".attn1.to_k.weight"), &W.at(t + ".attn1.to_v.weight")});
+    x.wqkv = W.upload(wqkv_h);
+    ok = ok && make_ln_linear(W, wqkv_h, {}, W.at(t + ".norm1.weight"), W.at(t + ".norm1.bias"), 3 * x.c, x.c, x.f_qkv) &&
+         make_ln_linear(W, W.at(t + ".attn2.to_q.weight").data, {}, W.at(t + ".norm2.weight"), W.at(t + ".norm2.bias"), x.c, x.c, x.f_q2);
+    x.wo1 = W.upload(W.at(t + ".attn1.to_out.0.weight").data); x.bo1 = W.upload(W.at(t + ".attn1.to_out.0.bias").data);
+    x.wq2 = W.upload(W.at(t + ".attn2.to_q.weight").data);
+    x.wkv2 = W.upload(concat_rows({&W.at(t + ".attn2.to_k.weight"), &W.at(t + ".attn2.to_v.weight")}));
+    x.wo2 = W.upload(W.at(t + ".attn2.to_out.0.weight").data); x.bo2 = W.upload(W.at(t + ".attn2.to_out.0.bias").data);
     // GEGLU: rows [0,4C) value, [4C,8C) gate  ->  blocks of (16 value | 16 gate) rows
-    const HostTensor& w1 = T(u, t + ".ff.net.0.proj.weight"); const HostTensor& b1 = T(u, t + ".ff.net.0.proj.bias");
+    const HostTensor<f16>& w1 = W.at(t + ".ff.net.0.proj.weight"); const HostTensor<f16>& b1 = W.at(t + ".ff.net.0.proj.bias");
     const int64_t C = x.c, H4 = 4 * C;
     std::vector<f16> pw((size_t)8 * C * C), pb((size_t)8 * C);
     for (int64_t P = 0; P < H4 / 16; ++P)
@@ -344,9 +298,9 @@ bool make_xformer(CsUNet* u, const std::string& p, Xformer& x) {
             std::memcpy(&pw[(32 * P + 16 + i) * C], &w1.data[(H4 + 16 * P + i) * C], C * sizeof(f16));
             pb[32 * P + i] = b1.data[16 * P + i]; pb[32 * P + 16 + i] = b1.data[H4 + 16 * P + i];
         }
-    x.wff1 = upload(u, pw); x.bff1 = upload(u, pb);
-    ok = ok && make_ln_linear(u, pw, pb, T(u, t + ".norm3.weight"), T(u, t + ".norm3.bias"), (int)(8 * C), (int)C, x.f_ff1);      // (row-wise: commutes with the GEGLU row permutation)
-    x.wff2 = upload(u, T(u, t + ".ff.net.2.weight").data); x.bff2 = upload(u, T(u, t + ".ff.net.2.bias").data);
+    x.wff1 = W.upload(pw); x.bff1 = W.upload(pb);
+    ok = ok && make_ln_linear(W, pw, pb, W.at(t + ".norm3.weight"), W.at(t + ".norm3.bias"), (int)(8 * C), (int)C, x.f_ff1);      // (row-wise: commutes with the GEGLU row permutation)
+    x.wff2 = W.upload(W.at(t + ".ff.net.2.weight").data); x.bff2 = W.upload(W.at(t + ".ff.net.2.bias").data);
     x.kv_off = u->kv_halfs_per_token; u->kv_halfs_per_token += 2 * (size_t)x.c;
     x.index = u->n_xformers++;
     return ok && x.wqkv && x.wo1 && x.bo1 && x.wq2 && x.wkv2 && x.wo2 && x.bo2 && x.wff1 && x.bff1 && x.wff2 && x.bff2;
@@ -793,54 +747,32 @@ int cs_unet_create(const CsUNetConfig* cfg, CsUNet** out) {
 
 void cs_unet_destroy(CsUNet* u) {
     if (!u) return;
-    for (void* p : u->dev_allocs) hipFree(p);
+    u->weights.free_device();
     for (auto& e : u->evs) { hipEventDestroy(e.a); hipEventDestroy(e.b); }
     delete u;
 }
 
-int cs_unet_num_weights(const CsUNet* u) { return u ? (int)u->names.size() : 0; }
+int cs_unet_num_weights(const CsUNet* u) { return u ? u->weights.count() : 0; }
 
-const char* cs_unet_weight_name(const CsUNet* u, int i, int64_t* shape4, int* ndim) {
-    if (!u || i < 0 || i >= (int)u->names.size()) return nullptr;
-    const auto& sh = u->expect.at(u->names[i]);
-    if (ndim) *ndim = (int)sh.size();
-    if (shape4) for (size_t k = 0; k < 4; ++k) shape4[k] = k < sh.size() ? sh[k] : 1;
-    return u->names[i].c_str();
-}
+const char* cs_unet_weight_name(const CsUNet* u, int i, int64_t* shape4, int* ndim) { return u ? u->weights.name_at(i, shape4, 4, ndim) : nullptr; }
 
 int cs_unet_set_weight(CsUNet* u, const char* name, const float* data, const int64_t* shape, int ndim) {
-    if (!u || !name || !data || !shape) CS_FAIL(CS_E_ARG, "null argument");
-    if (u->finalized) CS_FAIL(CS_E_STATE, "weights are already packed");
-    auto it = u->expect.find(name);
-    if (it == u->expect.end()) CS_FAIL(CS_E_ARG, "unexpected tensor name '%s'", name);
-    if ((int)it->second.size() != ndim) CS_FAIL(CS_E_SHAPE, "%s: rank %d, expected %zu", name, ndim, it->second.size());
-    int64_t n = 1;
-    for (int k = 0; k < ndim; ++k) { if (shape[k] != it->second[k]) CS_FAIL(CS_E_SHAPE, "%s: dim %d is %lld, expected %lld", name, k, (long long)shape[k], (long long)it->second[k]); n *= shape[k]; }
-    HostTensor t; t.shape.assign(shape, shape + ndim); t.data.resize(n);
-    for (int64_t i = 0; i < n; ++i) t.data[i] = (f16)data[i];
-    u->host[name] = std::move(t);
-    return CS_OK;
+    if (!u) CS_FAIL(CS_E_ARG, "null argument");
+    return u->weights.set(name, data, shape, ndim);
 }
 
 int cs_unet_finalize(CsUNet* u) {
     if (!u) CS_FAIL(CS_E_ARG, "null");
-    if (u->finalized) return CS_OK;
-    for (auto& n : u->names) if (!u->host.count(n)) CS_FAIL(CS_E_STATE, "missing weight '%s'", n.c_str());
+    F16Store& W = u->weights;
+    if (W.finalized) return CS_OK;
+    if (const std::string* n = W.first_missing()) CS_FAIL(CS_E_STATE, "missing weight '%s'", n->c_str());
     const CsUNetConfig& c = u->cfg;
     bool ok = true;
     std::vector<f16> tpw, tpb;
-    ok = ok && make_conv(u, "conv_in", u->conv_in) && make_conv(u, "conv_out", u->conv_out) && make_norm(u, "conv_norm_out", u->norm_out, 1e-5f);
-    {   // [co][ci][3][3] -> [co][9][64], channels >= ci zero
-        const HostTensor& w = T(u, "conv_in.weight");
-        const int64_t co = w.shape[0], ci = w.shape[1];
-        std::vector<f16> o((size_t)co * 9 * 64, (f16)0.f);
-        for (int64_t n = 0; n < co; ++n) for (int64_t ch = 0; ch < ci; ++ch) for (int64_t k = 0; k < 9; ++k) o[(n * 9 + k) * 64 + ch] = w.data[(n * ci + ch) * 9 + k];
-        u->conv_in64.cout = (int)co; u->conv_in64.cin = 64; u->conv_in64.taps = 9;
-        u->conv_in64.w = upload(u, o); u->conv_in64.b = u->conv_in.b;
-        ok = ok && u->conv_in64.w;
-    }
-    u->t_w1 = upload(u, T(u, "time_embedding.linear_1.weight").data); u->t_b1 = upload(u, T(u, "time_embedding.linear_1.bias").data);
-    u->t_w2 = upload(u, T(u, "time_embedding.linear_2.weight").data); u->t_b2 = upload(u, T(u, "time_embedding.linear_2.bias").data);
+    ok = ok && make_conv(W, "conv_in", u->conv_in) && make_conv(W, "conv_out", u->conv_out) && make_norm(W, "conv_norm_out", u->norm_out, 1e-5f);
+    ok = ok && make_conv_padded64(W, "conv_in", u->conv_in64);
+    u->t_w1 = W.upload(W.at("time_embedding.linear_1.weight").data); u->t_b1 = W.upload(W.at("time_embedding.linear_1.bias").data);
+    u->t_w2 = W.upload(W.at("time_embedding.linear_2.weight").data); u->t_b2 = W.upload(W.at("time_embedding.linear_2.bias").data);
     Topology t = topology(c);
     for (int i = 0; i < 4 && ok; ++i) {
         const std::string b = "down_blocks." + std::to_string(i);
@@ -851,7 +783,7 @@ int cs_unet_finalize(CsUNet* u) {
             if (c.down_has_attn[i]) ok = ok && make_xformer(u, b + ".attentions." + std::to_string(j), u->down_att[i][j]);
         }
         u->has_down[i] = i < 3;
-        if (i < 3) ok = ok && make_conv(u, b + ".downsamplers.0.conv", u->down_samp[i]);
+        if (i < 3) ok = ok && make_conv(W, b + ".downsamplers.0.conv", u->down_samp[i]);
     }
     ok = ok && make_resnet(u, "mid_block.resnets.0", u->mid_res[0], tpw, tpb) && make_xformer(u, "mid_block.attentions.0", u->mid_att) &&
          make_resnet(u, "mid_block.resnets.1", u->mid_res[1], tpw, tpb);
@@ -865,28 +797,28 @@ int cs_unet_finalize(CsUNet* u) {
         }
         u->has_up[i] = i < 3;
         if (i < 3) {
-            ok = ok && make_conv(u, b + ".upsamplers.0.conv", u->up_samp[i]);
+            ok = ok && make_conv(W, b + ".upsamplers.0.conv", u->up_samp[i]);
             // the same filter in its sub-pixel form (4 phases x 4 summed taps: 16 / 9 of the bytes), for the forwards that run on one fp16 plane (knob up_fold)
             Conv& uc = u->up_samp[i];
             if (ok && uc.taps == 9 && uc.cout % 160 == 0 && uc.cin % 64 == 0) {
                 std::vector<f16> sub((size_t)4 * uc.cout * 4 * uc.cin);
-                conv_up_fold_pack_host(pack_conv(T(u, b + ".upsamplers.0.conv.weight")).data(), uc.cout, uc.cin, sub.data());
-                uc.w_sub = upload(u, sub);
+                conv_up_fold_pack_host(pack_conv(W.at(b + ".upsamplers.0.conv.weight")).data(), uc.cout, uc.cin, sub.data());
+                uc.w_sub = W.upload(sub);
                 ok = ok && uc.w_sub;
             }
         }
     }
     u->tp_total = (int)tpb.size();
-    u->tp_w = upload(u, tpw); u->tp_b = upload(u, tpb);
+    u->tp_w = W.upload(tpw); u->tp_b = W.upload(tpb);
     if (!ok || !u->t_w1 || !u->t_b1 || !u->t_w2 || !u->t_b2 || !u->tp_w || !u->tp_b) CS_FAIL(CS_E_HIP, "weight upload failed (hipMalloc/hipMemcpy)");
-    u->host.clear();
-    u->finalized = true;
+    W.release_host();
+    W.finalized = true;
     return CS_OK;
 }
 
 size_t cs_unet_workspace_bytes(const CsUNet* cu, int batch) {
     CsUNet* u = const_cast<CsUNet*>(cu);
-    if (!u || !u->finalized || batch <= 0) return 0;
+    if (!u || !u->weights.finalized || batch <= 0) return 0;
     // the arena's peak depends on the execution variant (CFG shared prefix on / off, fused cross-attention block on / off): the workspace
     // covers all of them, whatever the knobs say now, so that toggling a knob later never outgrows a workspace sized earlier
     // (the knobs it does not enumerate come from the process-wide set)
@@ -911,14 +843,14 @@ size_t cs_unet_workspace_bytes(const CsUNet* cu, int batch) {
 
 double cs_unet_flops_executed(const CsUNet* cu, int n_lat, int dup) {
     CsUNet* u = const_cast<CsUNet*>(cu);
-    if (!u || !u->finalized || n_lat <= 0 || (dup != 1 && dup != 2)) return 0;
+    if (!u || !u->weights.finalized || n_lat <= 0 || (dup != 1 && dup != 2)) return 0;
     run_forward(u, handle_tune(u), true, nullptr, n_lat, dup, nullptr, 1, nullptr, nullptr, nullptr, 0, 0, nullptr, true);     // (what THIS handle's forwards execute)
     return u->dry_flops;
 }
 
 double cs_unet_flops(const CsUNet* cu, int batch) {
     CsUNet* u = const_cast<CsUNet*>(cu);
-    if (!u || !u->finalized || batch <= 0) return 0;
+    if (!u || !u->weights.finalized || batch <= 0) return 0;
     run_forward(u, handle_tune(u), true, nullptr, batch, 1, nullptr, 1, nullptr, nullptr, nullptr, 0, 0, nullptr);
     return u->dry_flops;
 }
@@ -926,7 +858,7 @@ double cs_unet_flops(const CsUNet* cu, int batch) {
 int cs_unet_forward(CsUNet* u, const void* latents, int n_lat, int dup, const float* timesteps, int n_timesteps, const void* ctx,
                     void* out, void* workspace, size_t workspace_bytes, int kv_cache_valid, void* stream) {
     if (!u) CS_FAIL(CS_E_ARG, "unet is NULL");
-    if (!u->finalized) CS_FAIL(CS_E_STATE, "cs_unet_finalize has not been called");
+    if (!u->weights.finalized) CS_FAIL(CS_E_STATE, "cs_unet_finalize has not been called");
     if (n_lat < 0 || (dup != 1 && dup != 2)) CS_FAIL(CS_E_ARG, "bad n_lat/dup");
     if (n_lat == 0) return CS_OK;
     if (!latents || !timesteps || !ctx || !out || !workspace) CS_FAIL(CS_E_ARG, "null pointer");
@@ -949,7 +881,7 @@ int cs_unet_forward(CsUNet* u, const void* latents, int n_lat, int dup, const fl
 int cs_unet_calibrate_ln_fold(CsUNet* u, const void* latents, int n_lat, int dup, const float* timesteps, int n_timesteps, const void* ctx, void* out,
                               void* workspace, size_t workspace_bytes, float bound, void* stream, unsigned* mask_out, float* worst_ratio_out) {
     if (!u) CS_FAIL(CS_E_ARG, "unet is NULL");
-    if (!u->finalized) CS_FAIL(CS_E_STATE, "cs_unet_finalize has not been called");
+    if (!u->weights.finalized) CS_FAIL(CS_E_STATE, "cs_unet_finalize has not been called");
     if (n_lat <= 0 || (dup != 1 && dup != 2) || !latents || !timesteps || !ctx || !out || !workspace) CS_FAIL(CS_E_ARG, "calibrate_ln_fold: bad arguments");
     if (n_timesteps != 1 && n_timesteps != n_lat * dup) CS_FAIL(CS_E_SHAPE, "n_timesteps must be 1 or the batch size");
     if (!(bound > 0.f)) CS_FAIL(CS_E_ARG, "calibrate_ln_fold: bound must be positive");
@@ -959,7 +891,7 @@ int cs_unet_calibrate_ln_fold(CsUNet* u, const void* latents, int n_lat, int dup
     if (!u->calib) {
         void* d = nullptr;
         CS_CHECK_HIP(hipMalloc(&d, nslots * sizeof(float)));
-        u->dev_allocs.push_back(d); u->calib = (float*)d;
+        u->weights.dev_allocs.push_back(d); u->calib = (float*)d;
     }
     hipStream_t s = (hipStream_t)stream;
     // measured on the FOLDED graph (every producer of the hidden state leaves its row statistics): the mask is cleared for the calibration forward

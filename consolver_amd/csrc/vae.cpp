@@ -11,23 +11,15 @@
 // GEMM-shaped rather than flash-shaped: scores = Q K^T and O = P V are plain GEMMs through the same
 // kernel, with a row-softmax kernel in between; V is produced directly transposed (V^T = Wv X^T) by
 // swapping the GEMM operand roles, and its bias is applied after P V (rows of P sum to 1).
-#include "ops.h"
+#include "weights.h"
 #include "consolver_hip.h"
 
-#include <map>
-#include <string>
-#include <vector>
-#include <algorithm>
 #include <cmath>
-
 
 namespace {
 
-struct HostT { std::vector<int64_t> shape; std::vector<f16> data; };
-struct VConv { f16* w = nullptr; f16* b = nullptr; int cin = 0, cout = 0, taps = 1; f16* w_sub = nullptr; };     // w_sub: an upsampler's sub-pixel filters (IgemmArgs::w_up_sub)
-struct VNorm { f16* g = nullptr; f16* b = nullptr; int c = 0; };
-struct VResnet { VNorm n1, n2; VConv c1, c2, sc; bool has_sc = false; int cin = 0, cout = 0; };
-struct VAttn { VNorm gn; f16 *wq = nullptr, *bq = nullptr, *wk = nullptr, *bk = nullptr, *wv = nullptr, *bv = nullptr, *wo = nullptr, *bo = nullptr; };
+struct VResnet { Norm n1, n2; Conv c1, c2, sc; bool has_sc = false; int cin = 0, cout = 0; };
+struct VAttn { Norm gn; f16 *wq = nullptr, *bq = nullptr, *wk = nullptr, *bk = nullptr, *wv = nullptr, *bv = nullptr, *wo = nullptr, *bo = nullptr; };
 
 struct VArena {   // bump allocator with explicit stack discipline (mark / rewind)
     char* base = nullptr; size_t cap = 0, top = 0, peak = 0; bool dry = false;
@@ -40,31 +32,28 @@ struct VArena {   // bump allocator with explicit stack discipline (mark / rewin
 };
 
 constexpr int VAE_GN_SPLITS = 256;
+constexpr float VAE_GN_EPS = 1e-6f;      // every GroupNorm of the AutoencoderKL
 
 }  // namespace
 
 struct CsVae {
     CsVaeConfig cfg;
-    std::vector<std::string> names;
-    std::map<std::string, std::vector<int64_t>> expect;
-    std::map<std::string, HostT> host;
-    std::vector<void*> dev_allocs;
-    bool finalized = false;
+    F16Store weights;
     f16 *pq_w = nullptr, *pq_b = nullptr;
-    VConv conv_in, conv_out; VNorm norm_out;
+    Conv conv_in, conv_out; Norm norm_out;
     VResnet mid_res[2];
     VAttn att;
-    std::vector<VResnet> up_res[4]; VConv up_samp[4];
+    std::vector<VResnet> up_res[4]; Conv up_samp[4];
     // encoder (optional, cfg.with_encoder): images -> mode of the latent distribution
-    VConv e_conv_in, e_conv_out; VNorm e_norm_out; VResnet e_mid_res[2]; VAttn e_att;
-    std::vector<VResnet> e_down_res[4]; VConv e_down_samp[4];
+    Conv e_conv_in, e_conv_out; Norm e_norm_out; VResnet e_mid_res[2]; VAttn e_att;
+    std::vector<VResnet> e_down_res[4]; Conv e_down_samp[4];
     f16 *q_w = nullptr, *q_b = nullptr;            // quant_conv rows of the mean half [L][2L], [L]
     VArena arena; double dry_flops = 0;
 };
 
 namespace {
 
-void expect_tensor(CsVae* v, const std::string& n, std::vector<int64_t> shape) { v->names.push_back(n); v->expect[n] = std::move(shape); }
+void expect_tensor(CsVae* v, const std::string& n, std::vector<int64_t> shape) { v->weights.expect(n, std::move(shape)); }
 void expect_resnet(CsVae* v, const std::string& p, int cin, int cout) {
     expect_tensor(v, p + ".norm1.weight", {cin}); expect_tensor(v, p + ".norm1.bias", {cin});
     expect_tensor(v, p + ".conv1.weight", {cout, cin, 3, 3}); expect_tensor(v, p + ".conv1.bias", {cout});
@@ -116,61 +105,22 @@ void build_manifest(CsVae* v) {
     expect_tensor(v, "decoder.conv_out.weight", {c.out_channels, c0, 3, 3}); expect_tensor(v, "decoder.conv_out.bias", {c.out_channels});
 }
 
-f16* upload(CsVae* v, const std::vector<f16>& h) {
-    void* d = nullptr;
-    if (hipMalloc(&d, std::max<size_t>(h.size() * sizeof(f16), 256)) != hipSuccess) return nullptr;
-    if (hipMemcpy(d, h.data(), h.size() * sizeof(f16), hipMemcpyHostToDevice) != hipSuccess) { hipFree(d); return nullptr; }
-    v->dev_allocs.push_back(d);
-    return (f16*)d;
-}
-const HostT& T(CsVae* v, const std::string& n) { return v->host.at(n); }
-
-std::vector<f16> pack_conv(const HostT& t) {   // [Cout][Cin][kh][kw] -> [Cout][kh*kw][Cin]
-    const int64_t co = t.shape[0], ci = t.shape[1], kk = t.shape.size() == 4 ? t.shape[2] * t.shape[3] : 1;
-    std::vector<f16> o((size_t)co * ci * kk);
-    for (int64_t n = 0; n < co; ++n)
-        for (int64_t c = 0; c < ci; ++c)
-            for (int64_t k = 0; k < kk; ++k) o[(n * kk + k) * ci + c] = t.data[(n * ci + c) * kk + k];
-    return o;
-}
-bool make_conv(CsVae* v, const std::string& p, VConv& c) {
-    const HostT& w = T(v, p + ".weight");
-    c.cout = (int)w.shape[0]; c.cin = (int)w.shape[1]; c.taps = w.shape.size() == 4 ? (int)(w.shape[2] * w.shape[3]) : 1;
-    c.w = upload(v, pack_conv(w)); c.b = upload(v, T(v, p + ".bias").data);
-    return c.w && c.b;
-}
-bool make_norm(CsVae* v, const std::string& p, VNorm& n) {
-    n.c = (int)T(v, p + ".weight").shape[0];
-    n.g = upload(v, T(v, p + ".weight").data); n.b = upload(v, T(v, p + ".bias").data);
-    return n.g && n.b;
-}
-bool make_resnet(CsVae* v, const std::string& p, VResnet& r) {
-    bool ok = make_norm(v, p + ".norm1", r.n1) && make_conv(v, p + ".conv1", r.c1) && make_norm(v, p + ".norm2", r.n2) && make_conv(v, p + ".conv2", r.c2);
+bool make_resnet(F16Store& W, const std::string& p, VResnet& r) {
+    bool ok = make_norm(W, p + ".norm1", r.n1, VAE_GN_EPS) && make_conv(W, p + ".conv1", r.c1) && make_norm(W, p + ".norm2", r.n2, VAE_GN_EPS) && make_conv(W, p + ".conv2", r.c2);
     r.cin = r.c1.cin; r.cout = r.c1.cout;
-    r.has_sc = v->host.count(p + ".conv_shortcut.weight") > 0;
-    if (r.has_sc) ok = ok && make_conv(v, p + ".conv_shortcut", r.sc);
+    r.has_sc = W.host.count(p + ".conv_shortcut.weight") > 0;
+    if (r.has_sc) ok = ok && make_conv(W, p + ".conv_shortcut", r.sc);
     return ok;
 }
 
-bool make_attn(CsVae* v, const std::string& a, VAttn& t) {
-    bool ok = make_norm(v, a + ".group_norm", t.gn);
-    t.wq = upload(v, T(v, a + ".to_q.weight").data); t.bq = upload(v, T(v, a + ".to_q.bias").data);
-    t.wk = upload(v, T(v, a + ".to_k.weight").data); t.bk = upload(v, T(v, a + ".to_k.bias").data);
-    t.wv = upload(v, T(v, a + ".to_v.weight").data); t.bv = upload(v, T(v, a + ".to_v.bias").data);
-    t.wo = upload(v, T(v, a + ".to_out.0.weight").data); t.bo = upload(v, T(v, a + ".to_out.0.bias").data);
+bool make_attn(F16Store& W, const std::string& a, VAttn& t) {
+    bool ok = make_norm(W, a + ".group_norm", t.gn, VAE_GN_EPS);
+    t.wq = W.upload(W.at(a + ".to_q.weight").data); t.bq = W.upload(W.at(a + ".to_q.bias").data);
+    t.wk = W.upload(W.at(a + ".to_k.weight").data); t.bk = W.upload(W.at(a + ".to_k.bias").data);
+    t.wv = W.upload(W.at(a + ".to_v.weight").data); t.bv = W.upload(W.at(a + ".to_v.bias").data);
+    t.wo = W.upload(W.at(a + ".to_out.0.weight").data); t.bo = W.upload(W.at(a + ".to_out.0.bias").data);
     return ok && t.wq && t.bq && t.wk && t.bk && t.wv && t.bv && t.wo && t.bo;
 }
-// 3x3 conv whose few input channels are zero-padded to 64 (the operand then arrives as NHWC-64): [co][ci][3][3] -> [co][9][64]
-bool make_conv_padded64(CsVae* v, const std::string& p, VConv& c) {
-    const HostT& w = T(v, p + ".weight");
-    const int64_t co = w.shape[0], ci = w.shape[1];
-    std::vector<f16> o((size_t)co * 9 * 64, (f16)0.f);
-    for (int64_t n = 0; n < co; ++n) for (int64_t ch = 0; ch < ci; ++ch) for (int64_t k = 0; k < 9; ++k) o[(n * 9 + k) * 64 + ch] = w.data[(n * ci + ch) * 9 + k];
-    c.cout = (int)co; c.cin = 64; c.taps = 9;
-    c.w = upload(v, o); c.b = upload(v, T(v, p + ".bias").data);
-    return c.w && c.b;
-}
-
 struct Run {
     CsVae* v; hipStream_t s; bool dry; int B; int rc = CS_OK;
     float* gn_ws = nullptr;
@@ -204,7 +154,7 @@ struct Run {
         if (dry) { v->dry_flops += flops; return; }
         if (rc == CS_OK) rc = f();
     }
-    void conv(const VConv& c, const f16* x, int H, int W, int up, const f16* res, f16* out) {
+    void conv(const Conv& c, const f16* x, int H, int W, int up, const f16* res, f16* out) {
         IgemmArgs a{};
         a.a0 = x; a.c0 = c.cin; a.B = B; a.Hi = H; a.Wi = W; a.Ho = up ? 2 * H : H; a.Wo = up ? 2 * W : W; a.taps = c.taps; a.stride = 1;
         a.upsample = up; a.N = c.cout; a.w = c.w; a.bias = c.b; a.res = res; a.out = out;
@@ -215,7 +165,7 @@ struct Run {
         a.gn_stats = c.taps == 9 ? stats_for_output(out, a.Ho * a.Wo, c.cout) : nullptr;
         launch(igemm_flops(a), [&] { return launch_igemm(a, s); });             // (a kernel without a statistics epilogue is followed by a statistics pass in the same layout)
     }
-    void conv_down(const VConv& c, const f16* x, int H, int W, f16* out) {       // pad (0,1,0,1) + 3x3 stride 2 (encoder downsample)
+    void conv_down(const Conv& c, const f16* x, int H, int W, f16* out) {       // pad (0,1,0,1) + 3x3 stride 2 (encoder downsample)
         IgemmArgs a{};
         a.a0 = x; a.c0 = c.cin; a.B = B; a.Hi = H; a.Wi = W; a.Ho = H / 2; a.Wo = W / 2; a.taps = 9; a.stride = 2; a.pad_after_only = 1;
         a.N = c.cout; a.w = c.w; a.bias = c.b; a.out = out;
@@ -228,9 +178,9 @@ struct Run {
         forget_stats(out);
         launch(igemm_flops(a), [&] { return launch_igemm(a, s); });
     }
-    void group_norm(const VNorm& n, const f16* x, int HW, bool silu, f16* out) {
+    void group_norm(const Norm& n, const f16* x, int HW, bool silu, f16* out) {
         GroupNormArgs a{};
-        a.x0 = x; a.c0 = n.c; a.B = B; a.HW = HW; a.groups = v->cfg.norm_num_groups; a.eps = 1e-6f; a.silu = silu;
+        a.x0 = x; a.c0 = n.c; a.B = B; a.HW = HW; a.groups = v->cfg.norm_num_groups; a.eps = n.eps; a.silu = silu;
         a.gamma = n.g; a.beta = n.b; a.partial = gn_ws; a.out = out; a.splits = VAE_GN_SPLITS;
         int S = 0;
         if (const float* st = stats_of(x, &S)) { a.stats0 = st; a.S0 = S; }
@@ -395,104 +345,87 @@ int cs_vae_create(const CsVaeConfig* cfg, CsVae** out) {
 
 void cs_vae_destroy(CsVae* v) {
     if (!v) return;
-    for (void* p : v->dev_allocs) hipFree(p);
+    v->weights.free_device();
     delete v;
 }
 
-int cs_vae_num_weights(const CsVae* v) { return v ? (int)v->names.size() : 0; }
+int cs_vae_num_weights(const CsVae* v) { return v ? v->weights.count() : 0; }
 
-const char* cs_vae_weight_name(const CsVae* v, int i, int64_t* shape4, int* ndim) {
-    if (!v || i < 0 || i >= (int)v->names.size()) return nullptr;
-    const auto& sh = v->expect.at(v->names[i]);
-    if (ndim) *ndim = (int)sh.size();
-    if (shape4) for (size_t k = 0; k < 4; ++k) shape4[k] = k < sh.size() ? sh[k] : 1;
-    return v->names[i].c_str();
-}
+const char* cs_vae_weight_name(const CsVae* v, int i, int64_t* shape4, int* ndim) { return v ? v->weights.name_at(i, shape4, 4, ndim) : nullptr; }
 
 int cs_vae_set_weight(CsVae* v, const char* name, const float* data, const int64_t* shape, int ndim) {
-    if (!v || !name || !data || !shape) CS_FAIL(CS_E_ARG, "null argument");
-    if (v->finalized) CS_FAIL(CS_E_STATE, "weights are already packed");
-    auto it = v->expect.find(name);
-    if (it == v->expect.end()) CS_FAIL(CS_E_ARG, "unexpected tensor name '%s'", name);
-    if ((int)it->second.size() != ndim) CS_FAIL(CS_E_SHAPE, "%s: rank %d, expected %zu", name, ndim, it->second.size());
-    int64_t n = 1;
-    for (int k = 0; k < ndim; ++k) {
-        if (shape[k] != it->second[k]) CS_FAIL(CS_E_SHAPE, "%s: dim %d is %lld, expected %lld", name, k, (long long)shape[k], (long long)it->second[k]);
-        n *= shape[k];
-    }
-    HostT t; t.shape.assign(shape, shape + ndim); t.data.resize(n);
-    for (int64_t i = 0; i < n; ++i) t.data[i] = (f16)data[i];
-    v->host[name] = std::move(t);
-    return CS_OK;
+    if (!v) CS_FAIL(CS_E_ARG, "null argument");
+    return v->weights.set(name, data, shape, ndim);
 }
 
 int cs_vae_finalize(CsVae* v) {
     if (!v) CS_FAIL(CS_E_ARG, "null");
-    if (v->finalized) return CS_OK;
-    for (auto& n : v->names) if (!v->host.count(n)) CS_FAIL(CS_E_STATE, "missing weight '%s'", n.c_str());
+    F16Store& W = v->weights;
+    if (W.finalized) return CS_OK;
+    if (const std::string* n = W.first_missing()) CS_FAIL(CS_E_STATE, "missing weight '%s'", n->c_str());
     bool ok = true;
-    if (v->cfg.use_post_quant_conv) { v->pq_w = upload(v, T(v, "post_quant_conv.weight").data); v->pq_b = upload(v, T(v, "post_quant_conv.bias").data); ok = v->pq_w && v->pq_b; }
-    if (v->cfg.latent_channels != 4) ok = ok && make_conv_padded64(v, "decoder.conv_in", v->conv_in);
-    else ok = ok && make_conv(v, "decoder.conv_in", v->conv_in);
-    ok = ok && make_conv(v, "decoder.conv_out", v->conv_out) && make_norm(v, "decoder.conv_norm_out", v->norm_out);
-    ok = ok && make_resnet(v, "decoder.mid_block.resnets.0", v->mid_res[0]) && make_resnet(v, "decoder.mid_block.resnets.1", v->mid_res[1]);
-    ok = ok && make_attn(v, "decoder.mid_block.attentions.0", v->att);
+    if (v->cfg.use_post_quant_conv) { v->pq_w = W.upload(W.at("post_quant_conv.weight").data); v->pq_b = W.upload(W.at("post_quant_conv.bias").data); ok = v->pq_w && v->pq_b; }
+    if (v->cfg.latent_channels != 4) ok = ok && make_conv_padded64(W, "decoder.conv_in", v->conv_in);
+    else ok = ok && make_conv(W, "decoder.conv_in", v->conv_in);
+    ok = ok && make_conv(W, "decoder.conv_out", v->conv_out) && make_norm(W, "decoder.conv_norm_out", v->norm_out, VAE_GN_EPS);
+    ok = ok && make_resnet(W, "decoder.mid_block.resnets.0", v->mid_res[0]) && make_resnet(W, "decoder.mid_block.resnets.1", v->mid_res[1]);
+    ok = ok && make_attn(W, "decoder.mid_block.attentions.0", v->att);
     for (int i = 0; i < 4 && ok; ++i) {
         const std::string b = "decoder.up_blocks." + std::to_string(i);
         v->up_res[i].resize(v->cfg.layers_per_block + 1);
-        for (size_t j = 0; j < v->up_res[i].size() && ok; ++j) ok = ok && make_resnet(v, b + ".resnets." + std::to_string(j), v->up_res[i][j]);
+        for (size_t j = 0; j < v->up_res[i].size() && ok; ++j) ok = ok && make_resnet(W, b + ".resnets." + std::to_string(j), v->up_res[i][j]);
         if (i < 3) {
-            ok = ok && make_conv(v, b + ".upsamplers.0.conv", v->up_samp[i]);
-            VConv& uc = v->up_samp[i];
+            ok = ok && make_conv(W, b + ".upsamplers.0.conv", v->up_samp[i]);
+            Conv& uc = v->up_samp[i];
             if (ok && uc.taps == 9 && (uc.cout % 160 == 0 || uc.cout % 128 == 0) && uc.cin % 64 == 0) {
                 std::vector<f16> sub((size_t)4 * uc.cout * 4 * uc.cin);
-                conv_up_fold_pack_host(pack_conv(T(v, b + ".upsamplers.0.conv.weight")).data(), uc.cout, uc.cin, sub.data());
-                uc.w_sub = upload(v, sub);
+                conv_up_fold_pack_host(pack_conv(W.at(b + ".upsamplers.0.conv.weight")).data(), uc.cout, uc.cin, sub.data());
+                uc.w_sub = W.upload(sub);
                 ok = ok && uc.w_sub;
             }
         }
     }
     if (v->cfg.with_encoder && ok) {
         const int L = v->cfg.latent_channels;
-        ok = make_conv_padded64(v, "encoder.conv_in", v->e_conv_in) && make_norm(v, "encoder.conv_norm_out", v->e_norm_out) &&
-             make_resnet(v, "encoder.mid_block.resnets.0", v->e_mid_res[0]) && make_resnet(v, "encoder.mid_block.resnets.1", v->e_mid_res[1]) &&
-             make_attn(v, "encoder.mid_block.attentions.0", v->e_att);
+        ok = make_conv_padded64(W, "encoder.conv_in", v->e_conv_in) && make_norm(W, "encoder.conv_norm_out", v->e_norm_out, VAE_GN_EPS) &&
+             make_resnet(W, "encoder.mid_block.resnets.0", v->e_mid_res[0]) && make_resnet(W, "encoder.mid_block.resnets.1", v->e_mid_res[1]) &&
+             make_attn(W, "encoder.mid_block.attentions.0", v->e_att);
         for (int i = 0; i < 4 && ok; ++i) {
             const std::string b = "encoder.down_blocks." + std::to_string(i);
             v->e_down_res[i].resize(v->cfg.layers_per_block);
-            for (size_t j = 0; j < v->e_down_res[i].size() && ok; ++j) ok = ok && make_resnet(v, b + ".resnets." + std::to_string(j), v->e_down_res[i][j]);
-            if (i < 3) ok = ok && make_conv(v, b + ".downsamplers.0.conv", v->e_down_samp[i]);
+            for (size_t j = 0; j < v->e_down_res[i].size() && ok; ++j) ok = ok && make_resnet(W, b + ".resnets." + std::to_string(j), v->e_down_res[i][j]);
+            if (i < 3) ok = ok && make_conv(W, b + ".downsamplers.0.conv", v->e_down_samp[i]);
         }
         // conv_out: with quant_conv every one of the 2L moments feeds the mean; without it only the mean half is needed
-        const HostT& w = T(v, "encoder.conv_out.weight"); const HostT& bb = T(v, "encoder.conv_out.bias");
+        const HostTensor<f16>& w = W.at("encoder.conv_out.weight"); const HostTensor<f16>& bb = W.at("encoder.conv_out.bias");
         const int rows = v->cfg.use_quant_conv ? 2 * L : L;
-        HostT wt; wt.shape = {rows, w.shape[1], 3, 3}; wt.data.assign(w.data.begin(), w.data.begin() + (size_t)rows * w.shape[1] * 9);
+        HostTensor<f16> wt; wt.shape = {rows, w.shape[1], 3, 3}; wt.data.assign(w.data.begin(), w.data.begin() + (size_t)rows * w.shape[1] * 9);
         v->e_conv_out.cout = rows; v->e_conv_out.cin = (int)w.shape[1]; v->e_conv_out.taps = 9;
-        v->e_conv_out.w = upload(v, pack_conv(wt)); v->e_conv_out.b = upload(v, std::vector<f16>(bb.data.begin(), bb.data.begin() + rows));
+        v->e_conv_out.w = W.upload(pack_conv(wt)); v->e_conv_out.b = W.upload(std::vector<f16>(bb.data.begin(), bb.data.begin() + rows));
         ok = ok && v->e_conv_out.w && v->e_conv_out.b;
         if (v->cfg.use_quant_conv) {
-            const HostT& qw = T(v, "quant_conv.weight"); const HostT& qb = T(v, "quant_conv.bias");
-            v->q_w = upload(v, std::vector<f16>(qw.data.begin(), qw.data.begin() + (size_t)L * 2 * L));
-            v->q_b = upload(v, std::vector<f16>(qb.data.begin(), qb.data.begin() + L));
+            const HostTensor<f16>& qw = W.at("quant_conv.weight"); const HostTensor<f16>& qb = W.at("quant_conv.bias");
+            v->q_w = W.upload(std::vector<f16>(qw.data.begin(), qw.data.begin() + (size_t)L * 2 * L));
+            v->q_b = W.upload(std::vector<f16>(qb.data.begin(), qb.data.begin() + L));
             ok = ok && v->q_w && v->q_b;
         }
     }
     if (!ok) CS_FAIL(CS_E_HIP, "vae: weight upload failed (hipMalloc/hipMemcpy)");
-    v->host.clear();
-    v->finalized = true;
+    W.release_host();
+    W.finalized = true;
     return CS_OK;
 }
 
 size_t cs_vae_workspace_bytes(const CsVae* cv, int batch) {
     CsVae* v = const_cast<CsVae*>(cv);
-    if (!v || !v->finalized || batch <= 0) return 0;
+    if (!v || !v->weights.finalized || batch <= 0) return 0;
     run_decode(v, true, nullptr, batch, 1.f, 0.f, nullptr, 0, nullptr, 0, nullptr);
     return gn_ws_bytes(v, batch) + v->arena.peak + 4096;
 }
 
 double cs_vae_flops(const CsVae* cv, int batch) {
     CsVae* v = const_cast<CsVae*>(cv);
-    if (!v || !v->finalized || batch <= 0) return 0;
+    if (!v || !v->weights.finalized || batch <= 0) return 0;
     run_decode(v, true, nullptr, batch, 1.f, 0.f, nullptr, 0, nullptr, 0, nullptr);
     return v->dry_flops;
 }
@@ -500,7 +433,7 @@ double cs_vae_flops(const CsVae* cv, int batch) {
 int cs_vae_decode(CsVae* v, const void* latents, int batch, float in_scale, float in_shift, void* images, int postprocess, void* workspace,
                   size_t workspace_bytes, void* stream) {
     if (!v) CS_FAIL(CS_E_ARG, "vae is NULL");
-    if (!v->finalized) CS_FAIL(CS_E_STATE, "cs_vae_finalize has not been called");
+    if (!v->weights.finalized) CS_FAIL(CS_E_STATE, "cs_vae_finalize has not been called");
     if (batch < 0) CS_FAIL(CS_E_ARG, "negative batch");
     if (batch == 0) return CS_OK;
     if (!latents || !images || !workspace) CS_FAIL(CS_E_ARG, "null pointer");
@@ -512,7 +445,7 @@ int cs_vae_decode(CsVae* v, const void* latents, int batch, float in_scale, floa
 
 size_t cs_vae_encode_workspace_bytes(const CsVae* cv, int batch) {
     CsVae* v = const_cast<CsVae*>(cv);
-    if (!v || !v->finalized || !v->cfg.with_encoder || batch <= 0) return 0;
+    if (!v || !v->weights.finalized || !v->cfg.with_encoder || batch <= 0) return 0;
     run_encode(v, true, nullptr, batch, 1.f, 0.f, nullptr, nullptr, 0, nullptr);
     return gn_ws_bytes(v, batch) + v->arena.peak + 4096;
 }
@@ -520,7 +453,7 @@ size_t cs_vae_encode_workspace_bytes(const CsVae* cv, int batch) {
 int cs_vae_encode(CsVae* v, const void* images, int batch, float out_scale, float out_shift, void* latents, void* workspace, size_t workspace_bytes,
                   void* stream) {
     if (!v) CS_FAIL(CS_E_ARG, "vae is NULL");
-    if (!v->finalized) CS_FAIL(CS_E_STATE, "cs_vae_finalize has not been called");
+    if (!v->weights.finalized) CS_FAIL(CS_E_STATE, "cs_vae_finalize has not been called");
     if (!v->cfg.with_encoder) CS_FAIL(CS_E_STATE, "vae: created without the encoder (cfg.with_encoder = 0)");
     if (batch < 0) CS_FAIL(CS_E_ARG, "negative batch");
     if (batch == 0) return CS_OK;

@@ -3,33 +3,23 @@
 // Replaces, for a batch of decoded images [B,3,H,W] in [0,1]:  ToPILImage -> the facebook/dinov2-base processor (PIL bicubic resize to shortest edge 256, center
 // crop 224, rescale, normalise) -> transformers Dinov2Model (14 x 14 patch conv, CLS token, position table bicubically interpolated from its 37 x 37 training grid,
 // 12 pre-LN layers with LayerScale and exact GELU, final LayerNorm) -> CLS row -> F.normalize / cosine_similarity -> (cos + 1) * 50.
-// The encoder is clip.cpp's layer loop (implicit-GEMM MFMA linears, flash attention at head dim 64 -- here unmasked, 257 tokens) with the LayerScale vectors folded
+// The encoder is encoder.h's layer loop (implicit-GEMM MFMA linears, flash attention at head dim 64 -- here unmasked, 257 tokens) with the LayerScale vectors folded
 // into the out-projection / fc2 weights and biases at pack time (fp32 product, one rounding to fp16); the front end and the tail are vit_ops.hip.
-#include "ops.h"
+#include "encoder.h"
 #include "consolver_hip.h"
 
-#include <map>
-#include <string>
-#include <vector>
-#include <algorithm>
 #include <cmath>
 
 namespace {
-struct HostT { std::vector<int64_t> shape; std::vector<float> data; };
-struct Layer { f16 *ln1g, *ln1b, *wqkv, *bqkv, *wo, *bo, *ln2g, *ln2b, *w1, *b1, *w2, *b2; };
 struct Plan { VitResizePlan dev; };
 }
 
 struct CsVit {
     CsVitConfig cfg;
     int G = 0, NP = 0, T = 0, K = 0, Kpad = 0, I = 0;      // patch grid of the crop, patches, tokens, patch-row length (and padded), MLP width
-    std::vector<std::string> names;
-    std::map<std::string, std::vector<int64_t>> expect;
-    std::map<std::string, HostT> host;
-    std::vector<void*> dev_allocs;
-    bool finalized = false;
+    WeightStore<float> weights;                            // fp32 staging: the LayerScale product is formed in fp32 and rounded once at upload
     f16 *wpatch = nullptr, *bpatch = nullptr, *cls = nullptr, *pos = nullptr, *lnfg = nullptr, *lnfb = nullptr;
-    std::vector<Layer> layers;
+    std::vector<PreLnLayer> layers;
     // resize tables per input (height, width), at most MAX_PLANS of them (a directory of many image sizes must not grow device memory without bound: when the
     // cache is full it is emptied -- hipFree waits for the kernels that still read a table).  Like every handle here a CsVit serves one thread at a time, and the
     // tables live on the device that is current when a size is first seen: callers run a handle on one device (the Python wrapper selects the tensor's).
@@ -40,46 +30,27 @@ struct CsVit {
 
 namespace {
 
-void expect_tensor(CsVit* c, const std::string& n, std::vector<int64_t> shape) { c->names.push_back(n); c->expect[n] = std::move(shape); }
-
 void build_manifest(CsVit* c) {          // transformers Dinov2Model.state_dict() order
+    WeightManifest& m = c->weights;
     const int D = c->cfg.hidden_size, I = c->I, P = c->cfg.patch_size, g = c->cfg.image_size / P;
-    expect_tensor(c, "embeddings.cls_token", {1, 1, D});
-    expect_tensor(c, "embeddings.mask_token", {1, D});                                   // in the published count; pre-training only, unused by the forward
-    expect_tensor(c, "embeddings.position_embeddings", {1, (int64_t)g * g + 1, D});
-    expect_tensor(c, "embeddings.patch_embeddings.projection.weight", {D, 3, P, P});
-    expect_tensor(c, "embeddings.patch_embeddings.projection.bias", {D});
+    m.expect("embeddings.cls_token", {1, 1, D});
+    m.expect("embeddings.mask_token", {1, D});                                   // in the published count; pre-training only, unused by the forward
+    m.expect("embeddings.position_embeddings", {1, (int64_t)g * g + 1, D});
+    m.expect("embeddings.patch_embeddings.projection.weight", {D, 3, P, P});
+    m.expect("embeddings.patch_embeddings.projection.bias", {D});
     for (int l = 0; l < c->cfg.num_hidden_layers; ++l) {
         const std::string p = "encoder.layer." + std::to_string(l);
-        expect_tensor(c, p + ".norm1.weight", {D}); expect_tensor(c, p + ".norm1.bias", {D});
+        m.expect(p + ".norm1.weight", {D}); m.expect(p + ".norm1.bias", {D});
         for (const char* q : {".attention.attention.query", ".attention.attention.key", ".attention.attention.value", ".attention.output.dense"}) {
-            expect_tensor(c, p + q + ".weight", {D, D}); expect_tensor(c, p + q + ".bias", {D});
+            m.expect(p + q + ".weight", {D, D}); m.expect(p + q + ".bias", {D});
         }
-        expect_tensor(c, p + ".layer_scale1.lambda1", {D});
-        expect_tensor(c, p + ".norm2.weight", {D}); expect_tensor(c, p + ".norm2.bias", {D});
-        expect_tensor(c, p + ".mlp.fc1.weight", {I, D}); expect_tensor(c, p + ".mlp.fc1.bias", {I});
-        expect_tensor(c, p + ".mlp.fc2.weight", {D, I}); expect_tensor(c, p + ".mlp.fc2.bias", {D});
-        expect_tensor(c, p + ".layer_scale2.lambda1", {D});
+        m.expect(p + ".layer_scale1.lambda1", {D});
+        m.expect(p + ".norm2.weight", {D}); m.expect(p + ".norm2.bias", {D});
+        m.expect(p + ".mlp.fc1.weight", {I, D}); m.expect(p + ".mlp.fc1.bias", {I});
+        m.expect(p + ".mlp.fc2.weight", {D, I}); m.expect(p + ".mlp.fc2.bias", {D});
+        m.expect(p + ".layer_scale2.lambda1", {D});
     }
-    expect_tensor(c, "layernorm.weight", {D}); expect_tensor(c, "layernorm.bias", {D});
-}
-
-f16* upload(CsVit* c, const std::vector<float>& h) {
-    std::vector<f16> t(h.size());
-    for (size_t i = 0; i < h.size(); ++i) t[i] = (f16)h[i];
-    void* d = nullptr;
-    if (hipMalloc(&d, std::max<size_t>(t.size() * sizeof(f16), 256)) != hipSuccess) return nullptr;
-    if (hipMemcpy(d, t.data(), t.size() * sizeof(f16), hipMemcpyHostToDevice) != hipSuccess) { hipFree(d); return nullptr; }
-    c->dev_allocs.push_back(d);
-    return (f16*)d;
-}
-const std::vector<float>& T(CsVit* c, const std::string& n) { return c->host.at(n).data; }
-
-// rows of w [N][K] (and b [N]) times lambda[N]: LayerScale folded into the linear layer in front of it
-std::vector<float> scale_rows(const std::vector<float>& w, const std::vector<float>& lam, int K) {
-    std::vector<float> o(w.size());
-    for (size_t i = 0; i < w.size(); ++i) o[i] = w[i] * lam[i / K];
-    return o;
+    m.expect("layernorm.weight", {D}); m.expect("layernorm.bias", {D});
 }
 
 // torch F.interpolate(mode="bicubic", align_corners=False) of the [s][s][D] position grid to [g][g][D] (cubic convolution, A = -0.75, clamped reads)
@@ -173,12 +144,6 @@ int get_plan(CsVit* c, int H, int W, const Plan** out) {
     return CS_OK;
 }
 
-int linear(const f16* x, int M, int K, const f16* w, const f16* b, int N, const f16* res, f16* out, hipStream_t s) {
-    IgemmArgs a{};
-    a.a0 = x; a.c0 = K; a.B = 1; a.Hi = M; a.Wi = 1; a.Ho = M; a.Wo = 1; a.taps = 1; a.stride = 1; a.N = N; a.w = w; a.bias = b; a.res = res; a.out = out;
-    return launch_igemm(a, s);
-}
-
 }  // namespace
 
 extern "C" {
@@ -203,81 +168,54 @@ int cs_vit_create(const CsVitConfig* cfg, CsVit** out) {
 
 void cs_vit_destroy(CsVit* c) {
     if (!c) return;
-    for (void* p : c->dev_allocs) (void)hipFree(p);
+    c->weights.free_device();
     for (void* p : c->plan_allocs) (void)hipFree(p);
     delete c;
 }
 
-int cs_vit_num_weights(const CsVit* c) { return c ? (int)c->names.size() : 0; }
+int cs_vit_num_weights(const CsVit* c) { return c ? c->weights.count() : 0; }
 
-const char* cs_vit_weight_name(const CsVit* c, int i, int64_t* shape4, int* ndim) {
-    if (!c || i < 0 || i >= (int)c->names.size()) return nullptr;
-    const auto& sh = c->expect.at(c->names[i]);
-    if (ndim) *ndim = (int)sh.size();
-    if (shape4) for (size_t k = 0; k < 4; ++k) shape4[k] = k < sh.size() ? sh[k] : 1;
-    return c->names[i].c_str();
-}
+const char* cs_vit_weight_name(const CsVit* c, int i, int64_t* shape4, int* ndim) { return c ? c->weights.name_at(i, shape4, 4, ndim) : nullptr; }
 
 int cs_vit_set_weight(CsVit* c, const char* name, const float* data, const int64_t* shape, int ndim) {
-    if (!c || !name || !data || !shape) CS_FAIL(CS_E_ARG, "null argument");
-    if (c->finalized) CS_FAIL(CS_E_STATE, "weights are already packed");
-    auto it = c->expect.find(name);
-    if (it == c->expect.end()) CS_FAIL(CS_E_ARG, "unexpected tensor name '%s'", name);
-    if ((int)it->second.size() != ndim) CS_FAIL(CS_E_SHAPE, "%s: rank %d, expected %zu", name, ndim, it->second.size());
-    int64_t n = 1;
-    for (int k = 0; k < ndim; ++k) {
-        if (shape[k] != it->second[k]) CS_FAIL(CS_E_SHAPE, "%s: dim %d is %lld, expected %lld", name, k, (long long)shape[k], (long long)it->second[k]);
-        n *= shape[k];
-    }
-    HostT t; t.shape.assign(shape, shape + ndim); t.data.assign(data, data + n);
-    c->host[name] = std::move(t);
-    return CS_OK;
+    if (!c) CS_FAIL(CS_E_ARG, "null argument");
+    return c->weights.set(name, data, shape, ndim);
 }
 
 int cs_vit_finalize(CsVit* c) {
     if (!c) CS_FAIL(CS_E_ARG, "null");
-    if (c->finalized) return CS_OK;
-    for (auto& n : c->names) if (!c->host.count(n)) CS_FAIL(CS_E_STATE, "missing weight '%s'", n.c_str());
-    const int D = c->cfg.hidden_size, I = c->I, K = c->K, Kpad = c->Kpad, s = c->cfg.image_size / c->cfg.patch_size, G = c->G;
+    WeightStore<float>& W = c->weights;
+    if (W.finalized) return CS_OK;
+    if (const std::string* n = W.first_missing()) CS_FAIL(CS_E_STATE, "missing weight '%s'", n->c_str());
+    auto T = [&](const char* n) -> const std::vector<float>& { return W.at(n).data; };
+    const int D = c->cfg.hidden_size, K = c->K, Kpad = c->Kpad, s = c->cfg.image_size / c->cfg.patch_size, G = c->G;
     {   // patch projection [D][3 P P] -> [D][Kpad]
-        const auto& w = T(c, "embeddings.patch_embeddings.projection.weight");
+        const auto& w = T("embeddings.patch_embeddings.projection.weight");
         std::vector<float> wp((size_t)D * Kpad, 0.f);
         for (int n = 0; n < D; ++n) std::copy(w.begin() + (size_t)n * K, w.begin() + (size_t)(n + 1) * K, wp.begin() + (size_t)n * Kpad);
-        c->wpatch = upload(c, wp); c->bpatch = upload(c, T(c, "embeddings.patch_embeddings.projection.bias"));
+        c->wpatch = W.upload(wp); c->bpatch = W.upload(T("embeddings.patch_embeddings.projection.bias"));
     }
     {   // position table of the crop's grid: the class row as is (pre-added to the CLS token in fp32), the patch grid interpolated when the crop is not the training size
-        const auto& pos = T(c, "embeddings.position_embeddings");
-        const auto& cls = T(c, "embeddings.cls_token");
+        const auto& pos = T("embeddings.position_embeddings");
+        const auto& cls = T("embeddings.cls_token");
         std::vector<float> cls0(D), table((size_t)c->T * D, 0.f);
         for (int d = 0; d < D; ++d) cls0[d] = cls[d] + pos[d];
         if (G == s) std::copy(pos.begin() + D, pos.end(), table.begin() + D);
         else { const auto g = interpolate_positions(pos.data() + D, s, G, D); std::copy(g.begin(), g.end(), table.begin() + D); }
-        c->cls = upload(c, cls0); c->pos = upload(c, table);
+        c->cls = W.upload(cls0); c->pos = W.upload(table);
     }
-    c->lnfg = upload(c, T(c, "layernorm.weight")); c->lnfb = upload(c, T(c, "layernorm.bias"));
+    c->lnfg = W.upload(T("layernorm.weight")); c->lnfb = W.upload(T("layernorm.bias"));
     bool ok = c->wpatch && c->bpatch && c->cls && c->pos && c->lnfg && c->lnfb;
     c->layers.resize(c->cfg.num_hidden_layers);
     for (int l = 0; l < c->cfg.num_hidden_layers && ok; ++l) {
         const std::string p = "encoder.layer." + std::to_string(l);
-        Layer& L = c->layers[l];
-        std::vector<float> w, b;
-        for (const char* q : {".attention.attention.query", ".attention.attention.key", ".attention.attention.value"}) {       // fused [3D, D]
-            const auto& tw = T(c, p + q + ".weight"); w.insert(w.end(), tw.begin(), tw.end());
-            const auto& tb = T(c, p + q + ".bias"); b.insert(b.end(), tb.begin(), tb.end());
-        }
-        L.wqkv = upload(c, w); L.bqkv = upload(c, b);
-        const auto& l1 = T(c, p + ".layer_scale1.lambda1");
-        const auto& l2 = T(c, p + ".layer_scale2.lambda1");
-        L.wo = upload(c, scale_rows(T(c, p + ".attention.output.dense.weight"), l1, D)); L.bo = upload(c, scale_rows(T(c, p + ".attention.output.dense.bias"), l1, 1));
-        L.ln1g = upload(c, T(c, p + ".norm1.weight")); L.ln1b = upload(c, T(c, p + ".norm1.bias"));
-        L.ln2g = upload(c, T(c, p + ".norm2.weight")); L.ln2b = upload(c, T(c, p + ".norm2.bias"));
-        L.w1 = upload(c, T(c, p + ".mlp.fc1.weight")); L.b1 = upload(c, T(c, p + ".mlp.fc1.bias"));
-        L.w2 = upload(c, scale_rows(T(c, p + ".mlp.fc2.weight"), l2, I)); L.b2 = upload(c, scale_rows(T(c, p + ".mlp.fc2.bias"), l2, 1));
-        ok = L.wqkv && L.bqkv && L.wo && L.bo && L.ln1g && L.ln1b && L.ln2g && L.ln2b && L.w1 && L.b1 && L.w2 && L.b2;
+        ok = pack_pre_ln_layer<float>(W, {p + ".attention.attention.query", p + ".attention.attention.key", p + ".attention.attention.value", p + ".attention.output.dense",
+                                          p + ".norm1", p + ".norm2", p + ".mlp.fc1", p + ".mlp.fc2"},
+                                      &W.at(p + ".layer_scale1.lambda1").data, &W.at(p + ".layer_scale2.lambda1").data, c->layers[l]);
     }
     if (!ok) CS_FAIL(CS_E_HIP, "vit: weight upload failed (hipMalloc/hipMemcpy)");
-    c->host.clear();
-    c->finalized = true;
+    W.release_host();
+    W.finalized = true;
     return CS_OK;
 }
 
@@ -286,14 +224,14 @@ int cs_vit_num_tokens(const CsVit* c) { return c ? c->T : 0; }
 
 size_t cs_vit_workspace_bytes(const CsVit* c, int batch) {
     if (!c || batch <= 0) return 0;
-    const size_t rows = (size_t)batch * c->T, D = c->cfg.hidden_size;
-    return (rows * (D + D + 3 * D + c->I) + (size_t)batch * c->NP * D) * sizeof(f16) + 4096;       // x, normed, qkv (attention output reuses normed), mlp, patch embeddings
+    const size_t D = c->cfg.hidden_size;
+    return (pre_ln_workspace_elems((size_t)batch * c->T, D, c->I) + (size_t)batch * c->NP * D) * sizeof(f16) + 4096;       // the encoder stack's, patch embeddings
 }
 
 double cs_vit_flops(const CsVit* c, int batch) {
     if (!c) return 0;
-    const double rows = (double)batch * c->T, D = c->cfg.hidden_size, I = c->I;
-    return 2.0 * batch * c->NP * (double)c->K * D + c->cfg.num_hidden_layers * (2.0 * rows * D * (4 * D + 2 * I) + 4.0 * batch * (double)c->T * c->T * D);
+    const double D = c->cfg.hidden_size;
+    return 2.0 * batch * c->NP * (double)c->K * D + pre_ln_flops(c->cfg.num_hidden_layers, batch, c->T, D, c->I);
 }
 
 size_t cs_vit_preprocess_workspace_bytes(const CsVit* c, int batch, int height, int width) {
@@ -317,7 +255,7 @@ int cs_vit_preprocess(CsVit* c, const void* images, int dtype, int batch, int he
 
 int cs_vit_forward(CsVit* c, const void* patches, int batch, float* cls_out, void* workspace, size_t workspace_bytes, void* stream) {
     if (!c) CS_FAIL(CS_E_ARG, "vit is NULL");
-    if (!c->finalized) CS_FAIL(CS_E_STATE, "cs_vit_finalize has not been called");
+    if (!c->weights.finalized) CS_FAIL(CS_E_STATE, "cs_vit_finalize has not been called");
     if (batch < 0) CS_FAIL(CS_E_ARG, "negative size");
     if (batch == 0) return CS_OK;
     if (!patches || !cls_out || !workspace) CS_FAIL(CS_E_ARG, "null pointer");
@@ -326,26 +264,12 @@ int cs_vit_forward(CsVit* c, const void* patches, int batch, float* cls_out, voi
     hipStream_t s = (hipStream_t)stream;
     const int D = c->cfg.hidden_size, I = c->I, H = c->cfg.num_attention_heads, Tn = c->T;
     const long rows = (long)batch * Tn;
-    f16* x = (f16*)workspace; f16* n = x + rows * D; f16* qkv = n + rows * D; f16* h = qkv + rows * 3 * D; f16* pe = h + rows * I;
+    const PreLnWorkspace w = carve_pre_ln(workspace, rows, D, I);
+    f16* pe = w.end;
     int rc = linear((const f16*)patches, batch * c->NP, c->Kpad, c->wpatch, c->bpatch, D, nullptr, pe, s);
-    if (rc == CS_OK) rc = launch_vit_tokens(pe, c->cls, c->pos, x, batch, c->NP, D, s);
-    for (int l = 0; l < c->cfg.num_hidden_layers && rc == CS_OK; ++l) {
-        const Layer& L = c->layers[l];
-        rc = launch_layer_norm(x, L.ln1g, L.ln1b, n, (int)rows, D, c->cfg.layer_norm_eps, s);
-        if (rc == CS_OK) rc = linear(n, (int)rows, D, L.wqkv, L.bqkv, 3 * D, nullptr, qkv, s);
-        if (rc == CS_OK) {
-            AttnArgs a{};
-            a.q = qkv; a.q_stride = 3 * D; a.k = qkv + D; a.k_stride = 3 * D; a.v = qkv + 2 * D; a.v_stride = 3 * D; a.out = n; a.out_stride = D;
-            a.B = batch; a.H = H; a.Nq = Tn; a.Nk = Tn; a.dh = 64; a.scale = 0.125f;
-            rc = launch_attention(a, s);
-        }
-        if (rc == CS_OK) rc = linear(n, (int)rows, D, L.wo, L.bo, D, x, x, s);                          // lambda1 folded; + residual
-        if (rc == CS_OK) rc = launch_layer_norm(x, L.ln2g, L.ln2b, n, (int)rows, D, c->cfg.layer_norm_eps, s);
-        if (rc == CS_OK) rc = linear(n, (int)rows, D, L.w1, L.b1, I, nullptr, h, s);
-        if (rc == CS_OK) rc = launch_gelu_erf(h, rows * I, s);
-        if (rc == CS_OK) rc = linear(h, (int)rows, I, L.w2, L.b2, D, x, x, s);                          // lambda2 folded; + residual
-    }
-    if (rc == CS_OK) rc = launch_vit_cls_layer_norm(x, (long)Tn * D, c->lnfg, c->lnfb, c->cfg.layer_norm_eps, batch, D, cls_out, s);
+    if (rc == CS_OK) rc = launch_vit_tokens(pe, c->cls, c->pos, w.x, batch, c->NP, D, s);
+    if (rc == CS_OK) rc = run_pre_ln_layers(c->layers, w, batch, Tn, D, I, H, c->cfg.layer_norm_eps, 0, launch_gelu_erf, s);
+    if (rc == CS_OK) rc = launch_vit_cls_layer_norm(w.x, (long)Tn * D, c->lnfg, c->lnfb, c->cfg.layer_norm_eps, batch, D, cls_out, s);
     return rc;
 }
 

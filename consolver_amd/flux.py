@@ -110,20 +110,10 @@ class HipFluxTransformer2DModel:
         return self
 
     def __del__(self):
-        try:
-            if getattr(self, "_h", None):
-                L.lib().cs_flux_destroy(self._h)
-                self._h = None
-        except Exception:
-            pass
+        L.destroy("flux", self)
 
     def manifest(self):
-        lib = L.lib()
-        out, shape, nd = [], (C.c_int64 * 2)(), C.c_int()
-        for i in range(lib.cs_flux_num_weights(self._h)):
-            name = lib.cs_flux_weight_name(self._h, i, shape, C.byref(nd)).decode()
-            out.append((name, tuple(shape[k] for k in range(nd.value))))
-        return out
+        return L.manifest("flux", self._h, cap=2)
 
     def set_weight(self, name, tensor):
         """tensor: torch tensor (cpu or cuda) of the manifest shape; converted to the model dtype."""
@@ -136,10 +126,11 @@ class HipFluxTransformer2DModel:
         missing = [k for k in want if k not in sd]
         if missing and strict:
             raise KeyError(f"missing {len(missing)} tensors, e.g. {missing[:3]}")
-        torch.cuda.set_device(self.device)
-        for name, shape in want.items():
+        for name, shape in want.items():             # every shape before the first device allocation
             if tuple(sd[name].shape) != shape:
                 raise ValueError(f"{name}: shape {tuple(sd[name].shape)} != {shape}")
+        torch.cuda.set_device(self.device)
+        for name in want:
             self.set_weight(name, sd[name])
         return self.finalize()
 

@@ -72,12 +72,7 @@ class HipDinov2Model:
         self.patch_cols, self.num_tokens = int(L.lib().cs_vit_patch_cols(h)), int(L.lib().cs_vit_num_tokens(h))
 
     def __del__(self):
-        try:
-            if getattr(self, "_h", None):
-                L.lib().cs_vit_destroy(self._h)
-                self._h = None
-        except Exception:
-            pass
+        L.destroy("vit", self)
 
     # reference call sites: reward_model.eval(); reward_model.to(device)
     def eval(self):
@@ -93,27 +88,10 @@ class HipDinov2Model:
         return self
 
     def manifest(self):
-        lib = L.lib()
-        out, shape, nd = [], (C.c_int64 * 4)(), C.c_int()
-        for i in range(lib.cs_vit_num_weights(self._h)):
-            name = lib.cs_vit_weight_name(self._h, i, shape, C.byref(nd)).decode()
-            out.append((name, tuple(shape[k] for k in range(nd.value))))
-        return out
+        return L.manifest("vit", self._h)
 
     def load_state_dict(self, sd, strict=True):
-        lib = L.lib()
-        want = dict(self.manifest())
-        missing = [k for k in want if k not in sd]
-        if missing:
-            raise KeyError(f"missing {len(missing)} tensors, e.g. {missing[:3]}")
-        for name, shape in want.items():
-            t = sd[name].detach().to("cpu", torch.float32).contiguous()
-            if tuple(t.shape) != shape:
-                raise ValueError(f"{name}: shape {tuple(t.shape)} != {shape}")
-            sh = (C.c_int64 * len(shape))(*shape)
-            L.check(lib.cs_vit_set_weight(self._h, name.encode(), C.c_void_p(t.data_ptr()), sh, len(shape)))
-        torch.cuda.set_device(self.device)
-        L.check(lib.cs_vit_finalize(self._h))
+        L.load_float_weights("vit", self._h, sd, self.device)
         self._finalized = True
         return self
 

@@ -46,36 +46,14 @@ class HipCLIPTextModel:
         self._finalized = False
 
     def __del__(self):
-        try:
-            if getattr(self, "_h", None):
-                L.lib().cs_clip_destroy(self._h)
-                self._h = None
-        except Exception:
-            pass
+        L.destroy("clip", self)
 
     def manifest(self):
-        lib = L.lib()
-        out, shape, nd = [], (C.c_int64 * 4)(), C.c_int()
-        for i in range(lib.cs_clip_num_weights(self._h)):
-            name = lib.cs_clip_weight_name(self._h, i, shape, C.byref(nd)).decode()
-            out.append((name, tuple(shape[k] for k in range(nd.value))))
-        return out
+        return L.manifest("clip", self._h)
 
     def load_state_dict(self, sd, strict=True):
         sd = {(k[len("text_model."):] if k.startswith("text_model.") else k): v for k, v in sd.items()}
-        lib = L.lib()
-        want = dict(self.manifest())
-        missing = [k for k in want if k not in sd]
-        if missing:
-            raise KeyError(f"missing {len(missing)} tensors, e.g. {missing[:3]}")
-        for name, shape in want.items():
-            t = sd[name].detach().to("cpu", torch.float32).contiguous()
-            if tuple(t.shape) != shape:
-                raise ValueError(f"{name}: shape {tuple(t.shape)} != {shape}")
-            sh = (C.c_int64 * len(shape))(*shape)
-            L.check(lib.cs_clip_set_weight(self._h, name.encode(), C.c_void_p(t.data_ptr()), sh, len(shape)))
-        torch.cuda.set_device(self.device)
-        L.check(lib.cs_clip_finalize(self._h))
+        L.load_float_weights("clip", self._h, sd, self.device)
         self._finalized = True
         return self
 

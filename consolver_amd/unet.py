@@ -127,39 +127,15 @@ class HipUNet2DConditionModel:
         self.invalidate_kv()
 
     def __del__(self):
-        try:
-            if getattr(self, "_h", None):
-                L.lib().cs_unet_destroy(self._h)
-                self._h = None
-        except Exception:
-            pass
+        L.destroy("unet", self)
 
     # ------------------------------------------------------------------ weights
     def manifest(self):
         """[(name, shape)] in diffusers state-dict naming."""
-        lib = L.lib()
-        out = []
-        shape = (C.c_int64 * 4)()
-        nd = C.c_int()
-        for i in range(lib.cs_unet_num_weights(self._h)):
-            name = lib.cs_unet_weight_name(self._h, i, shape, C.byref(nd)).decode()
-            out.append((name, tuple(shape[k] for k in range(nd.value))))
-        return out
+        return L.manifest("unet", self._h)
 
     def load_state_dict(self, sd, strict=True):
-        lib = L.lib()
-        want = dict(self.manifest())
-        missing = [k for k in want if k not in sd]
-        if missing and strict:
-            raise KeyError(f"missing {len(missing)} tensors, e.g. {missing[:3]}")
-        for name, shape in want.items():
-            t = sd[name].detach().to("cpu", torch.float32).contiguous()
-            if tuple(t.shape) != shape:
-                raise ValueError(f"{name}: shape {tuple(t.shape)} != {shape}")
-            sh = (C.c_int64 * len(shape))(*shape)
-            L.check(lib.cs_unet_set_weight(self._h, name.encode(), C.c_void_p(t.data_ptr()), sh, len(shape)))
-        torch.cuda.set_device(self.device)
-        L.check(lib.cs_unet_finalize(self._h))
+        L.load_float_weights("unet", self._h, sd, self.device, strict=strict)
         self._finalized = True
         return self
 

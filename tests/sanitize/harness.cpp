@@ -1,8 +1,10 @@
 // Sanitizer harness for the HOST side of libconsolver_hip (the reference has no sanitizer story; this is ours).
-// Built by tests/test_sanitize_host.py with -fsanitize=address,undefined -fno-gpu-sanitize from the real unet.cpp / vae.cpp / flux.cpp / clip.cpp / ops_api.cpp / api.cpp
-// plus tests/sanitize/stubs.cpp (host malloc as device memory, launch stubs that touch every tensor's first and last byte).  Drives, without a GPU:
+// Built by tests/test_sanitize_host.py with -fsanitize=address,undefined -fno-gpu-sanitize from the real unet.cpp / vae.cpp / flux.cpp / clip.cpp / vit.cpp / ops_api.cpp /
+// api.cpp (and through them weights.h, the weight store of every handle, and encoder.h, the CLIP / ViT layer loop) plus tests/sanitize/stubs.cpp (host malloc as
+// device memory, launch stubs that touch every tensor's first and last byte).  Drives, without a GPU:
 //   weight registration and repacking, finalize, the dry-run workspace sizing (every execution variant, both residual-stream modes), forwards through the
-//   first-fit arena with a workspace of EXACTLY the size the library asked for, the profiling event pool, and the error paths.
+//   first-fit arena with a workspace of EXACTLY the size the library asked for, the profiling event pool, and the error paths;
+//   the CLIP and ViT handles at their smallest legal shapes; a finalize with one weight missing on each of the five handles.
 #include "../../include/consolver_hip.h"
 #include "../../include/consolver_hip_ops.h"
 #include <cstdio>
@@ -15,12 +17,44 @@ extern "C" int g_stub_fail_memcpy_async;       // stubs.cpp
 static int g_fail = 0;
 #define EXPECT(cond) do { if (!(cond)) { fprintf(stderr, "FAIL %s:%d: %s  (last error: %s)\n", __FILE__, __LINE__, #cond, cs_last_error()); ++g_fail; } } while (0)
 
-static void unet_part() {
+static CsUNetConfig unet_config() {
     CsUNetConfig c{};
     c.in_channels = 4; c.out_channels = 4;
     const int boc[4] = {320, 320, 640, 640};
     for (int i = 0; i < 4; ++i) { c.block_out_channels[i] = boc[i]; c.down_has_attn[i] = i < 3; c.up_has_attn[i] = i > 0; }
     c.layers_per_block = 1; c.num_heads = 8; c.cross_attention_dim = 768; c.norm_num_groups = 32; c.sample_size = 32; c.ctx_len = 77;
+    return c;
+}
+static CsVaeConfig vae_config() {
+    CsVaeConfig c{};
+    c.latent_channels = 4; c.out_channels = 3;
+    const int boc[4] = {128, 128, 256, 256};
+    for (int i = 0; i < 4; ++i) c.block_out_channels[i] = boc[i];
+    c.layers_per_block = 1; c.norm_num_groups = 32; c.sample_size = 16; c.use_post_quant_conv = 1; c.with_encoder = 1; c.use_quant_conv = 1;
+    return c;
+}
+static CsFluxConfig flux_config() {
+    CsFluxConfig c{};
+    c.in_channels = 64; c.num_layers = 2; c.num_single_layers = 2; c.num_heads = 2; c.head_dim = 128; c.joint_attention_dim = 256; c.pooled_projection_dim = 64;
+    c.guidance_embeds = 1; c.axes_dims_rope[0] = 16; c.axes_dims_rope[1] = 56; c.axes_dims_rope[2] = 56; c.dtype = CS_BF16;
+    return c;
+}
+// CLIP and ViT at the smallest shapes their create accepts: hidden 128 = 2 heads of 64, 2 layers, MLP width 128
+static CsClipConfig clip_config() {
+    CsClipConfig c{};
+    c.vocab_size = 50; c.hidden_size = 128; c.intermediate_size = 128; c.num_hidden_layers = 2; c.num_attention_heads = 2; c.max_position_embeddings = 8; c.layer_norm_eps = 1e-5f;
+    return c;
+}
+static CsVitConfig vit_config() {
+    CsVitConfig c{};
+    c.hidden_size = 128; c.num_hidden_layers = 2; c.num_attention_heads = 2; c.mlp_ratio = 1; c.image_size = 28; c.patch_size = 14; c.layer_norm_eps = 1e-6f;
+    c.resize_shortest_edge = 28; c.crop_size = 28; c.rescale_factor = 1.0 / 255;
+    for (int i = 0; i < 3; ++i) { c.image_mean[i] = 0.5f; c.image_std[i] = 0.25f; }
+    return c;
+}
+
+static void unet_part() {
+    CsUNetConfig c = unet_config();
     CsUNet* u = nullptr;
     EXPECT(cs_unet_create(nullptr, &u) != CS_OK);
     CsUNetConfig bad = c; bad.block_out_channels[1] = 100;
@@ -154,11 +188,7 @@ static void unet_part() {
 }
 
 static void vae_part() {
-    CsVaeConfig c{};
-    c.latent_channels = 4; c.out_channels = 3;
-    const int boc[4] = {128, 128, 256, 256};
-    for (int i = 0; i < 4; ++i) c.block_out_channels[i] = boc[i];
-    c.layers_per_block = 1; c.norm_num_groups = 32; c.sample_size = 16; c.use_post_quant_conv = 1; c.with_encoder = 1; c.use_quant_conv = 1;
+    const CsVaeConfig c = vae_config();
     CsVae* v = nullptr;
     EXPECT(cs_vae_create(&c, &v) == CS_OK);
     if (!v) return;
@@ -194,9 +224,7 @@ static void vae_part() {
 }
 
 static void flux_part() {
-    CsFluxConfig c{};
-    c.in_channels = 64; c.num_layers = 2; c.num_single_layers = 2; c.num_heads = 2; c.head_dim = 128; c.joint_attention_dim = 256; c.pooled_projection_dim = 64;
-    c.guidance_embeds = 1; c.axes_dims_rope[0] = 16; c.axes_dims_rope[1] = 56; c.axes_dims_rope[2] = 56; c.dtype = CS_BF16;
+    const CsFluxConfig c = flux_config();
     CsFlux* f = nullptr;
     EXPECT(cs_flux_create(&c, &f) == CS_OK);
     if (!f) return;
@@ -240,6 +268,156 @@ static void flux_part() {
     cs_flux_destroy(f);
 }
 
+// the sequence every float handle goes through before its first run: the error paths of set_weight on a real tensor, every weight set, finalize (twice), a set
+// after finalize.  set(name, data, shape, ndim) and finalize() are the handle's own entry points
+template <typename NameAt, typename Set, typename Finalize>
+static void load_all_weights(int n, NameAt name_at, Set set, Finalize finalize) {
+    int64_t shape[4]; int nd = 0;
+    std::vector<float> buf;
+    EXPECT(n > 10 && name_at(-1, shape, &nd) == nullptr && name_at(n, shape, &nd) == nullptr);
+    for (int i = 0; i < n; ++i) {
+        const char* name = name_at(i, shape, &nd);
+        size_t cnt = 1; for (int k = 0; k < nd; ++k) cnt *= (size_t)shape[k];
+        buf.assign(cnt, 0.01f);
+        if (i == 3) {
+            int64_t wrong[4] = {shape[0] + 1, shape[1], shape[2], shape[3]};
+            EXPECT(set(name, buf.data(), wrong, nd) == CS_E_SHAPE);
+            EXPECT(set(name, buf.data(), shape, nd + 1) == CS_E_SHAPE);
+            EXPECT(set("no.such.tensor", buf.data(), shape, nd) == CS_E_ARG);
+            EXPECT(set(name, nullptr, shape, nd) == CS_E_ARG && set(nullptr, buf.data(), shape, nd) == CS_E_ARG && set(name, buf.data(), nullptr, nd) == CS_E_ARG);
+        }
+        EXPECT(set(name, buf.data(), shape, nd) == CS_OK);
+    }
+    EXPECT(finalize() == CS_OK && finalize() == CS_OK);
+    const char* first = name_at(0, shape, &nd);
+    buf.assign(1 << 16, 0.f);
+    EXPECT(set(first, buf.data(), shape, nd) == CS_E_STATE);          // packed already
+}
+
+static void clip_part() {
+    const CsClipConfig c = clip_config();
+    CsClip* h = nullptr;
+    CsClipConfig bad = c; bad.hidden_size = 192;
+    EXPECT(cs_clip_create(&bad, &h) != CS_OK && cs_clip_create(nullptr, &h) != CS_OK);
+    EXPECT(cs_clip_create(&c, &h) == CS_OK);
+    if (!h) return;
+    const int B = 2, T = 8;
+    const size_t wsb = cs_clip_workspace_bytes(h, B, T);
+    char* ws = (char*)malloc(wsb);
+    std::vector<int64_t> ids((size_t)B * T, 7);
+    std::vector<char> out((size_t)B * T * c.hidden_size * 2);
+    EXPECT(cs_clip_encode(h, ids.data(), B, T, out.data(), ws, wsb, nullptr) == CS_E_STATE);        // not finalized
+    EXPECT(cs_clip_set_weight(nullptr, "x", nullptr, nullptr, 0) == CS_E_ARG);
+    load_all_weights(cs_clip_num_weights(h), [&](int i, int64_t* sh, int* nd) { return cs_clip_weight_name(h, i, sh, nd); },
+                     [&](const char* n, const float* d, const int64_t* sh, int nd) { return cs_clip_set_weight(h, n, d, sh, nd); }, [&] { return cs_clip_finalize(h); });
+    EXPECT(wsb > 0 && cs_clip_workspace_bytes(h, B, T) == wsb && cs_clip_flops(h, B, T) > 0);
+    EXPECT(cs_clip_encode(h, ids.data(), B, T, out.data(), ws, wsb, nullptr) == CS_OK);
+    EXPECT(cs_clip_encode(h, ids.data(), B, T, out.data(), ws, wsb - 1, nullptr) != CS_OK);
+    EXPECT(cs_clip_encode(h, ids.data(), B, T + 1, out.data(), ws, wsb, nullptr) == CS_E_SHAPE);   // past max_position_embeddings
+    EXPECT(cs_clip_encode(h, nullptr, B, T, out.data(), ws, wsb, nullptr) != CS_OK);
+    EXPECT(cs_clip_encode(h, ids.data(), 0, T, out.data(), ws, wsb, nullptr) == CS_OK);             // empty batch: no-op
+    free(ws);
+    cs_clip_destroy(h);
+    cs_clip_destroy(nullptr);
+}
+
+static void vit_part() {
+    const CsVitConfig c = vit_config();
+    CsVit* h = nullptr;
+    CsVitConfig bad = c; bad.crop_size = 30;
+    EXPECT(cs_vit_create(&bad, &h) != CS_OK && cs_vit_create(nullptr, &h) != CS_OK);
+    EXPECT(cs_vit_create(&c, &h) == CS_OK);
+    if (!h) return;
+    const int B = 2, NP = 4, Kpad = cs_vit_patch_cols(h);
+    EXPECT(Kpad == 640 && cs_vit_num_tokens(h) == NP + 1);
+    const size_t wsb = cs_vit_workspace_bytes(h, B);
+    char* ws = (char*)malloc(wsb);
+    std::vector<char> patches((size_t)B * NP * Kpad * 2);
+    std::vector<float> cls((size_t)B * c.hidden_size), reward(B);
+    EXPECT(cs_vit_forward(h, patches.data(), B, cls.data(), ws, wsb, nullptr) == CS_E_STATE);       // not finalized
+    EXPECT(cs_vit_set_weight(nullptr, "x", nullptr, nullptr, 0) == CS_E_ARG);
+    load_all_weights(cs_vit_num_weights(h), [&](int i, int64_t* sh, int* nd) { return cs_vit_weight_name(h, i, sh, nd); },
+                     [&](const char* n, const float* d, const int64_t* sh, int nd) { return cs_vit_set_weight(h, n, d, sh, nd); }, [&] { return cs_vit_finalize(h); });
+    EXPECT(wsb > 0 && cs_vit_workspace_bytes(h, B) == wsb && cs_vit_flops(h, B) > 0);
+    {   // the front end on an image that is resized and cropped, its workspace exactly what the library asked for
+        const int H = 40, W = 56;
+        const size_t pwb = cs_vit_preprocess_workspace_bytes(h, B, H, W);
+        char* pws = (char*)malloc(pwb);
+        std::vector<float> img((size_t)B * 3 * H * W, 0.5f);
+        std::vector<unsigned char> crop((size_t)B * 3 * c.crop_size * c.crop_size);
+        EXPECT(pwb > 0 && cs_vit_preprocess(h, img.data(), CS_F32, B, H, W, patches.data(), crop.data(), pws, pwb, nullptr) == CS_OK);
+        EXPECT(cs_vit_preprocess(h, img.data(), CS_F32, B, 14, 14 * 3, patches.data(), nullptr, pws, pwb, nullptr) == CS_OK);      // a second size: a second table
+        EXPECT(cs_vit_preprocess(h, img.data(), CS_F32, B, H, W, patches.data(), nullptr, pws, 16, nullptr) != CS_OK);
+        free(pws);
+    }
+    EXPECT(cs_vit_forward(h, patches.data(), B, cls.data(), ws, wsb, nullptr) == CS_OK);
+    EXPECT(cs_vit_forward(h, patches.data(), B, cls.data(), ws, wsb - 1, nullptr) != CS_OK);
+    EXPECT(cs_vit_forward(h, nullptr, B, cls.data(), ws, wsb, nullptr) != CS_OK);
+    EXPECT(cs_vit_forward(h, patches.data(), 0, cls.data(), ws, wsb, nullptr) == CS_OK);            // empty batch: no-op
+    EXPECT(cs_cosine_reward(cls.data(), cls.data(), B, c.hidden_size, 0, reward.data(), nullptr) == CS_OK);
+    free(ws);
+    cs_vit_destroy(h);
+    cs_vit_destroy(nullptr);
+}
+
+// every weight but the last one set: finalize refuses with CS_E_STATE and names the tensor; what was staged is released by destroy (leak checking)
+template <typename NameAt, typename Set, typename Finalize>
+static void finalize_with_one_missing(int n, NameAt name_at, Set set, Finalize finalize) {
+    int64_t shape[4]; int nd = 0;
+    for (int i = 0; i + 1 < n; ++i) {
+        const char* name = name_at(i, shape, &nd);
+        size_t cnt = 1; for (int k = 0; k < nd; ++k) cnt *= (size_t)shape[k];
+        EXPECT(set(name, cnt, shape, nd) == CS_OK);
+    }
+    const std::string last = name_at(n - 1, shape, &nd);
+    EXPECT(finalize() == CS_E_STATE && std::string(cs_last_error()) == "missing weight '" + last + "'");
+}
+
+static void missing_weight_part() {
+    std::vector<float> buf;
+    std::vector<unsigned short> buf16;
+    {
+        const CsUNetConfig c = unet_config(); CsUNet* h = nullptr;
+        EXPECT(cs_unet_create(&c, &h) == CS_OK);
+        finalize_with_one_missing(cs_unet_num_weights(h), [&](int i, int64_t* sh, int* nd) { return cs_unet_weight_name(h, i, sh, nd); },
+                                  [&](const char* n, size_t cnt, const int64_t* sh, int nd) { buf.assign(cnt, 0.01f); return cs_unet_set_weight(h, n, buf.data(), sh, nd); },
+                                  [&] { return cs_unet_finalize(h); });
+        cs_unet_destroy(h);
+    }
+    {
+        const CsVaeConfig c = vae_config(); CsVae* h = nullptr;
+        EXPECT(cs_vae_create(&c, &h) == CS_OK);
+        finalize_with_one_missing(cs_vae_num_weights(h), [&](int i, int64_t* sh, int* nd) { return cs_vae_weight_name(h, i, sh, nd); },
+                                  [&](const char* n, size_t cnt, const int64_t* sh, int nd) { buf.assign(cnt, 0.01f); return cs_vae_set_weight(h, n, buf.data(), sh, nd); },
+                                  [&] { return cs_vae_finalize(h); });
+        cs_vae_destroy(h);
+    }
+    {
+        const CsClipConfig c = clip_config(); CsClip* h = nullptr;
+        EXPECT(cs_clip_create(&c, &h) == CS_OK);
+        finalize_with_one_missing(cs_clip_num_weights(h), [&](int i, int64_t* sh, int* nd) { return cs_clip_weight_name(h, i, sh, nd); },
+                                  [&](const char* n, size_t cnt, const int64_t* sh, int nd) { buf.assign(cnt, 0.01f); return cs_clip_set_weight(h, n, buf.data(), sh, nd); },
+                                  [&] { return cs_clip_finalize(h); });
+        cs_clip_destroy(h);
+    }
+    {
+        const CsVitConfig c = vit_config(); CsVit* h = nullptr;
+        EXPECT(cs_vit_create(&c, &h) == CS_OK);
+        finalize_with_one_missing(cs_vit_num_weights(h), [&](int i, int64_t* sh, int* nd) { return cs_vit_weight_name(h, i, sh, nd); },
+                                  [&](const char* n, size_t cnt, const int64_t* sh, int nd) { buf.assign(cnt, 0.01f); return cs_vit_set_weight(h, n, buf.data(), sh, nd); },
+                                  [&] { return cs_vit_finalize(h); });
+        cs_vit_destroy(h);
+    }
+    {
+        const CsFluxConfig c = flux_config(); CsFlux* h = nullptr;
+        EXPECT(cs_flux_create(&c, &h) == CS_OK);
+        finalize_with_one_missing(cs_flux_num_weights(h), [&](int i, int64_t* sh, int* nd) { return cs_flux_weight_name(h, i, sh, nd); },
+                                  [&](const char* n, size_t cnt, const int64_t* sh, int nd) { buf16.assign(cnt, 0x3c00); return cs_flux_set_weight(h, n, buf16.data(), 0, sh, nd); },
+                                  [&] { return cs_flux_finalize(h); });
+        cs_flux_destroy(h);
+    }
+}
+
 int main() {
     EXPECT(cs_abi_version() == 2);
     EXPECT(cs_set_tuning("conv_lw", 5) != CS_OK && cs_set_tuning("no_such_knob", 1) != CS_OK && cs_set_tuning("attn_qt40", 3) != CS_OK);
@@ -248,6 +426,9 @@ int main() {
     unet_part();
     vae_part();
     flux_part();
+    clip_part();
+    vit_part();
+    missing_weight_part();
     if (g_fail) { fprintf(stderr, "%d expectation(s) failed\n", g_fail); return 1; }
     printf("sanitize harness: ok\n");
     return 0;

@@ -1,6 +1,6 @@
 // Host-only stand-ins for the sanitizer harness (tests/sanitize/harness.cpp; TEST INFRASTRUCTURE, never linked into libconsolver_hip.so).
 //
-// The executors (unet.cpp / vae.cpp / flux.cpp / clip.cpp / ops_api.cpp / api.cpp) are host code: weight repacking, a first-fit arena over the caller's
+// The executors (unet.cpp / vae.cpp / flux.cpp / clip.cpp / vit.cpp / ops_api.cpp / api.cpp, with weights.h / encoder.h) are host code: weight repacking, a first-fit arena over the caller's
 // workspace, the dry-run workspace sizing and the launch sequence.  They are compiled here with -fsanitize=address,undefined -fno-gpu-sanitize (hipcc --cuda-host-only) and
 // linked against THIS file instead of the HIP kernels and the HIP runtime:
 //   * "device" memory is host malloc, so AddressSanitizer sees every buffer the executors carve out of the workspace;
@@ -101,8 +101,27 @@ int launch_pixel_linear_nchw(const f16* x, const f16*, const f16*, f16* out, int
 int launch_pixel_affine_nchw(const f16* x, int Cin, const f16*, const f16*, int Cout, f16* out, int B, int HW, float, float, hipStream_t) { rd(x, (size_t)B * Cin * HW * 2); wr(out, (size_t)B * Cout * HW * 2); return CS_OK; }
 int launch_latent_to_nhwc64(const f16* x, const f16*, const f16*, f16* out, int B, int C, int HW, float, float, hipStream_t) { rd(x, (size_t)B * C * HW * 2); wr(out, (size_t)B * HW * 64 * 2); return CS_OK; }
 int launch_row_softmax(f16* x, long rows, int cols, float, hipStream_t) { wr(x, (size_t)rows * cols * 2); return CS_OK; }
-int launch_embed_tokens(const int64_t* ids, const f16*, const f16*, f16* out, long rows, int, int C, int, hipStream_t) { rd(ids, rows * 8); wr(out, (size_t)rows * C * 2); return CS_OK; }
+int launch_embed_tokens(const int64_t* ids, const f16* tok, const f16* pos, f16* out, long rows, int L, int C, int vocab, hipStream_t) { rd(ids, rows * 8); rd(tok, (size_t)vocab * C * 2); rd(pos, (size_t)L * C * 2); wr(out, (size_t)rows * C * 2); return CS_OK; }
 int launch_quick_gelu(f16* x, long n, hipStream_t) { wr(x, (size_t)n * 2); return CS_OK; }
+int launch_gelu_erf(f16* x, long n, hipStream_t) { wr(x, (size_t)n * 2); return CS_OK; }
+// ---- vit_ops.hip
+int launch_vit_front_end(const void* images, int dtype, int B, int H, int W, const VitResizePlan& pl, const float* mean, const float* stdv, double, int P, int G, int Kpad,
+                         unsigned char* tmp, f16* patches, unsigned char* crop, hipStream_t) {
+    const size_t C = (size_t)P * G;                     // the crop's edge: one table row per output column / row
+    rd(images, (size_t)B * 3 * H * W * esz(dtype)); rd(mean, 3 * 4); rd(stdv, 3 * 4);
+    rd(pl.h_lo, C * 4); rd(pl.h_cnt, C * 4); rd(pl.h_kk, C * pl.h_ksize * 4); rd(pl.v_lo, C * 4); rd(pl.v_cnt, C * 4); rd(pl.v_kk, C * pl.v_ksize * 4);
+    wr(tmp, (size_t)B * 3 * pl.nrows * C); wr(patches, (size_t)B * G * G * Kpad * 2); wr(crop, (size_t)B * 3 * C * C);
+    return CS_OK;
+}
+int launch_vit_tokens(const f16* pe, const f16* cls, const f16* pos, f16* x, int B, int NP, int D, hipStream_t) {
+    rd(pe, (size_t)B * NP * D * 2); rd(cls, (size_t)D * 2); rd(pos, (size_t)(NP + 1) * D * 2); wr(x, (size_t)B * (NP + 1) * D * 2); return CS_OK;
+}
+int launch_vit_cls_layer_norm(const f16* x, long sample_stride, const f16* g, const f16* b, float, int B, int D, float* out, hipStream_t) {
+    rd(x, ((size_t)(B - 1) * sample_stride + D) * 2); rd(g, (size_t)D * 2); rd(b, (size_t)D * 2); wr(out, (size_t)B * D * 4); return CS_OK;
+}
+int launch_cosine_reward(const float* pred, const float* target, long target_stride, int B, int D, float* out, hipStream_t) {
+    rd(pred, (size_t)B * D * 4); rd(target, ((size_t)(B - 1) * target_stride + D) * 4); wr(out, (size_t)B * 4); return CS_OK;
+}
 int launch_gemm2(const Gemm2Args& a, hipStream_t) {
     rd(a.a, 2); rd(a.w, (size_t)((a.N + 255) / 256 * 256) * a.K * 2); wr(a.out, 2);
     if (!a.c_seg_rows) wr(a.out, (((size_t)a.M - 1 + a.c_row_off) * a.ldc + a.c_col_off + a.N) * 2);

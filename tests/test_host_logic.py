@@ -317,3 +317,38 @@ def test_weight_manifests_match_published_counts_and_committed_key_lists(name):
             assert k in names, k
         assert dict(m)["down_blocks.0.attentions.0.transformer_blocks.0.attn2.to_k.weight"] == (320, 768)
         assert dict(m)["up_blocks.0.resnets.0.conv1.weight"] == (1280, 2560, 3, 3)
+
+
+def _handle_classes():
+    from consolver_amd.unet import HipUNet2DConditionModel
+    from consolver_amd.vae import HipAutoencoderKL
+    from consolver_amd.text_encoder import HipCLIPTextModel
+    from consolver_amd.reward_model import HipDinov2Model
+    from consolver_amd.flux import HipFluxTransformer2DModel
+    return {"unet": (HipUNet2DConditionModel, dict(layers_per_block=1, sample_size=16)),
+            "vae": (HipAutoencoderKL, dict(layers_per_block=1, sample_size=16)),
+            "clip": (HipCLIPTextModel, dict(num_hidden_layers=1, vocab_size=500)),
+            "vit": (HipDinov2Model, dict(hidden_size=128, num_hidden_layers=1, num_attention_heads=2)),
+            "flux": (HipFluxTransformer2DModel, dict(num_layers=1, num_single_layers=1, num_heads=2, joint_attention_dim=256, pooled_projection_dim=64))}
+
+
+@pytest.mark.parametrize("name", ["unet", "vae", "clip", "vit", "flux"])
+def test_load_state_dict_rejects_missing_and_misshapen_tensors(name):
+    """the loader the five model classes share (_lib.manifest / load_float_weights; FLUX: its device-side path behind the same manifest): a state dict that lacks
+    a tensor raises KeyError, one with a tensor of the wrong shape raises ValueError, both before cs_*_finalize -- so before anything touches a GPU (device="cpu")."""
+    _ensure_built()
+    ctor, cfg = _handle_classes()[name]
+    m = ctor(cfg, device="cpu")
+    man = m.manifest()
+    assert len(man) > 10 and man == _lib.manifest(name, m._h, cap=2 if name == "flux" else 4)
+    sd = {k: torch.zeros(s) for k, s in man}              # (zero pages: never touched past the tensors in front of the bad one)
+    victim, shape = man[2]
+    short = dict(sd)
+    del short[victim]
+    with pytest.raises(KeyError, match="missing 1 tensors"):
+        m.load_state_dict(short)
+    bad = dict(sd)
+    bad[victim] = torch.zeros((shape[0] + 1,) + tuple(shape[1:]))
+    with pytest.raises(ValueError, match="shape"):
+        m.load_state_dict(bad)
+    assert not m._finalized
