@@ -62,6 +62,13 @@ class CsVitConfig(C.Structure):
                 ("crop_size", C.c_int), ("image_mean", C.c_float * 3), ("image_std", C.c_float * 3), ("rescale_factor", C.c_double)]
 
 
+class CsClipVisionConfig(C.Structure):
+    _fields_ = [("hidden_size", C.c_int), ("intermediate_size", C.c_int), ("num_hidden_layers", C.c_int), ("num_attention_heads", C.c_int),
+                ("image_size", C.c_int), ("patch_size", C.c_int), ("projection_dim", C.c_int), ("layer_norm_eps", C.c_float),
+                ("resize_shortest_edge", C.c_int), ("crop_size", C.c_int), ("image_mean", C.c_float * 3), ("image_std", C.c_float * 3),
+                ("rescale_factor", C.c_double)]
+
+
 class CsGemm2Problem(C.Structure):
     _fields_ = [("x", C.c_void_p), ("M", C.c_int), ("K", C.c_int), ("w", C.c_void_p), ("bias", C.c_void_p), ("N", C.c_int),
                 ("res", C.c_void_p), ("gate", C.c_void_p), ("gate_stride", C.c_long), ("rows_per_sample", C.c_int), ("act", C.c_int),
@@ -122,6 +129,20 @@ SYMBOLS = {
                                     C.c_void_p]),
     "cs_vit_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "cs_cosine_reward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p]),
+    "cs_clipv_create": (C.c_int, [C.POINTER(CsClipVisionConfig), C.POINTER(C.c_void_p)]),
+    "cs_clipv_destroy": (None, [C.c_void_p]),
+    "cs_clipv_set_weight": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int]),
+    "cs_clipv_num_weights": (C.c_int, [C.c_void_p]),
+    "cs_clipv_weight_name": (C.c_char_p, [C.c_void_p, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int)]),
+    "cs_clipv_finalize": (C.c_int, [C.c_void_p]),
+    "cs_clipv_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int]),
+    "cs_clipv_flops": (C.c_double, [C.c_void_p, C.c_int]),
+    "cs_clipv_patch_cols": (C.c_int, [C.c_void_p]),
+    "cs_clipv_num_tokens": (C.c_int, [C.c_void_p]),
+    "cs_clipv_preprocess_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
+    "cs_clipv_preprocess": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                      C.c_void_p]),
+    "cs_clipv_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "cs_vae_create": (C.c_int, [C.POINTER(CsVaeConfig), C.POINTER(C.c_void_p)]),
     "cs_vae_destroy": (None, [C.c_void_p]),
     "cs_vae_set_weight": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int]),
@@ -240,6 +261,8 @@ SYMBOLS = {
     "cs_debug_trace_read": (C.c_int, [C.c_void_p, C.c_size_t]),
     "cs_debug_attn_trace_read": (C.c_int, [C.c_void_p, C.c_size_t]),
     "cs_op_layer_norm": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p]),
+    "cs_op_clipv_tokens_ln": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "cs_op_clipv_head": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
 }
 
 _lib = None

@@ -31,6 +31,7 @@ SOURCES = {
     "clip.cpp": [],
     "vit_ops.hip": [],
     "vit.cpp": [],
+    "clip_vision.cpp": [],
     "ppo.hip": [],
     "ops_api.cpp": [],
 }

@@ -280,3 +280,9 @@ int launch_gelu_erf(f16* x, long n, hipStream_t s);
 int launch_vit_cls_layer_norm(const f16* x, long sample_stride, const f16* g, const f16* b, float eps, int B, int D, float* out, hipStream_t s);
 // (cosine_similarity(normalize(pred), normalize(target)) + 1) * 50 -> out [B]; target rows target_stride floats apart (0 broadcasts one row)
 int launch_cosine_reward(const float* pred, const float* target, long target_stride, int B, int D, float* out, hipStream_t s);
+// ---- CLIP image reward (vit_ops.hip / clip_vision.cpp): the two ends of CLIPVisionModelWithProjection around the shared encoder loop ----------------
+// x[b][0] = cls + pos[0], x[b][1 + p] = pe[b * NP + p] + pos[1 + p], then LayerNorm over D (pre_layrnorm): the sum and the normalisation in fp32, one rounding.
+// D a multiple of 128 up to 2048
+int launch_clipv_tokens_ln(const f16* pe, const f16* cls, const f16* pos, const f16* g, const f16* b, float eps, f16* x, int B, int NP, int D, hipStream_t s);
+// out[b][p] = sum_d LayerNorm(first row of sample b)[d] * w[p][d]: post_layernorm + visual_projection (no bias) -> [B][P] fp32; rows sample_stride halfs apart
+int launch_clipv_head(const f16* x, long sample_stride, const f16* g, const f16* b, float eps, const f16* w, int B, int D, int P, float* out, hipStream_t s);

@@ -6,13 +6,10 @@
 // The encoder is encoder.h's layer loop (implicit-GEMM MFMA linears, flash attention at head dim 64 -- here unmasked, 257 tokens) with the LayerScale vectors folded
 // into the out-projection / fc2 weights and biases at pack time (fp32 product, one rounding to fp16); the front end and the tail are vit_ops.hip.
 #include "encoder.h"
+#include "image_front_end.h"
 #include "consolver_hip.h"
 
 #include <cmath>
-
-namespace {
-struct Plan { VitResizePlan dev; };
-}
 
 struct CsVit {
     CsVitConfig cfg;
@@ -20,12 +17,7 @@ struct CsVit {
     WeightStore<float> weights;                            // fp32 staging: the LayerScale product is formed in fp32 and rounded once at upload
     f16 *wpatch = nullptr, *bpatch = nullptr, *cls = nullptr, *pos = nullptr, *lnfg = nullptr, *lnfb = nullptr;
     std::vector<PreLnLayer> layers;
-    // resize tables per input (height, width), at most MAX_PLANS of them (a directory of many image sizes must not grow device memory without bound: when the
-    // cache is full it is emptied -- hipFree waits for the kernels that still read a table).  Like every handle here a CsVit serves one thread at a time, and the
-    // tables live on the device that is current when a size is first seen: callers run a handle on one device (the Python wrapper selects the tensor's).
-    static constexpr size_t MAX_PLANS = 16;
-    std::map<std::pair<int, int>, Plan> plans;
-    std::vector<void*> plan_allocs;
+    image_front_end::PlanCache plans;                      // resize tables per input (height, width), bounded (image_front_end.h)
 };
 
 namespace {
@@ -82,68 +74,6 @@ std::vector<float> interpolate_positions(const float* grid, int s, int g, int D)
     return out;
 }
 
-// one pass of PIL's ImagingResample (BICUBIC: Keys cubic a = -0.5, support 2 * max(scale, 1)) for output indices win0 .. win0 + win: taps normalised in double,
-// converted as int(+-0.5 + k 2^22)
-struct Taps { std::vector<int> lo, cnt, kk; int ksize; };
-double pil_cubic(double x) {
-    const double a = -0.5;
-    x = std::fabs(x);
-    if (x < 1.0) return ((a + 2.0) * x - (a + 3.0)) * x * x + 1;
-    if (x < 2.0) return (((x - 5) * x + 8) * x - 4) * a;
-    return 0.0;
-}
-Taps pil_taps(int in, int out, int win0, int win) {
-    Taps t;
-    const double scale = (double)in / out, fs = std::max(scale, 1.0), support = 2.0 * fs, ww = 1.0 / fs;
-    t.ksize = (int)std::ceil(support) * 2 + 1;
-    t.lo.resize(win); t.cnt.resize(win); t.kk.assign((size_t)win * t.ksize, 0);
-    std::vector<double> w(t.ksize);
-    for (int i = 0; i < win; ++i) {
-        const double center = (win0 + i + 0.5) * scale;
-        const int xmin = std::max((int)(center - support + 0.5), 0), n = std::min((int)(center + support + 0.5), in) - xmin;
-        double tot = 0;
-        for (int x = 0; x < n; ++x) { w[x] = pil_cubic((x + xmin - center + 0.5) * ww); tot += w[x]; }
-        for (int x = 0; x < n; ++x) {
-            const double k = tot != 0.0 ? w[x] / tot : w[x];
-            t.kk[(size_t)i * t.ksize + x] = k < 0 ? (int)(-0.5 + k * (1 << 22)) : (int)(0.5 + k * (1 << 22));
-        }
-        t.lo[i] = xmin; t.cnt[i] = n;
-    }
-    return t;
-}
-
-int get_plan(CsVit* c, int H, int W, const Plan** out) {
-    auto it = c->plans.find({H, W});
-    if (it != c->plans.end()) { *out = &it->second; return CS_OK; }
-    const int edge = c->cfg.resize_shortest_edge, C = c->cfg.crop_size;
-    if (H < 1 || W < 1) CS_FAIL(CS_E_SHAPE, "vit: bad image size %d x %d", H, W);
-    // the processor's output-size rule (default_to_square = False): the short side becomes `edge`, the long side int(edge * long / short)
-    const int shrt = std::min(H, W), lng = std::max(H, W), nl = (int)((double)((int64_t)edge * lng) / shrt);
-    const int nh = H <= W ? edge : nl, nw = H <= W ? nl : edge;
-    if (nh < C || nw < C) CS_FAIL(CS_E_UNSUPPORTED, "vit: resized image %d x %d is smaller than the %d crop (the processor would pad)", nh, nw, C);
-    const Taps th = pil_taps(W, nw, (nw - C) / 2, C), tv = pil_taps(H, nh, (nh - C) / 2, C);
-    Plan p{};
-    int row0 = H, row1 = 0, col0 = W, col1 = 0;
-    for (int i = 0; i < C; ++i) {
-        row0 = std::min(row0, tv.lo[i]); row1 = std::max(row1, tv.lo[i] + tv.cnt[i]);
-        col0 = std::min(col0, th.lo[i]); col1 = std::max(col1, th.lo[i] + th.cnt[i]);
-    }
-    std::vector<int> all;
-    auto put = [&](const std::vector<int>& v) { const size_t o = all.size(); all.insert(all.end(), v.begin(), v.end()); return o; };
-    const size_t o0 = put(th.lo), o1 = put(th.cnt), o2 = put(th.kk), o3 = put(tv.lo), o4 = put(tv.cnt), o5 = put(tv.kk);
-    if (c->plans.size() >= CsVit::MAX_PLANS) {
-        for (void* q : c->plan_allocs) CS_CHECK_HIP(hipFree(q));
-        c->plan_allocs.clear(); c->plans.clear();
-    }
-    int* d = nullptr;
-    CS_CHECK_HIP(hipMalloc((void**)&d, all.size() * sizeof(int)));
-    if (hipMemcpy(d, all.data(), all.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(d); CS_FAIL(CS_E_HIP, "vit: resize table upload failed"); }
-    c->plan_allocs.push_back(d);
-    p.dev = VitResizePlan{d + o0, d + o1, d + o2, th.ksize, d + o3, d + o4, d + o5, tv.ksize, row0, row1 - row0, col0, col1};
-    *out = &(c->plans[{H, W}] = p);
-    return CS_OK;
-}
-
 }  // namespace
 
 extern "C" {
@@ -169,7 +99,7 @@ int cs_vit_create(const CsVitConfig* cfg, CsVit** out) {
 void cs_vit_destroy(CsVit* c) {
     if (!c) return;
     c->weights.free_device();
-    for (void* p : c->plan_allocs) (void)hipFree(p);
+    c->plans.free_device();
     delete c;
 }
 
@@ -245,8 +175,8 @@ int cs_vit_preprocess(CsVit* c, const void* images, int dtype, int batch, int he
     if (batch < 0) CS_FAIL(CS_E_ARG, "negative size");
     if (batch == 0) return CS_OK;
     if (!images || !patches || !workspace) CS_FAIL(CS_E_ARG, "null pointer");
-    const Plan* pl = nullptr;
-    const int rc = get_plan(c, height, width, &pl);
+    const image_front_end::Plan* pl = nullptr;
+    const int rc = c->plans.get_plan("vit", c->cfg.resize_shortest_edge, c->cfg.crop_size, height, width, &pl);
     if (rc != CS_OK) return rc;
     if (workspace_bytes < (size_t)batch * 3 * pl->dev.nrows * c->cfg.crop_size) CS_FAIL(CS_E_ARG, "vit: preprocess workspace too small");
     return launch_vit_front_end(images, dtype, batch, height, width, pl->dev, c->cfg.image_mean, c->cfg.image_std, c->cfg.rescale_factor,

@@ -1,9 +1,12 @@
-// Kernels of the DINOv2 image-similarity reward (vit.cpp; edit_ppo/reward_model.py:217-257) that are not GEMM / attention / LayerNorm:
+// Kernels of the DINOv2 and CLIP image-similarity rewards (vit.cpp, clip_vision.cpp; edit_ppo/reward_model.py:217-257, 512-552) that are not GEMM / attention /
+// LayerNorm:
 //
 //   * the image front end: ToPILImage's quantisation, PIL's two-pass fixed-point bicubic resize restricted to the center-crop window, the processor's
 //     rescale + normalise, written straight as the patch-embedding GEMM's A operand [B * tokens][K padded to 64];
 //   * token assembly (CLS row + position table), exact (erf) GELU, the final LayerNorm on the CLS rows only, and the reward tail
-//     F.normalize -> F.cosine_similarity -> (cos + 1) * 50.
+//     F.normalize -> F.cosine_similarity -> (cos + 1) * 50;
+//   * CLIP's two ends: token assembly fused with pre_layrnorm (one wave per token row, the sum and the normalisation in fp32 registers, one rounding), and
+//     post_layernorm of the CLS row + the bias-free visual_projection (one workgroup per image, the normalised row in LDS, one wave per output column).
 //
 // Everything here is bandwidth- or latency-trivial next to the encoder's GEMMs (one image = 46 GFLOP): plain one-thread-per-output kernels, integer
 // arithmetic identical to PIL's (22 fractional bits, accumulator seeded with 2^21, arithmetic shift, clip to 8 bits), so the uint8 crop is bit-exact.
@@ -135,6 +138,89 @@ __global__ __launch_bounds__(64) void cosine_reward_kernel(const float* __restri
     if (lane == 0) out[b] = (dot / (fmaxf(sqrtf(ma), 1e-8f) * fmaxf(sqrtf(mt), 1e-8f)) + 1.0f) * 50.0f;
 }
 
+// CLIP vision embeddings + pre_layrnorm: row (b, t) = (t == 0 ? cls : pe[b * NP + t - 1]) + pos[t], then LayerNorm over D -- one wave per row, the row in fp32
+// registers from the 16-byte loads to the one fp16 store (lane l holds the 8-channel chunks l, l + 64, ...: NCH of them, D <= 512 NCH).  Mean first, then the
+// variance of the centred values.
+template <int NCH>
+__global__ __launch_bounds__(256) void clipv_tokens_ln_kernel(const f16* __restrict__ pe, const f16* __restrict__ cls, const f16* __restrict__ pos,
+                                                              const f16* __restrict__ g, const f16* __restrict__ be, float eps, f16* __restrict__ x,
+                                                              long rows, int NP, int D) {
+    const int lane = threadIdx.x & 63;
+    const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;                                  // (whole waves leave: no barrier below)
+    const int t = (int)(row % (NP + 1));
+    const long b = row / (NP + 1);
+    const f16* src = t == 0 ? cls : pe + (b * NP + t - 1) * D;
+    const f16* prow = pos + (long)t * D;
+    float v[NCH][8];
+    float s = 0.f;
+#pragma unroll
+    for (int j = 0; j < NCH; ++j) {
+        const int d = (j * 64 + lane) * 8;
+        if (d < D) {
+            const f16x8 a = *reinterpret_cast<const f16x8*>(src + d), q = *reinterpret_cast<const f16x8*>(prow + d);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) { v[j][e] = (float)a[e] + (float)q[e]; s += v[j][e]; }
+        } else {
+#pragma unroll
+            for (int e = 0; e < 8; ++e) v[j][e] = 0.f;
+        }
+    }
+    const float mean = wave_sum(s) / (float)D;
+    float q2 = 0.f;
+#pragma unroll
+    for (int j = 0; j < NCH; ++j) {
+        if ((j * 64 + lane) * 8 < D) {
+#pragma unroll
+            for (int e = 0; e < 8; ++e) { v[j][e] -= mean; q2 += v[j][e] * v[j][e]; }
+        }
+    }
+    const float rstd = 1.0f / sqrtf(wave_sum(q2) / (float)D + eps);
+#pragma unroll
+    for (int j = 0; j < NCH; ++j) {
+        const int d = (j * 64 + lane) * 8;
+        if (d < D) {
+            const f16x8 gg = *reinterpret_cast<const f16x8*>(g + d), bb = *reinterpret_cast<const f16x8*>(be + d);
+            f16x8 o;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) o[e] = (f16)(v[j][e] * rstd * (float)gg[e] + (float)bb[e]);
+            *reinterpret_cast<f16x8*>(x + row * D + d) = o;
+        }
+    }
+}
+
+// CLIP vision head: out[b][p] = sum_d LayerNorm(x[b * sample_stride + d])[d] * w[p][d]   (post_layernorm of the CLS row, visual_projection without bias).
+// One workgroup of 8 waves per image: every wave takes the row's statistics itself (2 KB, no cross-wave reduction), the workgroup writes the normalised
+// row to LDS in fp32, then wave w forms the columns w, w + 8, ... as lane-strided dot products with 16-byte weight loads and fp32 accumulation.
+constexpr int HEAD_WAVES = 8;
+__global__ __launch_bounds__(HEAD_WAVES * 64) void clipv_head_kernel(const f16* __restrict__ x, long sample_stride, const f16* __restrict__ g,
+                                                                     const f16* __restrict__ be, float eps, const f16* __restrict__ w, int D, int P,
+                                                                     float* __restrict__ out) {
+    extern __shared__ __attribute__((aligned(16))) float clipv_head_row[];               // [D]
+    const int b = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const f16* row = x + (long)b * sample_stride;
+    float s = 0.f;
+    for (int d = lane; d < D; d += 64) s += (float)row[d];
+    const float mean = wave_sum(s) / (float)D;
+    float q = 0.f;
+    for (int d = lane; d < D; d += 64) { const float c = (float)row[d] - mean; q += c * c; }
+    const float rstd = 1.0f / sqrtf(wave_sum(q) / (float)D + eps);
+    for (int d = threadIdx.x; d < D; d += HEAD_WAVES * 64) clipv_head_row[d] = ((float)row[d] - mean) * rstd * (float)g[d] + (float)be[d];
+    __syncthreads();
+    for (int p = wave; p < P; p += HEAD_WAVES) {
+        const f16* wr = w + (long)p * D;
+        float acc = 0.f;
+        for (int d = lane * 8; d < D; d += 512) {
+            const f16x8 ww = *reinterpret_cast<const f16x8*>(wr + d);
+            const f32x4 n0 = *reinterpret_cast<const f32x4*>(clipv_head_row + d), n1 = *reinterpret_cast<const f32x4*>(clipv_head_row + d + 4);
+            acc += n0[0] * (float)ww[0] + n0[1] * (float)ww[1] + n0[2] * (float)ww[2] + n0[3] * (float)ww[3]
+                 + n1[0] * (float)ww[4] + n1[1] * (float)ww[5] + n1[2] * (float)ww[6] + n1[3] * (float)ww[7];
+        }
+        acc = wave_sum(acc);
+        if (lane == 0) out[(long)b * P + p] = acc;
+    }
+}
+
 inline unsigned blocks_for(long n) { return (unsigned)((n + 255) / 256); }
 
 }  // namespace
@@ -180,6 +266,32 @@ int launch_vit_cls_layer_norm(const f16* x, long sample_stride, const f16* g, co
     if (!x || !g || !b || !out) CS_FAIL(CS_E_ARG, "vit cls layer norm: null pointer");
     if (B <= 0) return B < 0 ? CS_E_SHAPE : CS_OK;
     hipLaunchKernelGGL(vit_cls_layer_norm_kernel, dim3(B), dim3(64), 0, s, x, sample_stride, g, b, eps, D, out);
+    CS_CHECK_LAUNCH();
+    return CS_OK;
+}
+
+int launch_clipv_tokens_ln(const f16* pe, const f16* cls, const f16* pos, const f16* g, const f16* b, float eps, f16* x, int B, int NP, int D, hipStream_t s) {
+    if (!pe || !cls || !pos || !g || !b || !x) CS_FAIL(CS_E_ARG, "clip vision tokens: null pointer");
+    if (D < 128 || D % 128 || D > 2048 || NP < 1) CS_FAIL(CS_E_SHAPE, "clip vision tokens: D = %d must be a multiple of 128 up to 2048", D);
+    if (B <= 0) return B < 0 ? CS_E_SHAPE : CS_OK;
+    const long rows = (long)B * (NP + 1);
+    if ((rows + 3) / 4 > 0x7fffffffL) CS_FAIL(CS_E_SHAPE, "clip vision tokens: batch too large");
+    const dim3 grid((unsigned)((rows + 3) / 4)), block(256);
+    switch ((D + 511) / 512) {
+        case 1: hipLaunchKernelGGL(clipv_tokens_ln_kernel<1>, grid, block, 0, s, pe, cls, pos, g, b, eps, x, rows, NP, D); break;
+        case 2: hipLaunchKernelGGL(clipv_tokens_ln_kernel<2>, grid, block, 0, s, pe, cls, pos, g, b, eps, x, rows, NP, D); break;
+        case 3: hipLaunchKernelGGL(clipv_tokens_ln_kernel<3>, grid, block, 0, s, pe, cls, pos, g, b, eps, x, rows, NP, D); break;
+        default: hipLaunchKernelGGL(clipv_tokens_ln_kernel<4>, grid, block, 0, s, pe, cls, pos, g, b, eps, x, rows, NP, D); break;
+    }
+    CS_CHECK_LAUNCH();
+    return CS_OK;
+}
+
+int launch_clipv_head(const f16* x, long sample_stride, const f16* g, const f16* b, float eps, const f16* w, int B, int D, int P, float* out, hipStream_t s) {
+    if (!x || !g || !b || !w || !out) CS_FAIL(CS_E_ARG, "clip vision head: null pointer");
+    if (D < 8 || D % 8 || D > 8192 || P < 1 || sample_stride < D) CS_FAIL(CS_E_SHAPE, "clip vision head: D = %d must be a multiple of 8 up to 8192, P = %d positive", D, P);
+    if (B <= 0) return B < 0 ? CS_E_SHAPE : CS_OK;
+    hipLaunchKernelGGL(clipv_head_kernel, dim3(B), dim3(HEAD_WAVES * 64), (size_t)D * sizeof(float), s, x, sample_stride, g, b, eps, w, D, P, out);
     CS_CHECK_LAUNCH();
     return CS_OK;
 }

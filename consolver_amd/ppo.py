@@ -4,14 +4,15 @@ Mirror of the body of the training loop in train_ppo.py:352-427 up to (not inclu
 step, with the reference's names:
 
 * ``calculate_reward(reward_type, reward_model, reward_model_processor, model_pred, target, device)``
-  (edit_ppo/reward_model.py:138-161): ``"image_psnr"`` (:484-509, arithmetic only) and ``"dino"`` (:217-257, the DINOv2
-  image-similarity reward the reference's run scripts train with; consolver_amd/reward_model.py).  The other backbone
-  rewards (depth / inception / clip / ...) are third-party networks that are not implemented; they raise.
+  (edit_ppo/reward_model.py:138-161): ``"image_psnr"`` (:484-509, arithmetic only), ``"dino"`` (:217-257, the DINOv2
+  image-similarity reward the reference's run scripts train with) and ``"clip"`` (:512-552, CLIP ViT-L/14 image features;
+  both in consolver_amd/reward_model.py).  The other backbone rewards (depth / inception / segmentation / ...) are
+  third-party networks that are not implemented; they raise.
 * ``compute_advantages`` = train_ppo.py:376-390, ``ppo_loss`` = :408-421 (value), ``PolicyTrainer`` = the
   optimisation step :404-437 (gradients, clip_grad_norm_, AdamW) and the checkpoint format.
 * ``collect_rollout`` = :352-403 for one batch of teacher pairs.
 
-Everything runs in the HIP library (cs_image_psnr / cs_vit_* / cs_ppo_advantages / cs_ppo_loss); there is no
+Everything runs in the HIP library (cs_image_psnr / cs_vit_* / cs_clipv_* / cs_ppo_advantages / cs_ppo_loss); there is no
 CPU fallback.
 """
 import ctypes as C
@@ -59,14 +60,17 @@ def depth_psnr_tail(pred_depth, target_depth):
 
 
 def calculate_reward(reward_type, reward_model, reward_model_processor, model_pred, target, device=None):
-    """edit_ppo/reward_model.py:138-161.  decode_latents already maps to [0, 1], so the clamp at :141-142 is a no-op here (the "dino"
+    """edit_ppo/reward_model.py:138-161.  decode_latents already maps to [0, 1], so the clamp at :141-142 is a no-op here (the "dino" / "clip"
     front end clamps to [0, 1] unconditionally)."""
     if reward_type == "image_psnr":
         return calculate_image_psnr_reward(reward_model_processor, model_pred, target, device)
     if reward_type == "dino":
         from .reward_model import calculate_dino_reward
         return calculate_dino_reward(reward_model, reward_model_processor, model_pred, target, device)
-    if reward_type in ("depth", "inception", "segmentation", "clip", "llava", "qwen_vl"):
+    if reward_type == "clip":
+        from .reward_model import calculate_clip_reward
+        return calculate_clip_reward(reward_model, reward_model_processor, model_pred, target, device)
+    if reward_type in ("depth", "inception", "segmentation", "llava", "qwen_vl"):
         raise NotImplementedError(f"reward_type '{reward_type}' needs a third-party backbone network (out of scope, SURVEY 8 a21)")
     raise ValueError(f"Unknown reward_type: {reward_type}")
 
@@ -102,7 +106,7 @@ def collect_rollout(text_encoder, noise_scheduler, unet, vae, noise, text, token
     records flattened to [B (n-1), ...].  Returns a dict(conds, actions, probs, masks, advantages, rewards, model_pred).
     ``identical_inputs=True``: the B rows are copies of one (prompt, noise, teacher latent) sample (``repeat_random_sample``):
     the rollout shares the denoiser calls whose inputs cannot differ yet, and the teacher image is decoded once (and, for the "dino"
-    reward, encoded once)."""
+    and "clip" rewards, encoded once)."""
     n = num_inference_steps
     model_pred, conds, probs, actions, masks, _ = denoise_diffusion(
         text_encoder, noise_scheduler, unet, noise, text, tokenizer, cfg=float(cfg), num_inference_steps=n,
@@ -110,7 +114,7 @@ def collect_rollout(text_encoder, noise_scheduler, unet, vae, noise, text, token
     model_pred_decoded = decode_latents(vae, model_pred, batch_size=decode_batch_size)
     if identical_inputs and target_latents.shape[0] > 1:
         target_decoded = decode_latents(vae, target_latents[:1], batch_size=1)
-        if reward_type != "dino":               # calculate_dino_reward takes one shared target as [1,3,H,W]
+        if reward_type not in ("dino", "clip"):               # calculate_dino_reward / calculate_clip_reward take one shared target as [1,3,H,W]
             target_decoded = target_decoded.expand(target_latents.shape[0], -1, -1, -1).contiguous()
     else:
         target_decoded = decode_latents(vae, target_latents, batch_size=decode_batch_size)

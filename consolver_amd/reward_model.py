@@ -1,4 +1,4 @@
-"""DINOv2 image-similarity reward on the HIP library (``--reward_type="dino"``, edit_ppo/run_ppo.sh:30).
+"""DINOv2 and CLIP image-similarity rewards on the HIP library (``--reward_type="dino"``, edit_ppo/run_ppo.sh:30; ``"clip"``, compute_reward.sh:5).
 
 Mirror of edit_ppo/reward_model.py by name:
 
@@ -12,6 +12,12 @@ bicubic resize to shortest edge 256, center crop 224, rescale, normalise -- runs
 image; the encoder runs in fp16 with fp32 accumulation (cs_vit_forward) and returns the CLS features in fp32; the tail (normalize, cosine, (cos + 1) * 50)
 is one kernel.  Inputs are clamped to [0, 1] unconditionally (the reference clamps when ``min < 0``; ``decode_latents`` never leaves [0, 1]).
 There is no CPU fallback; the fp32 restatement lives in tests/vit_oracle.py.
+
+``clip`` has the same shape (:128-134, :512-552): ``load_reward_model("clip")`` -> a ``HipCLIPVisionModel`` of the ``openai/clip-vit-large-patch14`` vision
+tower + ``visual_projection`` and a ``ClipImageProcessor``; ``calculate_clip_reward`` runs the same front end with CLIP's constants (shortest edge 224), the
+tower (cs_clipv_forward: embeddings + pre_layrnorm in one kernel, the shared pre-LN layer loop with quick-GELU, post_layernorm + projection in one kernel)
+and the same tail on ``image_embeds``.  Weights load under their ``transformers.CLIPModel`` names (a full CLIPModel state dict or a
+CLIPVisionModelWithProjection one).  The fp32 restatement lives in tests/clip_vision_oracle.py.
 """
 import ctypes as C
 
@@ -21,6 +27,8 @@ from . import _lib as L
 
 DINOV2_BASE_CONFIG = dict(hidden_size=768, num_hidden_layers=12, num_attention_heads=12, mlp_ratio=4, image_size=518, patch_size=14,
                           layer_norm_eps=1e-6)
+CLIP_VIT_L14_CONFIG = dict(hidden_size=1024, intermediate_size=4096, num_hidden_layers=24, num_attention_heads=16, image_size=224, patch_size=14,
+                           projection_dim=768, layer_norm_eps=1e-5)
 _DT = {torch.float32: L.CS_F32, torch.float16: L.CS_F16}
 
 
@@ -48,31 +56,30 @@ class _VitOutput(tuple):
     pooler_output = property(lambda self: self[1])
 
 
-class HipDinov2Model:
+class _HipImageEncoder:
+    """What the two image-reward models share: a handle of the C ABI family ``cs_<_prefix>_*`` (create / weights / preprocess / forward), the front end,
+    and the chunked encoder call.  Subclasses create the handle from their config struct and name the width of the features (``_feature_dim``)."""
     is_consolver_hip = True
     dtype = torch.float16
-    max_batch = 64             # images per encoder call (bounds the workspace: 7.6 MB per image at the base size)
+    max_batch = 64             # images per encoder call (bounds the workspace)
+    _prefix = None
 
-    def __init__(self, config=None, device="cuda:0", processor=None):
-        cfg = dict(DINOV2_BASE_CONFIG)
-        cfg.update(config or {})
-        self.config = cfg
-        self.device = torch.device(device)
-        self.processor = processor or DinoImageProcessor()
-        edge, crop, rescale, mean, std = self.processor.constants()
-        c = L.CsVitConfig(cfg["hidden_size"], cfg["num_hidden_layers"], cfg["num_attention_heads"], cfg["mlp_ratio"], cfg["image_size"], cfg["patch_size"],
-                          cfg["layer_norm_eps"], edge, crop, (C.c_float * 3)(*mean), (C.c_float * 3)(*std), rescale)
-        h = C.c_void_p()
-        L.check(L.lib().cs_vit_create(C.byref(c), C.byref(h)))
+    def _init_handle(self, h, crop, patch):
         self._h = h
         self._ws = None
         self._pws = None
         self._finalized = False
-        self.crop, self.patch = crop, cfg["patch_size"]
-        self.patch_cols, self.num_tokens = int(L.lib().cs_vit_patch_cols(h)), int(L.lib().cs_vit_num_tokens(h))
+        self.crop, self.patch = crop, patch
+        self.patch_cols, self.num_tokens = int(self._fn("patch_cols")(h)), int(self._fn("num_tokens")(h))
+
+    def _fn(self, name):
+        return getattr(L.lib(), f"cs_{self._prefix}_{name}")
 
     def __del__(self):
-        L.destroy("vit", self)
+        try:
+            L.destroy(self._prefix, self)
+        except Exception:          # interpreter shutdown: the module's globals may be gone
+            pass
 
     # reference call sites: reward_model.eval(); reward_model.to(device)
     def eval(self):
@@ -84,19 +91,19 @@ class HipDinov2Model:
             if d.type == "cuda" and d.index is None:
                 d = torch.device("cuda", self.device.index if self.device.type == "cuda" else torch.cuda.current_device())
             if d != self.device:
-                raise RuntimeError(f"HipDinov2Model lives on {self.device} (its weights are packed there); cannot move it to {d}")
+                raise RuntimeError(f"{type(self).__name__} lives on {self.device} (its weights are packed there); cannot move it to {d}")
         return self
 
     def manifest(self):
-        return L.manifest("vit", self._h)
+        return L.manifest(self._prefix, self._h)
 
     def load_state_dict(self, sd, strict=True):
-        L.load_float_weights("vit", self._h, sd, self.device)
+        L.load_float_weights(self._prefix, self._h, sd, self.device)
         self._finalized = True
         return self
 
     def flops(self, batch):
-        return float(L.lib().cs_vit_flops(self._h, batch))
+        return float(self._fn("flops")(self._h, batch))
 
     # ---- front end ------------------------------------------------------------------------------------------------
     def preprocess(self, images, return_crop=False):
@@ -114,13 +121,12 @@ class HipDinov2Model:
         patches = torch.empty(B * g * g, self.patch_cols, dtype=torch.float16, device=images.device)
         crop = torch.empty(B, 3, self.crop, self.crop, dtype=torch.uint8, device=images.device) if return_crop else None
         if B:
-            lib = L.lib()
-            need = int(lib.cs_vit_preprocess_workspace_bytes(self._h, B, H, W))
+            need = int(self._fn("preprocess_workspace_bytes")(self._h, B, H, W))
             if self._pws is None or self._pws.numel() < need or self._pws.device != images.device:
                 self._pws = torch.empty(need, dtype=torch.uint8, device=images.device)
             with torch.cuda.device(images.device):          # the resize tables of a new image size are allocated on the current device
-                L.check(lib.cs_vit_preprocess(self._h, L.ptr(images), _DT[images.dtype], B, H, W, L.ptr(patches), L.ptr(crop), L.ptr(self._pws),
-                                              self._pws.numel(), L.stream_ptr(images.device)))
+                L.check(self._fn("preprocess")(self._h, L.ptr(images), _DT[images.dtype], B, H, W, L.ptr(patches), L.ptr(crop), L.ptr(self._pws),
+                                                self._pws.numel(), L.stream_ptr(images.device)))
         return (patches, crop) if return_crop else patches
 
     def patches_to_pixel_values(self, patches):
@@ -141,26 +147,44 @@ class HipDinov2Model:
 
     # ---- encoder --------------------------------------------------------------------------------------------------
     def encode_patches(self, patches):
-        """patch rows -> CLS features [B, hidden] fp32 (``last_hidden_state[:, 0]`` after the final LayerNorm)"""
+        """patch rows -> features [B, _feature_dim] fp32 (dino: ``last_hidden_state[:, 0]`` after the final LayerNorm; clip: ``image_embeds``)"""
         if not self._finalized:
             raise RuntimeError("weights not loaded")
         L.require_cuda(patches, "patches")
         g = self.crop // self.patch
         B = patches.shape[0] // (g * g)
-        out = torch.empty(B, self.config["hidden_size"], dtype=torch.float32, device=patches.device)
-        lib = L.lib()
+        out = torch.empty(B, self._feature_dim, dtype=torch.float32, device=patches.device)
         for s in range(0, B, self.max_batch):
             n = min(self.max_batch, B - s)
-            need = int(lib.cs_vit_workspace_bytes(self._h, n))
+            need = int(self._fn("workspace_bytes")(self._h, n))
             if self._ws is None or self._ws.numel() < need or self._ws.device != patches.device:
                 self._ws = torch.empty(need, dtype=torch.uint8, device=patches.device)
-            L.check(lib.cs_vit_forward(self._h, L.ptr(patches[s * g * g:]), n, L.ptr(out[s:]), L.ptr(self._ws), self._ws.numel(),
-                                       L.stream_ptr(patches.device)))
+            L.check(self._fn("forward")(self._h, L.ptr(patches[s * g * g:]), n, L.ptr(out[s:]), L.ptr(self._ws), self._ws.numel(),
+                                        L.stream_ptr(patches.device)))
         return out
 
     def image_features(self, images):
-        """[B,3,H,W] in [0,1] -> CLS features [B, hidden] fp32: the whole per-image path of calculate_dino_reward up to F.normalize"""
+        """[B,3,H,W] in [0,1] -> features [B, _feature_dim] fp32: the whole per-image path of the reward up to F.normalize"""
         return self.encode_patches(self.preprocess(images))
+
+
+class HipDinov2Model(_HipImageEncoder):
+    max_batch = 64             # 7.6 MB of workspace per image at the base size
+    _prefix = "vit"
+
+    def __init__(self, config=None, device="cuda:0", processor=None):
+        cfg = dict(DINOV2_BASE_CONFIG)
+        cfg.update(config or {})
+        self.config = cfg
+        self.device = torch.device(device)
+        self.processor = processor or DinoImageProcessor()
+        edge, crop, rescale, mean, std = self.processor.constants()
+        c = L.CsVitConfig(cfg["hidden_size"], cfg["num_hidden_layers"], cfg["num_attention_heads"], cfg["mlp_ratio"], cfg["image_size"], cfg["patch_size"],
+                          cfg["layer_norm_eps"], edge, crop, (C.c_float * 3)(*mean), (C.c_float * 3)(*std), rescale)
+        h = C.c_void_p()
+        L.check(L.lib().cs_vit_create(C.byref(c), C.byref(h)))
+        self._init_handle(h, crop, cfg["patch_size"])
+        self._feature_dim = cfg["hidden_size"]
 
     @torch.no_grad()
     def __call__(self, pixel_values=None, **_ignored):
@@ -172,19 +196,66 @@ class HipDinov2Model:
         return _VitOutput((cls.unsqueeze(1), cls))
 
 
+class ClipImageProcessor(DinoImageProcessor):
+    """The preprocessing constants of ``openai/clip-vit-large-patch14`` (its preprocessor_config.json): resize to shortest edge 224 with PIL BICUBIC, center
+    crop 224, rescale 1/255, normalise with the CLIP mean / std.  A plain holder: the arithmetic runs in ``HipCLIPVisionModel.preprocess``."""
+
+    def __init__(self, size=None, crop_size=None, rescale_factor=1 / 255, image_mean=(0.48145466, 0.4578275, 0.40821073),
+                 image_std=(0.26862954, 0.26130258, 0.27577711)):
+        super().__init__(size or {"shortest_edge": 224}, crop_size, rescale_factor, image_mean, image_std)
+
+
+class HipCLIPVisionModel(_HipImageEncoder):
+    """The vision tower and ``visual_projection`` of ``transformers.CLIPModel`` (default: ViT-L/14).  ``get_image_features(pixel_values=...)`` is the call the
+    reference makes; ``image_features(images)`` runs the processor's arithmetic on the GPU as well."""
+    max_batch = 32             # 12.4 MB of workspace per image at ViT-L/14
+    _prefix = "clipv"
+
+    def __init__(self, config=None, device="cuda:0", processor=None):
+        cfg = dict(CLIP_VIT_L14_CONFIG)
+        cfg.update(config or {})
+        self.config = cfg
+        self.device = torch.device(device)
+        self.processor = processor or ClipImageProcessor()
+        edge, crop, rescale, mean, std = self.processor.constants()
+        c = L.CsClipVisionConfig(cfg["hidden_size"], cfg["intermediate_size"], cfg["num_hidden_layers"], cfg["num_attention_heads"], cfg["image_size"],
+                                 cfg["patch_size"], cfg["projection_dim"], cfg["layer_norm_eps"], edge, crop, (C.c_float * 3)(*mean), (C.c_float * 3)(*std),
+                                 rescale)
+        h = C.c_void_p()
+        L.check(L.lib().cs_clipv_create(C.byref(c), C.byref(h)))
+        self._init_handle(h, crop, cfg["patch_size"])
+        self._feature_dim = cfg["projection_dim"]
+
+    @torch.no_grad()
+    def get_image_features(self, pixel_values=None, **_ignored):
+        """``reward_model.get_image_features(**inputs)`` with the processor's ``pixel_values`` [B,3,crop,crop] -> ``image_embeds`` [B, projection_dim] fp32"""
+        if pixel_values is None:
+            raise ValueError("You have to specify pixel_values")
+        L.require_cuda(pixel_values, "pixel_values")
+        return self.encode_patches(self.pixel_values_to_patches(pixel_values))
+
+
 def load_dino_reward(device="cuda:0", config=None):
     """edit_ppo/reward_model.py:59-64 without the hub: the dinov2-base shapes and processor constants; the caller loads the weights."""
     processor = DinoImageProcessor()
     return HipDinov2Model(config, device=device, processor=processor), processor
 
 
+def load_clip_reward(device="cuda:0", config=None):
+    """edit_ppo/reward_model.py:128-134 without the hub: the clip-vit-large-patch14 vision shapes and processor constants; the caller loads the weights."""
+    processor = ClipImageProcessor()
+    return HipCLIPVisionModel(config, device=device, processor=processor), processor
+
+
 def load_reward_model(reward_type, device="cuda:0", config=None):
-    """edit_ppo/reward_model.py:25-57.  ``image_psnr`` needs no model; ``dino`` is built here; the other backbones are not implemented."""
+    """edit_ppo/reward_model.py:25-57.  ``image_psnr`` needs no model; ``dino`` and ``clip`` are built here; the other backbones are not implemented."""
     if reward_type == "image_psnr":
         return None, None
     if reward_type == "dino":
         return load_dino_reward(device, config)
-    if reward_type in ("depth", "inception", "segmentation", "clip", "llava", "qwen_vl"):
+    if reward_type == "clip":
+        return load_clip_reward(device, config)
+    if reward_type in ("depth", "inception", "segmentation", "llava", "qwen_vl"):
         raise NotImplementedError(f"reward_type '{reward_type}' needs a third-party backbone network that is not implemented")
     raise ValueError(f"Unknown reward_type: {reward_type}")
 
@@ -202,11 +273,9 @@ def cosine_reward(pred_features, target_features):
     return out
 
 
-def calculate_dino_reward(reward_model, reward_model_processor, model_pred, target, device=None):
-    """edit_ppo/reward_model.py:217-257 for the whole batch in one pass: ``model_pred`` [B,3,H,W] and ``target`` [B,3,H,W] (or [1,3,H,W]: one
-    target shared by the batch, its features computed once) in [0,1] -> rewards [B,1] fp32 in [0, 100].  Values outside [0,1] are clamped."""
-    if not isinstance(reward_model, HipDinov2Model):
-        raise TypeError("reward_type 'dino' needs a HipDinov2Model (load_reward_model('dino')); there is no CPU or eager path")
+def _feature_cosine_reward(reward_model, reward_model_processor, model_pred, target):
+    """the part the image-similarity rewards share: processor check, one front-end and one encoder pass for the 2 B images (a [1,3,H,W] target is
+    encoded once), the cosine tail"""
     if reward_model_processor is not None and reward_model_processor.constants() != reward_model.processor.constants():
         raise ValueError("the processor's constants differ from the ones the model's front end was built with")
     L.require_cuda(model_pred, "model_pred")
@@ -218,3 +287,20 @@ def calculate_dino_reward(reward_model, reward_model_processor, model_pred, targ
         return cosine_reward(reward_model.image_features(model_pred), reward_model.image_features(target))
     feats = reward_model.image_features(torch.cat([model_pred, target]))            # one front-end and one encoder pass for the 2 B images
     return cosine_reward(feats[:B], feats[B:])
+
+
+def calculate_dino_reward(reward_model, reward_model_processor, model_pred, target, device=None):
+    """edit_ppo/reward_model.py:217-257 for the whole batch in one pass: ``model_pred`` [B,3,H,W] and ``target`` [B,3,H,W] (or [1,3,H,W]: one
+    target shared by the batch, its features computed once) in [0,1] -> rewards [B,1] fp32 in [0, 100].  Values outside [0,1] are clamped."""
+    if not isinstance(reward_model, HipDinov2Model):
+        raise TypeError("reward_type 'dino' needs a HipDinov2Model (load_reward_model('dino')); there is no CPU or eager path")
+    return _feature_cosine_reward(reward_model, reward_model_processor, model_pred, target)
+
+
+def calculate_clip_reward(reward_model, reward_model_processor, model_pred, target, device=None):
+    """edit_ppo/reward_model.py:512-552 for the whole batch in one pass, with the argument forms of ``calculate_dino_reward``: cosine similarity of the
+    CLIP ``image_embeds`` of pred and target -> rewards [B,1] fp32 in [0, 100].  Any other ``reward_model`` (``None``, a transformers CLIPModel) raises
+    ``NotImplementedError``: the eager transformers path is not implemented."""
+    if not isinstance(reward_model, HipCLIPVisionModel):
+        raise NotImplementedError("reward_type 'clip' needs a HipCLIPVisionModel (load_reward_model('clip')); the eager transformers path is not implemented")
+    return _feature_cosine_reward(reward_model, reward_model_processor, model_pred, target)

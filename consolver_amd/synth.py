@@ -71,6 +71,27 @@ def synthetic_dinov2_state_dict(manifest, seed=20251229):
     return sd
 
 
+def synthetic_clip_vision_state_dict(manifest, seed=20251230):
+    """CLIP vision tower + projection: matrices (the patch projection included) ~ N(0, 1/fan_in), class and position embeddings 0.5 N, norm gains
+    1 + 0.1 N (``pre_layrnorm`` / ``post_layernorm`` / ``layer_norm1|2``), biases 0.05 N."""
+    g = torch.Generator().manual_seed(seed)
+    sd = {}
+    for name, shape in manifest:
+        if name.endswith("class_embedding") or name.endswith("position_embedding.weight"):
+            w = 0.5 * torch.randn(shape, generator=g)
+        elif name.endswith(".weight") and len(shape) >= 2:
+            fan_in = 1
+            for s in shape[1:]:
+                fan_in *= s
+            w = torch.randn(shape, generator=g) * (1.0 / fan_in) ** 0.5
+        elif "norm" in name and name.endswith(".weight"):
+            w = 1.0 + 0.1 * torch.randn(shape, generator=g)
+        else:
+            w = 0.05 * torch.randn(shape, generator=g)
+        sd[name] = w
+    return sd
+
+
 def synthetic_prompt_embeds(batch, ctx_len=77, dim=768, seed=1001):
     g = torch.Generator().manual_seed(seed)
     x = torch.randn(batch, ctx_len, dim, generator=g)

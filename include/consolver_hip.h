@@ -468,6 +468,52 @@ int cs_vit_forward(CsVit* v, const void* patches, int batch, float* cls_out, voi
 int cs_cosine_reward(const float* pred, const float* target, int batch, int dim, int64_t target_stride, float* out,
                      void* stream);
 
+/* ------------------------------------------------------------------------
+ * CLIP image-similarity reward (reward_type "clip": edit_ppo/reward_model.py:128-134, 512-552;
+ * third-party transformers CLIPModel.get_image_features + the openai/clip-vit-large-patch14 image processor).
+ * ---------------------------------------------------------------------- */
+typedef struct CsClipVisionConfig {
+    int hidden_size;               /* 1024  */
+    int intermediate_size;         /* 4096  */
+    int num_hidden_layers;         /* 24    */
+    int num_attention_heads;       /* 16 (head dim 64) */
+    int image_size;                /* 224: the position table has (image_size / patch_size)^2 + 1 rows, no interpolation */
+    int patch_size;                /* 14    */
+    int projection_dim;            /* 768   */
+    float layer_norm_eps;          /* 1e-5  */
+    /* the processor's constants */
+    int resize_shortest_edge;      /* 224 (PIL BICUBIC) */
+    int crop_size;                 /* 224 (center crop; must equal image_size) */
+    float image_mean[3];           /* 0.48145466, 0.4578275, 0.40821073 */
+    float image_std[3];            /* 0.26862954, 0.26130258, 0.27577711 */
+    double rescale_factor;         /* 1 / 255: the processor rescales in double, rounds to fp32, then normalises in fp32 */
+} CsClipVisionConfig;
+
+typedef struct CsClipVision CsClipVision;
+
+/* host only: builds the weight manifest, touches no GPU */
+int cs_clipv_create(const CsClipVisionConfig* cfg, CsClipVision** out);
+void cs_clipv_destroy(CsClipVision* v);
+/* tensors by their transformers CLIPModel / CLIPVisionModelWithProjection state-dict names ("vision_model.embeddings.class_embedding",
+ * "vision_model.pre_layrnorm.weight" -- transformers' own spelling --, "vision_model.encoder.layers.0.self_attn.k_proj.weight", ...,
+ * "visual_projection.weight"); fp32 host memory */
+int cs_clipv_set_weight(CsClipVision* v, const char* name, const float* data_host, const int64_t* shape, int ndim);
+int cs_clipv_num_weights(const CsClipVision* v);
+const char* cs_clipv_weight_name(const CsClipVision* v, int i, int64_t* shape4, int* ndim);
+int cs_clipv_finalize(CsClipVision* v);
+size_t cs_clipv_workspace_bytes(const CsClipVision* v, int batch);
+double cs_clipv_flops(const CsClipVision* v, int batch);
+/* row length of the patch matrix (3 * patch_size^2 padded to a multiple of 64) and tokens per image */
+int cs_clipv_patch_cols(const CsClipVision* v);
+int cs_clipv_num_tokens(const CsClipVision* v);
+size_t cs_clipv_preprocess_workspace_bytes(const CsClipVision* v, int batch, int height, int width);
+/* the image front end of cs_vit_preprocess with this handle's processor constants (same contract) */
+int cs_clipv_preprocess(CsClipVision* v, const void* images, int dtype, int batch, int height, int width, void* patches,
+                        unsigned char* crop_u8, void* workspace, size_t workspace_bytes, void* stream);
+/* patches from cs_clipv_preprocess -> image_embeds [batch, projection_dim] fp32 = visual_projection(post_layernorm(CLS row)) */
+int cs_clipv_forward(CsClipVision* v, const void* patches, int batch, float* image_embeds, void* workspace, size_t workspace_bytes,
+                     void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -252,6 +252,14 @@ int cs_debug_trace_read(void* dst_host, size_t bytes);
  * over the same, tiles in it, loader wave 4's cycles in its DMA waits, at the tile barriers, unused (at most 4096 slots; tools/attn_lw_trace.py). */
 int cs_debug_attn_trace_read(void* dst_host, size_t bytes);
 
+/* the two ends of the CLIP vision tower (csrc/vit_ops.hip), all device pointers fp16 unless noted:
+ * x [B * (NP + 1)][D] = LayerNorm((t == 0 ? cls : pe[b * NP + t - 1]) + pos[t]) -- sum and normalisation in fp32, one rounding; D % 128 == 0, D <= 2048 */
+int cs_op_clipv_tokens_ln(const void* pe, const void* cls, const void* pos, const void* gamma, const void* beta, float eps, void* x, int B, int NP, int D,
+                          void* stream);
+/* out [B][P] fp32 = LayerNorm(x[b * sample_stride ..][D]) @ w[P][D]^T (no bias); any P >= 1 */
+int cs_op_clipv_head(const void* x, int64_t sample_stride, const void* gamma, const void* beta, float eps, const void* w, int B, int D, int P, float* out,
+                     void* stream);
+
 #ifdef __cplusplus
 }
 #endif
