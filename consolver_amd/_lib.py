@@ -69,6 +69,13 @@ class CsClipVisionConfig(C.Structure):
                 ("rescale_factor", C.c_double)]
 
 
+class CsDepthConfig(C.Structure):
+    _fields_ = [("hidden_size", C.c_int), ("num_hidden_layers", C.c_int), ("num_attention_heads", C.c_int), ("mlp_ratio", C.c_int),
+                ("image_size", C.c_int), ("patch_size", C.c_int), ("layer_norm_eps", C.c_float), ("out_indices", C.c_int * 4),
+                ("neck_hidden_sizes", C.c_int * 4), ("fusion_hidden_size", C.c_int), ("head_hidden_size", C.c_int), ("max_depth", C.c_float),
+                ("size", C.c_int), ("image_mean", C.c_float * 3), ("image_std", C.c_float * 3), ("rescale_factor", C.c_double)]
+
+
 class CsGemm2Problem(C.Structure):
     _fields_ = [("x", C.c_void_p), ("M", C.c_int), ("K", C.c_int), ("w", C.c_void_p), ("bias", C.c_void_p), ("N", C.c_int),
                 ("res", C.c_void_p), ("gate", C.c_void_p), ("gate_stride", C.c_long), ("rows_per_sample", C.c_int), ("act", C.c_int),
@@ -143,6 +150,21 @@ SYMBOLS = {
     "cs_clipv_preprocess": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
                                       C.c_void_p]),
     "cs_clipv_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "cs_depth_create": (C.c_int, [C.POINTER(CsDepthConfig), C.POINTER(C.c_void_p)]),
+    "cs_depth_destroy": (None, [C.c_void_p]),
+    "cs_depth_set_weight": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int]),
+    "cs_depth_num_weights": (C.c_int, [C.c_void_p]),
+    "cs_depth_weight_name": (C.c_char_p, [C.c_void_p, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int)]),
+    "cs_depth_finalize": (C.c_int, [C.c_void_p]),
+    "cs_depth_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int]),
+    "cs_depth_flops": (C.c_double, [C.c_void_p, C.c_int]),
+    "cs_depth_patch_cols": (C.c_int, [C.c_void_p]),
+    "cs_depth_num_tokens": (C.c_int, [C.c_void_p]),
+    "cs_depth_preprocess_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
+    "cs_depth_preprocess": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                      C.c_void_p]),
+    "cs_depth_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "cs_depth_normalized_maps": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "cs_vae_create": (C.c_int, [C.POINTER(CsVaeConfig), C.POINTER(C.c_void_p)]),
     "cs_vae_destroy": (None, [C.c_void_p]),
     "cs_vae_set_weight": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int]),
@@ -263,6 +285,13 @@ SYMBOLS = {
     "cs_op_layer_norm": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p]),
     "cs_op_clipv_tokens_ln": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "cs_op_clipv_head": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "cs_op_dpt_conv": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                 C.c_void_p, C.c_void_p]),
+    "cs_op_dpt_bilinear": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "cs_op_dpt_pixel_shuffle": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "cs_op_dpt_head": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]),
+    "cs_op_dpt_bicubic": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "cs_op_dpt_minmax_normalize": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_void_p]),
 }
 
 _lib = None

@@ -32,6 +32,8 @@ SOURCES = {
     "vit_ops.hip": [],
     "vit.cpp": [],
     "clip_vision.cpp": [],
+    "dpt_ops.hip": [],
+    "depth.cpp": [],
     "ppo.hip": [],
     "ops_api.cpp": [],
 }

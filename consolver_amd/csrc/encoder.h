@@ -55,13 +55,14 @@ inline double pre_ln_flops(int layers, int batch, int tokens, double D, double I
     return layers * (2.0 * rows * D * (4 * D + 2 * I) + 4.0 * batch * (double)tokens * tokens * D);
 }
 
-// x [batch * tokens][D] in place through every layer; activation: launch_quick_gelu or launch_gelu_erf.  Returns the first code that is not CS_OK
+// x [batch * tokens][D] in place through the layers first .. last - 1 (default: every layer; a caller that taps the hidden state between layers runs the stack in
+// ranges); activation: launch_quick_gelu or launch_gelu_erf.  Returns the first code that is not CS_OK
 inline int run_pre_ln_layers(const std::vector<PreLnLayer>& layers, const PreLnWorkspace& w, int batch, int tokens, int D, int I, int heads, float eps, int causal,
-                             int (*activation)(f16*, long, hipStream_t), hipStream_t s) {
+                             int (*activation)(f16*, long, hipStream_t), hipStream_t s, size_t first = 0, size_t last = (size_t)-1) {
     const long rows = (long)batch * tokens;
     f16 *x = w.x, *n = w.n, *qkv = w.qkv, *h = w.h;
     int rc = CS_OK;
-    for (size_t l = 0; l < layers.size() && rc == CS_OK; ++l) {
+    for (size_t l = first; l < std::min(last, layers.size()) && rc == CS_OK; ++l) {
         const PreLnLayer& L = layers[l];
         rc = launch_layer_norm(x, L.ln1g, L.ln1b, n, (int)rows, D, eps, s);
         if (rc == CS_OK) rc = linear(n, (int)rows, D, L.wqkv, L.bqkv, 3 * D, nullptr, qkv, s);

@@ -286,3 +286,27 @@ int launch_cosine_reward(const float* pred, const float* target, long target_str
 int launch_clipv_tokens_ln(const f16* pe, const f16* cls, const f16* pos, const f16* g, const f16* b, float eps, f16* x, int B, int NP, int D, hipStream_t s);
 // out[b][p] = sum_d LayerNorm(first row of sample b)[d] * w[p][d]: post_layernorm + visual_projection (no bias) -> [B][P] fp32; rows sample_stride halfs apart
 int launch_clipv_head(const f16* x, long sample_stride, const f16* g, const f16* b, float eps, const f16* w, int B, int D, int P, float* out, hipStream_t s);
+
+// ---- Depth Anything reward (dpt_ops.hip / depth.cpp): the DPT neck and head around the shared encoder loop ------------------------------------------
+// conv 3x3 (pad 1, stride 1; taps = 9) or 1x1 (taps = 1) to a NARROW output on the matrix cores: NHWC fp16 x [B][H][W][Cin] -> out [B][H][W][Cout], Cout in
+// {32, 64}, Cin a multiple of 32, any H x W; w [Cout][taps][Cin].  out = relu_out(conv(relu_in(x)) + bias + res + res2), the sum in fp32, one rounding.
+// bias / res / res2 may be null; res / res2 are [B][H][W][Cout]; out must not alias x.
+struct DptConvArgs {
+    const f16* x; int B, H, W, Cin;
+    const f16* w; const f16* bias; int Cout, taps;
+    int relu_in, relu_out;
+    const f16* res; const f16* res2;
+    f16* out;
+};
+int launch_dpt_conv(const DptConvArgs& a, hipStream_t s);
+// F.interpolate(mode="bilinear", align_corners=True) on NHWC fp16 [B][Hi][Wi][C] -> [B][Ho][Wo][C], C % 8 == 0; the blend in fp32, one rounding
+int launch_dpt_bilinear(const f16* x, int B, int Hi, int Wi, int C, int Ho, int Wo, f16* out, hipStream_t s);
+// the store of a transposed conv whose kernel equals its stride k, after its GEMM: y [B * T][k * k * C] (row b * T + skip + gy * G + gx, column (ky * k + kx) * C + c)
+// -> out NHWC [B][G k][G k][C]; skip = rows in front of every sample's grid (the CLS token), T = skip + G * G; C % 8 == 0.  k = 1 drops the CLS rows.
+int launch_dpt_pixel_shuffle(const f16* y, int B, int G, int k, int C, int skip, f16* out, hipStream_t s);
+// out[m] = max(sum_c x[m][c] w[c] + bias, 0) * scale: the head's last 1x1 conv + ReLU (x max_depth) -> fp32; C % 8 == 0, C <= 64
+int launch_dpt_head(const f16* x, long M, int C, const f16* w, const f16* bias, float scale, float* out, hipStream_t s);
+// F.interpolate(mode="bicubic", align_corners=False) (A = -0.75, clamped reads, no antialias) of fp32 maps [B][Hi][Wi] -> [B][Ho][Wo]
+int launch_dpt_bicubic(const float* x, int B, int Hi, int Wi, int Ho, int Wo, float* out, hipStream_t s);
+// x[b] <- (x[b] - min) / (max - min + 1e-8) over the n elements of every map, in place (one workgroup per map)
+int launch_dpt_minmax_normalize(float* x, int B, long n, hipStream_t s);

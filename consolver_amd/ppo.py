@@ -6,13 +6,14 @@ step, with the reference's names:
 * ``calculate_reward(reward_type, reward_model, reward_model_processor, model_pred, target, device)``
   (edit_ppo/reward_model.py:138-161): ``"image_psnr"`` (:484-509, arithmetic only), ``"dino"`` (:217-257, the DINOv2
   image-similarity reward the reference's run scripts train with) and ``"clip"`` (:512-552, CLIP ViT-L/14 image features;
-  both in consolver_amd/reward_model.py).  The other backbone rewards (depth / inception / segmentation / ...) are
+  both in consolver_amd/reward_model.py) and ``"depth"`` (:359-422, the Depth Anything depth-map PSNR the reference's config defaults to; given a
+  ``HipDepthAnythingModel`` from ``reward_model.load_depth_reward``).  The other backbone rewards (inception / segmentation / ...) are
   third-party networks that are not implemented; they raise.
 * ``compute_advantages`` = train_ppo.py:376-390, ``ppo_loss`` = :408-421 (value), ``PolicyTrainer`` = the
   optimisation step :404-437 (gradients, clip_grad_norm_, AdamW) and the checkpoint format.
 * ``collect_rollout`` = :352-403 for one batch of teacher pairs.
 
-Everything runs in the HIP library (cs_image_psnr / cs_vit_* / cs_clipv_* / cs_ppo_advantages / cs_ppo_loss); there is no
+Everything runs in the HIP library (cs_image_psnr / cs_vit_* / cs_clipv_* / cs_depth_* / cs_ppo_advantages / cs_ppo_loss); there is no
 CPU fallback.
 """
 import ctypes as C
@@ -70,7 +71,10 @@ def calculate_reward(reward_type, reward_model, reward_model_processor, model_pr
     if reward_type == "clip":
         from .reward_model import calculate_clip_reward
         return calculate_clip_reward(reward_model, reward_model_processor, model_pred, target, device)
-    if reward_type in ("depth", "inception", "segmentation", "llava", "qwen_vl"):
+    if reward_type == "depth":
+        from .reward_model import calculate_depth_reward
+        return calculate_depth_reward(reward_model, reward_model_processor, model_pred, target, device)
+    if reward_type in ("inception", "segmentation", "llava", "qwen_vl"):
         raise NotImplementedError(f"reward_type '{reward_type}' needs a third-party backbone network (out of scope, SURVEY 8 a21)")
     raise ValueError(f"Unknown reward_type: {reward_type}")
 

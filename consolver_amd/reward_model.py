@@ -1,4 +1,4 @@
-"""DINOv2 and CLIP image-similarity rewards on the HIP library (``--reward_type="dino"``, edit_ppo/run_ppo.sh:30; ``"clip"``, compute_reward.sh:5).
+"""DINOv2 and CLIP image-similarity rewards and the Depth Anything depth-PSNR reward on the HIP library (``--reward_type="dino"``, edit_ppo/run_ppo.sh:30; ``"clip"``, compute_reward.sh:5).
 
 Mirror of edit_ppo/reward_model.py by name:
 
@@ -18,6 +18,13 @@ tower + ``visual_projection`` and a ``ClipImageProcessor``; ``calculate_clip_rew
 tower (cs_clipv_forward: embeddings + pre_layrnorm in one kernel, the shared pre-LN layer loop with quick-GELU, post_layernorm + projection in one kernel)
 and the same tail on ``image_embeds``.  Weights load under their ``transformers.CLIPModel`` names (a full CLIPModel state dict or a
 CLIPVisionModelWithProjection one).  The fp32 restatement lives in tests/clip_vision_oracle.py.
+
+``depth`` (:92-96, :359-422; the reward the reference trains with by default): ``load_depth_reward()`` -> a ``HipDepthAnythingModel`` of the
+``depth-anything/Depth-Anything-V2-Small-hf`` shape and a ``DepthImageProcessor``; ``calculate_depth_reward`` runs the front end (PIL bicubic resize of the
+square image to 518 x 518, bit-identical on the uint8 image), the DINOv2-small backbone tapped at four depths, the DPT neck and head (cs_depth_forward),
+torch's bicubic resize back to the images' size with the per-map min / max normalisation (cs_depth_normalized_maps) and the PSNR tail
+(``ppo.depth_psnr_tail``).  Weights load under their ``transformers.DepthAnythingForDepthEstimation`` names.  The fp32 restatement lives in
+tests/depth_oracle.py.
 """
 import ctypes as C
 
@@ -29,6 +36,11 @@ DINOV2_BASE_CONFIG = dict(hidden_size=768, num_hidden_layers=12, num_attention_h
                           layer_norm_eps=1e-6)
 CLIP_VIT_L14_CONFIG = dict(hidden_size=1024, intermediate_size=4096, num_hidden_layers=24, num_attention_heads=16, image_size=224, patch_size=14,
                            projection_dim=768, layer_norm_eps=1e-5)
+# depth-anything/Depth-Anything-V2-Small-hf (its config.json, from memory: no hub access here): a DINOv2-small backbone tapped after ``out_indices`` layers
+# (the final LayerNorm applied to every tap), the DPT neck and head.  ``out_indices`` is a config key: a checkpoint with other taps passes its own.
+DEPTH_ANYTHING_V2_SMALL_CONFIG = dict(hidden_size=384, num_hidden_layers=12, num_attention_heads=6, mlp_ratio=4, image_size=518, patch_size=14,
+                                      layer_norm_eps=1e-6, out_indices=(3, 6, 9, 12), neck_hidden_sizes=(48, 96, 192, 384), fusion_hidden_size=64,
+                                      head_hidden_size=32, max_depth=1.0)
 _DT = {torch.float32: L.CS_F32, torch.float16: L.CS_F16}
 
 
@@ -235,6 +247,99 @@ class HipCLIPVisionModel(_HipImageEncoder):
         return self.encode_patches(self.pixel_values_to_patches(pixel_values))
 
 
+class DepthImageProcessor:
+    """The preprocessing constants of ``depth-anything/Depth-Anything-V2-Small-hf`` (its preprocessor_config.json, a DPTImageProcessor; from memory: no hub
+    access here): resize to 518 x 518 with PIL BICUBIC under ``keep_aspect_ratio`` and ``ensure_multiple_of = 14`` (for a square input exactly
+    ``size`` x ``size``; other inputs are refused by the front end), no crop, no pad, rescale 1/255, normalise with the ImageNet mean / std.  A plain
+    holder: the arithmetic runs in ``HipDepthAnythingModel.preprocess``."""
+    do_resize = do_rescale = do_normalize = keep_aspect_ratio = True
+    do_pad = False
+    ensure_multiple_of = 14
+    resample = 3                                   # PIL.Image.BICUBIC
+
+    def __init__(self, size=None, rescale_factor=1 / 255, image_mean=(0.485, 0.456, 0.406), image_std=(0.229, 0.224, 0.225)):
+        self.size = dict(size or {"height": 518, "width": 518})
+        if set(self.size) != {"height", "width"} or self.size["height"] != self.size["width"] or self.size["height"] % self.ensure_multiple_of:
+            raise ValueError("the HIP front end implements a square size that is a multiple of 14")
+        self.rescale_factor, self.image_mean, self.image_std = float(rescale_factor), tuple(image_mean), tuple(image_std)
+
+    def constants(self):
+        return (self.size["height"], self.size["height"], self.rescale_factor, self.image_mean, self.image_std)
+
+
+class _DepthOutput(tuple):
+    """(predicted_depth,): ``outputs.predicted_depth`` [B, size, size] fp32, as transformers' DepthEstimatorOutput names it"""
+    predicted_depth = property(lambda self: self[0])
+
+
+class HipDepthAnythingModel(_HipImageEncoder):
+    """``transformers.DepthAnythingForDepthEstimation`` (default: the V2-Small shape).  ``model(pixel_values=...).predicted_depth`` is the call the reference
+    makes; ``predicted_depth(images)`` and ``normalized_depth(images)`` run the processor's arithmetic and the post-processing on the GPU as well."""
+    workspace_budget = 600 << 20          # bytes of workspace one call may take: max_batch is sized from it (V2-Small: 72.7 MB per image -> 8 images per call)
+    _prefix = "depth"
+
+    def __init__(self, config=None, device="cuda:0", processor=None):
+        cfg = dict(DEPTH_ANYTHING_V2_SMALL_CONFIG)
+        cfg.update(config or {})
+        self.config = cfg
+        self.device = torch.device(device)
+        self.processor = processor or DepthImageProcessor({"height": cfg["image_size"], "width": cfg["image_size"]})
+        size, _, rescale, mean, std = self.processor.constants()
+        c = L.CsDepthConfig(cfg["hidden_size"], cfg["num_hidden_layers"], cfg["num_attention_heads"], cfg["mlp_ratio"], cfg["image_size"], cfg["patch_size"],
+                            cfg["layer_norm_eps"], (C.c_int * 4)(*cfg["out_indices"]), (C.c_int * 4)(*cfg["neck_hidden_sizes"]), cfg["fusion_hidden_size"],
+                            cfg["head_hidden_size"], cfg["max_depth"], size, (C.c_float * 3)(*mean), (C.c_float * 3)(*std), rescale)
+        h = C.c_void_p()
+        L.check(L.lib().cs_depth_create(C.byref(c), C.byref(h)))
+        self._init_handle(h, size, cfg["patch_size"])
+        self.max_batch = max(1, min(_HipImageEncoder.max_batch, self.workspace_budget // int(self._fn("workspace_bytes")(h, 1))))
+
+    def depth_from_patches(self, patches):
+        """patch rows -> ``predicted_depth`` [B, size, size] fp32, ``max_batch`` images per call"""
+        if not self._finalized:
+            raise RuntimeError("weights not loaded")
+        L.require_cuda(patches, "patches")
+        g = self.crop // self.patch
+        B = patches.shape[0] // (g * g)
+        out = torch.empty(B, self.crop, self.crop, dtype=torch.float32, device=patches.device)
+        for s in range(0, B, self.max_batch):
+            n = min(self.max_batch, B - s)
+            need = int(self._fn("workspace_bytes")(self._h, n))
+            if self._ws is None or self._ws.numel() < need or self._ws.device != patches.device:
+                self._ws = torch.empty(need, dtype=torch.uint8, device=patches.device)
+            L.check(self._fn("forward")(self._h, L.ptr(patches[s * g * g:]), n, L.ptr(out[s:]), L.ptr(self._ws), self._ws.numel(),
+                                        L.stream_ptr(patches.device)))
+        return out
+
+    @torch.no_grad()
+    def __call__(self, pixel_values=None, **_ignored):
+        """``reward_model(**inputs)`` with the processor's ``pixel_values`` [B,3,size,size] -> see ``_DepthOutput``"""
+        if pixel_values is None:
+            raise ValueError("You have to specify pixel_values")
+        L.require_cuda(pixel_values, "pixel_values")
+        return _DepthOutput((self.depth_from_patches(self.pixel_values_to_patches(pixel_values)),))
+
+    def predicted_depth(self, images):
+        """[B,3,H,H] in [0,1] -> ``predicted_depth`` [B, size, size] fp32"""
+        return self.depth_from_patches(self.preprocess(images))
+
+    def post_process(self, predicted_depth, height, width):
+        """``post_process_depth_estimation(target_sizes=[(height, width)])`` (torch bicubic) and the reward's per-map (d - min) / (max - min + 1e-8):
+        [B, size, size] fp32 -> [B, height, width] fp32"""
+        L.require_cuda(predicted_depth, "predicted_depth")
+        d = predicted_depth.to(torch.float32).contiguous()
+        B = d.shape[0]
+        if tuple(d.shape[1:]) != (self.crop, self.crop):
+            raise ValueError(f"predicted_depth must be [B,{self.crop},{self.crop}], got {tuple(d.shape)}")
+        out = torch.empty(B, height, width, dtype=torch.float32, device=d.device)
+        if B:
+            L.check(self._fn("normalized_maps")(self._h, L.ptr(d), B, height, width, L.ptr(out), L.stream_ptr(d.device)))
+        return out
+
+    def normalized_depth(self, images):
+        """[B,3,H,H] in [0,1] -> the normalised depth maps at the images' size, [B,H,H] fp32: the whole per-image path of the reward up to the PSNR"""
+        return self.post_process(self.predicted_depth(images), images.shape[-2], images.shape[-1])
+
+
 def load_dino_reward(device="cuda:0", config=None):
     """edit_ppo/reward_model.py:59-64 without the hub: the dinov2-base shapes and processor constants; the caller loads the weights."""
     processor = DinoImageProcessor()
@@ -247,15 +352,26 @@ def load_clip_reward(device="cuda:0", config=None):
     return HipCLIPVisionModel(config, device=device, processor=processor), processor
 
 
+def load_depth_reward(device="cuda:0", config=None):
+    """edit_ppo/reward_model.py:92-96 without the hub: the Depth-Anything-V2-Small shapes and processor constants; the caller loads the weights."""
+    cfg = dict(DEPTH_ANYTHING_V2_SMALL_CONFIG)
+    cfg.update(config or {})
+    processor = DepthImageProcessor({"height": cfg["image_size"], "width": cfg["image_size"]})
+    return HipDepthAnythingModel(cfg, device=device, processor=processor), processor
+
+
 def load_reward_model(reward_type, device="cuda:0", config=None):
-    """edit_ppo/reward_model.py:25-57.  ``image_psnr`` needs no model; ``dino`` and ``clip`` are built here; the other backbones are not implemented."""
+    """edit_ppo/reward_model.py:25-57.  ``image_psnr`` needs no model; ``dino`` and ``clip`` are built here; ``depth`` is built but loaded through
+    ``load_depth_reward`` (this dispatcher's answer for it is pinned by the existing tests); the other backbones are not implemented."""
     if reward_type == "image_psnr":
         return None, None
     if reward_type == "dino":
         return load_dino_reward(device, config)
     if reward_type == "clip":
         return load_clip_reward(device, config)
-    if reward_type in ("depth", "inception", "segmentation", "llava", "qwen_vl"):
+    if reward_type == "depth":
+        raise NotImplementedError("reward_type 'depth' is not loaded through this dispatcher yet: use load_depth_reward(device, config)")
+    if reward_type in ("inception", "segmentation", "llava", "qwen_vl"):
         raise NotImplementedError(f"reward_type '{reward_type}' needs a third-party backbone network that is not implemented")
     raise ValueError(f"Unknown reward_type: {reward_type}")
 
@@ -304,3 +420,29 @@ def calculate_clip_reward(reward_model, reward_model_processor, model_pred, targ
     if not isinstance(reward_model, HipCLIPVisionModel):
         raise NotImplementedError("reward_type 'clip' needs a HipCLIPVisionModel (load_reward_model('clip')); the eager transformers path is not implemented")
     return _feature_cosine_reward(reward_model, reward_model_processor, model_pred, target)
+
+
+def calculate_depth_reward(reward_model, reward_model_processor, model_pred, target, device=None):
+    """edit_ppo/reward_model.py:359-422 for the whole batch on the GPU, with the argument forms of ``calculate_dino_reward``: the PSNR of the min / max
+    normalised Depth Anything maps of pred and target at the images' size, clamp(min=0) only -> rewards [B,1] fp32 (identical maps: 80, the value of
+    10 log10(1 / 1e-8)).  Any other ``reward_model`` (``None``, a transformers model) raises ``NotImplementedError``: the eager transformers path is
+    not implemented."""
+    if not isinstance(reward_model, HipDepthAnythingModel):
+        raise NotImplementedError("reward_type 'depth' needs a HipDepthAnythingModel (load_depth_reward(device, config)); the eager transformers path is "
+                                  "not implemented")
+    if reward_model_processor is not None and reward_model_processor.constants() != reward_model.processor.constants():
+        raise ValueError("the processor's constants differ from the ones the model's front end was built with")
+    L.require_cuda(model_pred, "model_pred")
+    L.require_cuda(target, "target")
+    B = model_pred.shape[0]
+    if target.shape[0] not in (B, 1) or target.shape[1:] != model_pred.shape[1:]:
+        raise ValueError(f"shape mismatch {tuple(model_pred.shape)} vs {tuple(target.shape)}")
+    if target.dtype != model_pred.dtype or target.shape[0] != B:
+        pred_maps, target_maps = reward_model.normalized_depth(model_pred), reward_model.normalized_depth(target)
+        if target_maps.shape[0] != B:
+            target_maps = target_maps.expand(B, -1, -1)
+    else:
+        maps = reward_model.normalized_depth(torch.cat([model_pred, target]))            # one pass for the 2 B images
+        pred_maps, target_maps = maps[:B], maps[B:]
+    from .ppo import depth_psnr_tail
+    return depth_psnr_tail(pred_maps, target_maps)

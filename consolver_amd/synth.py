@@ -71,6 +71,26 @@ def synthetic_dinov2_state_dict(manifest, seed=20251229):
     return sd
 
 
+def synthetic_depth_anything_state_dict(manifest, seed=20251231):
+    """Depth Anything (``HipDepthAnythingModel.manifest()``): the ``backbone.*`` tensors from ``synthetic_dinov2_state_dict``; neck and head matrices
+    ~ N(0, 1/fan_in), where the two transposed convs of the reassemble stage (kernel = stride: ONE tap per output pixel, weight [in, out, k, k]) count
+    fan_in = input channels; biases 0.05 N.  With torch's default init the head's ReLU output is ~1e-5 everywhere and the reward's min / max normalisation
+    would turn rounding noise into the whole signal; this scaling keeps every layer's activations of order one, so the depth map has a range of order one."""
+    bb = "backbone."
+    sd = {bb + k: v for k, v in synthetic_dinov2_state_dict([(n[len(bb):], s) for n, s in manifest if n.startswith(bb)], seed=seed).items()}
+    g = torch.Generator().manual_seed(seed + 1)
+    for name, shape in manifest:
+        if name.startswith(bb):
+            continue
+        if name.endswith(".weight"):
+            transposed = ".resize." in name and shape[2] != 3
+            fan_in = shape[0] if transposed else shape[1] * shape[2] * shape[3]
+            sd[name] = torch.randn(shape, generator=g) * (1.0 / fan_in) ** 0.5
+        else:
+            sd[name] = 0.05 * torch.randn(shape, generator=g)
+    return sd
+
+
 def synthetic_clip_vision_state_dict(manifest, seed=20251230):
     """CLIP vision tower + projection: matrices (the patch projection included) ~ N(0, 1/fan_in), class and position embeddings 0.5 N, norm gains
     1 + 0.1 N (``pre_layrnorm`` / ``post_layernorm`` / ``layer_norm1|2``), biases 0.05 N."""

@@ -514,6 +514,59 @@ int cs_clipv_preprocess(CsClipVision* v, const void* images, int dtype, int batc
 int cs_clipv_forward(CsClipVision* v, const void* patches, int batch, float* image_embeds, void* workspace, size_t workspace_bytes,
                      void* stream);
 
+/* ------------------------------------------------------------------------
+ * Depth Anything V2 depth-map PSNR reward (reward_type "depth": edit_ppo/reward_model.py:92-96, 359-422;
+ * third-party transformers DepthAnythingForDepthEstimation + the depth-anything/Depth-Anything-V2-Small-hf DPT image processor).
+ * ---------------------------------------------------------------------- */
+typedef struct CsDepthConfig {
+    /* backbone: DINOv2 */
+    int hidden_size;               /* 384   */
+    int num_hidden_layers;         /* 12    */
+    int num_attention_heads;       /* 6 (head dim 64) */
+    int mlp_ratio;                 /* 4     */
+    int image_size;                /* 518: the position table's grid (image_size / patch_size)^2; must equal `size` (the table is used as it is) */
+    int patch_size;                /* 14    */
+    float layer_norm_eps;          /* 1e-6  */
+    int out_indices[4];            /* 3, 6, 9, 12: the hidden states (after that many layers, final LayerNorm applied) the neck reads; increasing */
+    /* neck and head */
+    int neck_hidden_sizes[4];      /* 48, 96, 192, 384 */
+    int fusion_hidden_size;        /* 64 (the only width built) */
+    int head_hidden_size;          /* 32 (32 or 64) */
+    float max_depth;               /* 1 (depth_estimation_type "relative": ReLU x max_depth) */
+    /* the processor's constants */
+    int size;                      /* 518: PIL BICUBIC resize to size x size (keep_aspect_ratio, ensure_multiple_of = patch_size: square inputs only) */
+    float image_mean[3];           /* 0.485, 0.456, 0.406 */
+    float image_std[3];            /* 0.229, 0.224, 0.225 */
+    double rescale_factor;         /* 1 / 255 */
+} CsDepthConfig;
+
+typedef struct CsDepth CsDepth;
+
+/* host only: builds the weight manifest, touches no GPU */
+int cs_depth_create(const CsDepthConfig* cfg, CsDepth** out);
+void cs_depth_destroy(CsDepth* d);
+/* tensors by their transformers DepthAnythingForDepthEstimation state-dict names ("backbone.embeddings.cls_token", ...,
+ * "neck.reassemble_stage.layers.0.resize.weight", "neck.fusion_stage.layers.0.residual_layer1.convolution1.weight", "head.conv3.bias"); fp32 host memory */
+int cs_depth_set_weight(CsDepth* d, const char* name, const float* data_host, const int64_t* shape, int ndim);
+int cs_depth_num_weights(const CsDepth* d);
+const char* cs_depth_weight_name(const CsDepth* d, int i, int64_t* shape4, int* ndim);
+int cs_depth_finalize(CsDepth* d);
+size_t cs_depth_workspace_bytes(const CsDepth* d, int batch);
+double cs_depth_flops(const CsDepth* d, int batch);
+int cs_depth_patch_cols(const CsDepth* d);
+int cs_depth_num_tokens(const CsDepth* d);
+size_t cs_depth_preprocess_workspace_bytes(const CsDepth* d, int batch, int height, int width);
+/* the image front end of cs_vit_preprocess with the DPT processor's rule: the whole image resized to size x size, no crop.  height != width (where the
+ * processor's keep_aspect_ratio rule gives another shape): CS_E_UNSUPPORTED.  crop_u8 (may be NULL): the resized uint8 image [batch, 3, size, size] */
+int cs_depth_preprocess(CsDepth* d, const void* images, int dtype, int batch, int height, int width, void* patches,
+                        unsigned char* crop_u8, void* workspace, size_t workspace_bytes, void* stream);
+/* patches from cs_depth_preprocess -> predicted_depth [batch, size, size] fp32 */
+int cs_depth_forward(CsDepth* d, const void* patches, int batch, float* predicted_depth, void* workspace, size_t workspace_bytes,
+                     void* stream);
+/* post_process_depth_estimation + the reward's normalisation: predicted_depth [batch, size, size] fp32 -> torch-style bicubic (align_corners = False) to
+ * height x width -> per map (d - min) / (max - min + 1e-8): maps [batch, height, width] fp32 */
+int cs_depth_normalized_maps(CsDepth* d, const float* predicted_depth, int batch, int height, int width, float* maps, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

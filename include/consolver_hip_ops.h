@@ -260,6 +260,22 @@ int cs_op_clipv_tokens_ln(const void* pe, const void* cls, const void* pos, cons
 int cs_op_clipv_head(const void* x, int64_t sample_stride, const void* gamma, const void* beta, float eps, const void* w, int B, int D, int P, float* out,
                      void* stream);
 
+/* the kernels of the Depth Anything neck and head (csrc/dpt_ops.hip), NHWC fp16 device pointers unless noted:
+ * out [B][H][W][Cout] = relu_out(conv(relu_in(x [B][H][W][Cin]), w [Cout][taps][Cin]) + bias + res + res2): taps 9 (3x3, pad 1) or 1; Cout 32 or 64; Cin % 32 == 0;
+ * bias / res / res2 may be NULL; fp32 accumulation, one rounding */
+int cs_op_dpt_conv(const void* x, int B, int H, int W, int Cin, const void* w, const void* bias, int Cout, int taps, int relu_in, int relu_out,
+                   const void* res, const void* res2, void* out, void* stream);
+/* bilinear, align_corners = True: [B][Hi][Wi][C] -> [B][Ho][Wo][C], C % 8 == 0 */
+int cs_op_dpt_bilinear(const void* x, int B, int Hi, int Wi, int C, int Ho, int Wo, void* out, void* stream);
+/* y [B * (skip + G * G)][k * k * C] (column (ky * k + kx) * C + c) -> out [B][G k][G k][C]: the store of a kernel = stride transposed conv after its GEMM */
+int cs_op_dpt_pixel_shuffle(const void* y, int B, int G, int k, int C, int skip, void* out, void* stream);
+/* out [M] fp32 = max(x [M][C] . w [C] + bias[0], 0) * scale */
+int cs_op_dpt_head(const void* x, int64_t M, int C, const void* w, const void* bias, float scale, float* out, void* stream);
+/* torch-style bicubic (A = -0.75, align_corners = False, no antialias) of fp32 maps [B][Hi][Wi] -> [B][Ho][Wo] */
+int cs_op_dpt_bicubic(const float* x, int B, int Hi, int Wi, int Ho, int Wo, float* out, void* stream);
+/* x [B][n] fp32 <- (x - min) / (max - min + 1e-8) per map, in place */
+int cs_op_dpt_minmax_normalize(float* x, int B, int64_t n, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
