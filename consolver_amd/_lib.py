@@ -121,49 +121,7 @@ SYMBOLS = {
     "cs_clip_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int]),
     "cs_clip_flops": (C.c_double, [C.c_void_p, C.c_int, C.c_int]),
     "cs_clip_encode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
-    "cs_vit_create": (C.c_int, [C.POINTER(CsVitConfig), C.POINTER(C.c_void_p)]),
-    "cs_vit_destroy": (None, [C.c_void_p]),
-    "cs_vit_set_weight": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int]),
-    "cs_vit_num_weights": (C.c_int, [C.c_void_p]),
-    "cs_vit_weight_name": (C.c_char_p, [C.c_void_p, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int)]),
-    "cs_vit_finalize": (C.c_int, [C.c_void_p]),
-    "cs_vit_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int]),
-    "cs_vit_flops": (C.c_double, [C.c_void_p, C.c_int]),
-    "cs_vit_patch_cols": (C.c_int, [C.c_void_p]),
-    "cs_vit_num_tokens": (C.c_int, [C.c_void_p]),
-    "cs_vit_preprocess_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
-    "cs_vit_preprocess": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
-                                    C.c_void_p]),
-    "cs_vit_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "cs_cosine_reward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p]),
-    "cs_clipv_create": (C.c_int, [C.POINTER(CsClipVisionConfig), C.POINTER(C.c_void_p)]),
-    "cs_clipv_destroy": (None, [C.c_void_p]),
-    "cs_clipv_set_weight": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int]),
-    "cs_clipv_num_weights": (C.c_int, [C.c_void_p]),
-    "cs_clipv_weight_name": (C.c_char_p, [C.c_void_p, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int)]),
-    "cs_clipv_finalize": (C.c_int, [C.c_void_p]),
-    "cs_clipv_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int]),
-    "cs_clipv_flops": (C.c_double, [C.c_void_p, C.c_int]),
-    "cs_clipv_patch_cols": (C.c_int, [C.c_void_p]),
-    "cs_clipv_num_tokens": (C.c_int, [C.c_void_p]),
-    "cs_clipv_preprocess_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
-    "cs_clipv_preprocess": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
-                                      C.c_void_p]),
-    "cs_clipv_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
-    "cs_depth_create": (C.c_int, [C.POINTER(CsDepthConfig), C.POINTER(C.c_void_p)]),
-    "cs_depth_destroy": (None, [C.c_void_p]),
-    "cs_depth_set_weight": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int]),
-    "cs_depth_num_weights": (C.c_int, [C.c_void_p]),
-    "cs_depth_weight_name": (C.c_char_p, [C.c_void_p, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int)]),
-    "cs_depth_finalize": (C.c_int, [C.c_void_p]),
-    "cs_depth_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int]),
-    "cs_depth_flops": (C.c_double, [C.c_void_p, C.c_int]),
-    "cs_depth_patch_cols": (C.c_int, [C.c_void_p]),
-    "cs_depth_num_tokens": (C.c_int, [C.c_void_p]),
-    "cs_depth_preprocess_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
-    "cs_depth_preprocess": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
-                                      C.c_void_p]),
-    "cs_depth_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "cs_depth_normalized_maps": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "cs_vae_create": (C.c_int, [C.POINTER(CsVaeConfig), C.POINTER(C.c_void_p)]),
     "cs_vae_destroy": (None, [C.c_void_p]),
@@ -293,6 +251,25 @@ SYMBOLS = {
     "cs_op_dpt_bicubic": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "cs_op_dpt_minmax_normalize": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_void_p]),
 }
+
+# the three image-tower handle families (csrc/image_tower.h) declare the same 13 entry points, each over its own config struct
+for _prefix, _config in (("vit", CsVitConfig), ("clipv", CsClipVisionConfig), ("depth", CsDepthConfig)):
+    SYMBOLS.update({
+        f"cs_{_prefix}_create": (C.c_int, [C.POINTER(_config), C.POINTER(C.c_void_p)]),
+        f"cs_{_prefix}_destroy": (None, [C.c_void_p]),
+        f"cs_{_prefix}_set_weight": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int]),
+        f"cs_{_prefix}_num_weights": (C.c_int, [C.c_void_p]),
+        f"cs_{_prefix}_weight_name": (C.c_char_p, [C.c_void_p, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int)]),
+        f"cs_{_prefix}_finalize": (C.c_int, [C.c_void_p]),
+        f"cs_{_prefix}_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int]),
+        f"cs_{_prefix}_flops": (C.c_double, [C.c_void_p, C.c_int]),
+        f"cs_{_prefix}_patch_cols": (C.c_int, [C.c_void_p]),
+        f"cs_{_prefix}_num_tokens": (C.c_int, [C.c_void_p]),
+        f"cs_{_prefix}_preprocess_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
+        f"cs_{_prefix}_preprocess": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                               C.c_void_p]),
+        f"cs_{_prefix}_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    })
 
 _lib = None
 

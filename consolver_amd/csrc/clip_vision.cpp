@@ -5,31 +5,28 @@
 // table, pre_layrnorm, 24 pre-LN layers with quick-GELU, post_layernorm of the CLS row, bias-free visual_projection) -> image_embeds [B, 768] fp32.
 // The front end is the DINOv2 reward's (vit_ops.hip, with this processor's constants), the layer stack is encoder.h's loop (unmasked, quick-GELU, head dim 64);
 // what CLIP has of its own are the two ends: launch_clipv_tokens_ln (embeddings + pre_layrnorm in one pass) and launch_clipv_head.
-#include "encoder.h"
-#include "image_front_end.h"
+#include "image_tower.h"
 #include "consolver_hip.h"
 #include "../../include/consolver_hip_ops.h"
 
 struct CsClipVision {
     CsClipVisionConfig cfg;
-    int G = 0, NP = 0, T = 0, K = 0, Kpad = 0;             // patch grid, patches, tokens, patch-row length (and padded)
-    WeightStore<float> weights;                            // fp32 staging, rounded once at upload
-    f16 *wpatch = nullptr, *cls = nullptr, *pos = nullptr, *preg = nullptr, *preb = nullptr, *postg = nullptr, *postb = nullptr, *wproj = nullptr;
-    std::vector<PreLnLayer> layers;
-    image_front_end::PlanCache plans;                      // resize tables per input (height, width), bounded (image_front_end.h)
+    ImageTower tower;                                      // its final LayerNorm is post_layernorm
+    f16 *preg = nullptr, *preb = nullptr, *wproj = nullptr;
 };
 
 namespace {
 
+const TowerNames NAMES = {"clip vision", "clipv", "clip vision handle is NULL"};
 const char* const VM = "vision_model.";
 
 void build_manifest(CsClipVision* c) {          // transformers CLIPVisionModelWithProjection.state_dict() order (CLIPModel's vision part under the same names)
-    WeightManifest& m = c->weights;
+    WeightManifest& m = c->tower.weights;
     const int D = c->cfg.hidden_size, I = c->cfg.intermediate_size, P = c->cfg.patch_size;
     const std::string v = VM;
     m.expect(v + "embeddings.class_embedding", {D});
     m.expect(v + "embeddings.patch_embedding.weight", {D, 3, P, P});
-    m.expect(v + "embeddings.position_embedding.weight", {c->T, D});
+    m.expect(v + "embeddings.position_embedding.weight", {c->tower.T, D});
     m.expect(v + "pre_layrnorm.weight", {D}); m.expect(v + "pre_layrnorm.bias", {D});
     for (int l = 0; l < c->cfg.num_hidden_layers; ++l) {
         const std::string p = v + "encoder.layers." + std::to_string(l);
@@ -45,25 +42,44 @@ void build_manifest(CsClipVision* c) {          // transformers CLIPVisionModelW
     m.expect("visual_projection.weight", {c->cfg.projection_dim, D});
 }
 
+bool pack(CsClipVision* c) {
+    ImageTower& t = c->tower;
+    WeightStore<float>& W = t.weights;
+    const std::string v = VM;
+    auto T = [&](const std::string& n) -> const std::vector<float>& { return W.at(v + n).data; };
+    t.wpatch = image_tower::pack_patch_projection(t, v + "embeddings.patch_embedding.weight");          // no bias in CLIP
+    t.cls = W.upload(T("embeddings.class_embedding")); t.pos = W.upload(T("embeddings.position_embedding.weight"));
+    c->preg = W.upload(T("pre_layrnorm.weight")); c->preb = W.upload(T("pre_layrnorm.bias"));
+    t.lnfg = W.upload(T("post_layernorm.weight")); t.lnfb = W.upload(T("post_layernorm.bias"));
+    c->wproj = W.upload(W.at("visual_projection.weight").data);
+    bool ok = t.wpatch && t.cls && t.pos && c->preg && c->preb && t.lnfg && t.lnfb && c->wproj;
+    t.layers.resize(c->cfg.num_hidden_layers);
+    for (int l = 0; l < c->cfg.num_hidden_layers && ok; ++l) {
+        const std::string p = v + "encoder.layers." + std::to_string(l);
+        ok = pack_pre_ln_layer<float>(W, {p + ".self_attn.q_proj", p + ".self_attn.k_proj", p + ".self_attn.v_proj", p + ".self_attn.out_proj",
+                                          p + ".layer_norm1", p + ".layer_norm2", p + ".mlp.fc1", p + ".mlp.fc2"}, nullptr, nullptr, t.layers[l]);
+    }
+    return ok;
+}
+
 }  // namespace
 
 extern "C" {
 
 int cs_clipv_create(const CsClipVisionConfig* cfg, CsClipVision** out) {
     if (!cfg || !out) CS_FAIL(CS_E_ARG, "cfg/out is NULL");
-    if (cfg->hidden_size < 128 || cfg->hidden_size % 128 || cfg->hidden_size > 2048 || cfg->intermediate_size < 128 || cfg->intermediate_size % 128)
-        CS_FAIL(CS_E_SHAPE, "clip vision: hidden (up to 2048) / intermediate size must be multiples of 128");
-    if (cfg->num_attention_heads < 1 || cfg->hidden_size != cfg->num_attention_heads * 64) CS_FAIL(CS_E_UNSUPPORTED, "clip vision: built for heads of dim 64");
-    if (cfg->num_hidden_layers < 1 || cfg->patch_size < 1 || cfg->image_size < cfg->patch_size || cfg->image_size % cfg->patch_size || cfg->projection_dim < 1)
-        CS_FAIL(CS_E_ARG, "clip vision: bad config");
+    int rc = image_tower::check_encoder_config(NAMES.who, "hidden (up to 2048) / intermediate size", 2048, cfg->hidden_size, cfg->intermediate_size, cfg->num_attention_heads,
+                                               cfg->num_hidden_layers, cfg->patch_size, cfg->image_size);          // (launch_clipv_head holds a row of at most 2048)
+    if (rc != CS_OK) return rc;
+    if (cfg->projection_dim < 1) CS_FAIL(CS_E_ARG, "clip vision: bad config");
     if (cfg->crop_size != cfg->image_size) CS_FAIL(CS_E_UNSUPPORTED, "clip vision: crop_size %d must equal image_size %d (CLIP's position table is not interpolated)",
                                                    cfg->crop_size, cfg->image_size);
     if (cfg->resize_shortest_edge < cfg->crop_size) CS_FAIL(CS_E_ARG, "clip vision: crop_size must be at most resize_shortest_edge");
-    for (int i = 0; i < 3; ++i) if (!(cfg->image_std[i] > 0.f)) CS_FAIL(CS_E_ARG, "clip vision: image_std must be positive");
+    if ((rc = image_tower::check_image_std(NAMES.who, cfg->image_std)) != CS_OK) return rc;
     CsClipVision* c = new CsClipVision();
     c->cfg = *cfg;
-    c->G = cfg->crop_size / cfg->patch_size; c->NP = c->G * c->G; c->T = c->NP + 1;
-    c->K = 3 * cfg->patch_size * cfg->patch_size; c->Kpad = (c->K + 63) / 64 * 64;
+    c->tower.init(cfg->hidden_size, cfg->intermediate_size, cfg->num_attention_heads, cfg->layer_norm_eps, cfg->patch_size, cfg->resize_shortest_edge, cfg->crop_size,
+                  cfg->image_mean, cfg->image_std, cfg->rescale_factor);
     build_manifest(c);
     *out = c;
     return CS_OK;
@@ -71,103 +87,51 @@ int cs_clipv_create(const CsClipVisionConfig* cfg, CsClipVision** out) {
 
 void cs_clipv_destroy(CsClipVision* c) {
     if (!c) return;
-    c->weights.free_device();
-    c->plans.free_device();
+    c->tower.free_device();
     delete c;
 }
 
-int cs_clipv_num_weights(const CsClipVision* c) { return c ? c->weights.count() : 0; }
+int cs_clipv_num_weights(const CsClipVision* c) { return c ? c->tower.weights.count() : 0; }
 
-const char* cs_clipv_weight_name(const CsClipVision* c, int i, int64_t* shape4, int* ndim) { return c ? c->weights.name_at(i, shape4, 4, ndim) : nullptr; }
+const char* cs_clipv_weight_name(const CsClipVision* c, int i, int64_t* shape4, int* ndim) { return c ? c->tower.weights.name_at(i, shape4, 4, ndim) : nullptr; }
 
 int cs_clipv_set_weight(CsClipVision* c, const char* name, const float* data, const int64_t* shape, int ndim) {
-    if (!c) CS_FAIL(CS_E_ARG, "null argument");
-    return c->weights.set(name, data, shape, ndim);
+    return image_tower::set_weight(tower_of(c), name, data, shape, ndim);
 }
 
-int cs_clipv_finalize(CsClipVision* c) {
-    if (!c) CS_FAIL(CS_E_ARG, "null");
-    WeightStore<float>& W = c->weights;
-    if (W.finalized) return CS_OK;
-    if (const std::string* n = W.first_missing()) CS_FAIL(CS_E_STATE, "missing weight '%s'", n->c_str());
-    const std::string v = VM;
-    auto T = [&](const std::string& n) -> const std::vector<float>& { return W.at(v + n).data; };
-    const int D = c->cfg.hidden_size, K = c->K, Kpad = c->Kpad;
-    {   // patch projection [D][3 P P] -> [D][Kpad] (no bias in CLIP)
-        const auto& w = T("embeddings.patch_embedding.weight");
-        std::vector<float> wp((size_t)D * Kpad, 0.f);
-        for (int n = 0; n < D; ++n) std::copy(w.begin() + (size_t)n * K, w.begin() + (size_t)(n + 1) * K, wp.begin() + (size_t)n * Kpad);
-        c->wpatch = W.upload(wp);
-    }
-    c->cls = W.upload(T("embeddings.class_embedding")); c->pos = W.upload(T("embeddings.position_embedding.weight"));
-    c->preg = W.upload(T("pre_layrnorm.weight")); c->preb = W.upload(T("pre_layrnorm.bias"));
-    c->postg = W.upload(T("post_layernorm.weight")); c->postb = W.upload(T("post_layernorm.bias"));
-    c->wproj = W.upload(W.at("visual_projection.weight").data);
-    bool ok = c->wpatch && c->cls && c->pos && c->preg && c->preb && c->postg && c->postb && c->wproj;
-    c->layers.resize(c->cfg.num_hidden_layers);
-    for (int l = 0; l < c->cfg.num_hidden_layers && ok; ++l) {
-        const std::string p = v + "encoder.layers." + std::to_string(l);
-        ok = pack_pre_ln_layer<float>(W, {p + ".self_attn.q_proj", p + ".self_attn.k_proj", p + ".self_attn.v_proj", p + ".self_attn.out_proj",
-                                          p + ".layer_norm1", p + ".layer_norm2", p + ".mlp.fc1", p + ".mlp.fc2"}, nullptr, nullptr, c->layers[l]);
-    }
-    if (!ok) CS_FAIL(CS_E_HIP, "clip vision: weight upload failed (hipMalloc/hipMemcpy)");
-    W.release_host();
-    W.finalized = true;
-    return CS_OK;
-}
+int cs_clipv_finalize(CsClipVision* c) { return image_tower::finalize(NAMES, tower_of(c), [&] { return pack(c); }); }
 
-int cs_clipv_patch_cols(const CsClipVision* c) { return c ? c->Kpad : 0; }
-int cs_clipv_num_tokens(const CsClipVision* c) { return c ? c->T : 0; }
+int cs_clipv_patch_cols(const CsClipVision* c) { return c ? c->tower.Kpad : 0; }
+int cs_clipv_num_tokens(const CsClipVision* c) { return c ? c->tower.T : 0; }
 
-size_t cs_clipv_workspace_bytes(const CsClipVision* c, int batch) {
-    if (!c || batch <= 0) return 0;
-    const size_t D = c->cfg.hidden_size;
-    return (pre_ln_workspace_elems((size_t)batch * c->T, D, c->cfg.intermediate_size) + (size_t)batch * c->NP * D) * sizeof(f16) + 4096;   // the encoder stack's, patch embeddings
-}
+size_t cs_clipv_workspace_bytes(const CsClipVision* c, int batch) { return !c || batch <= 0 ? 0 : c->tower.workspace_elems((size_t)batch) * sizeof(f16) + 4096; }
 
 double cs_clipv_flops(const CsClipVision* c, int batch) {
-    if (!c) return 0;
-    const double D = c->cfg.hidden_size;
-    return 2.0 * batch * c->NP * (double)c->K * D + pre_ln_flops(c->cfg.num_hidden_layers, batch, c->T, D, c->cfg.intermediate_size)
-         + 2.0 * batch * D * c->cfg.projection_dim;
+    return c ? c->tower.flops(c->cfg.num_hidden_layers, batch) + 2.0 * batch * (double)c->cfg.hidden_size * c->cfg.projection_dim : 0;
 }
 
 size_t cs_clipv_preprocess_workspace_bytes(const CsClipVision* c, int batch, int height, int width) {
-    if (!c || batch <= 0 || height <= 0 || width <= 0) return 0;
-    return (size_t)batch * 3 * height * c->cfg.crop_size + 256;          // the horizontal pass's rows (at most every input row) x crop columns, uint8
+    return image_tower::preprocess_workspace_bytes(tower_of(c), batch, height, width);
 }
 
 int cs_clipv_preprocess(CsClipVision* c, const void* images, int dtype, int batch, int height, int width, void* patches, unsigned char* crop_u8,
                         void* workspace, size_t workspace_bytes, void* stream) {
-    if (!c) CS_FAIL(CS_E_ARG, "clip vision handle is NULL");
-    if (batch < 0) CS_FAIL(CS_E_ARG, "negative size");
-    if (batch == 0) return CS_OK;
-    if (!images || !patches || !workspace) CS_FAIL(CS_E_ARG, "null pointer");
-    const image_front_end::Plan* pl = nullptr;
-    const int rc = c->plans.get_plan("clip vision", c->cfg.resize_shortest_edge, c->cfg.crop_size, height, width, &pl);
-    if (rc != CS_OK) return rc;
-    if (workspace_bytes < (size_t)batch * 3 * pl->dev.nrows * c->cfg.crop_size) CS_FAIL(CS_E_ARG, "clip vision: preprocess workspace too small");
-    return launch_vit_front_end(images, dtype, batch, height, width, pl->dev, c->cfg.image_mean, c->cfg.image_std, c->cfg.rescale_factor,
-                                c->cfg.patch_size, c->G, c->Kpad, (unsigned char*)workspace, (f16*)patches, crop_u8, (hipStream_t)stream);
+    return image_tower::preprocess(NAMES, tower_of(c), images, dtype, batch, height, width, patches, crop_u8, workspace, workspace_bytes, stream);
 }
 
 int cs_clipv_forward(CsClipVision* c, const void* patches, int batch, float* image_embeds, void* workspace, size_t workspace_bytes, void* stream) {
-    if (!c) CS_FAIL(CS_E_ARG, "clip vision handle is NULL");
-    if (!c->weights.finalized) CS_FAIL(CS_E_STATE, "cs_clipv_finalize has not been called");
-    if (batch < 0) CS_FAIL(CS_E_ARG, "negative size");
-    if (batch == 0) return CS_OK;
-    if (!patches || !image_embeds || !workspace) CS_FAIL(CS_E_ARG, "null pointer");
-    if (workspace_bytes < cs_clipv_workspace_bytes(c, batch)) CS_FAIL(CS_E_ARG, "clip vision: workspace too small");
-    const int D = c->cfg.hidden_size, I = c->cfg.intermediate_size, H = c->cfg.num_attention_heads, Tn = c->T;
-    if ((long)batch * Tn > 0x7fffffffL / std::max(I, 3 * D)) CS_FAIL(CS_E_SHAPE, "clip vision: batch too large for one call");
+    bool run = false;
+    int rc = image_tower::begin_forward(NAMES, tower_of(c), batch, patches && image_embeds && workspace, workspace_bytes, cs_clipv_workspace_bytes(c, batch), &run);
+    if (!run) return rc;
+    const ImageTower& t = c->tower;
+    if (t.too_many_rows(batch)) CS_FAIL(CS_E_SHAPE, "clip vision: batch too large for one call");
     hipStream_t s = (hipStream_t)stream;
-    const long rows = (long)batch * Tn;
-    const PreLnWorkspace w = carve_pre_ln(workspace, rows, D, I);
+    const PreLnWorkspace w = carve_pre_ln(workspace, (long)batch * t.T, t.D, t.I);
     f16* pe = w.end;
-    int rc = linear((const f16*)patches, batch * c->NP, c->Kpad, c->wpatch, nullptr, D, nullptr, pe, s);             // CLIP's patch conv has no bias
-    if (rc == CS_OK) rc = launch_clipv_tokens_ln(pe, c->cls, c->pos, c->preg, c->preb, c->cfg.layer_norm_eps, w.x, batch, c->NP, D, s);
-    if (rc == CS_OK) rc = run_pre_ln_layers(c->layers, w, batch, Tn, D, I, H, c->cfg.layer_norm_eps, 0, launch_quick_gelu, s);
-    if (rc == CS_OK) rc = launch_clipv_head(w.x, (long)Tn * D, c->postg, c->postb, c->cfg.layer_norm_eps, c->wproj, batch, D, c->cfg.projection_dim, image_embeds, s);
+    rc = linear((const f16*)patches, batch * t.NP, t.Kpad, t.wpatch, nullptr, t.D, nullptr, pe, s);             // CLIP's patch conv has no bias
+    if (rc == CS_OK) rc = launch_clipv_tokens_ln(pe, t.cls, t.pos, c->preg, c->preb, t.eps, w.x, batch, t.NP, t.D, s);
+    if (rc == CS_OK) rc = run_pre_ln_layers(t.layers, w, batch, t.T, t.D, t.I, t.heads, t.eps, 0, launch_quick_gelu, s);
+    if (rc == CS_OK) rc = launch_clipv_head(w.x, (long)t.T * t.D, t.lnfg, t.lnfb, t.eps, c->wproj, batch, t.D, c->cfg.projection_dim, image_embeds, s);
     return rc;
 }
 

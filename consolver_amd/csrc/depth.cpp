@@ -10,12 +10,9 @@
 //     the token to its k x k output pixels): one GEMM [tokens][D] x [k k C][D]^T through launch_igemm, then the pixel-shuffle store;
 //   * channel counts the kernels cannot take are zero-padded in the weights of the layer that produces them and of the one that consumes them (48 -> 64 for the
 //     narrow conv's 32-channel k step; 192 -> 256 for the GEMM's 128-column tile).
-#include "encoder.h"
-#include "image_front_end.h"
+#include "image_tower.h"
 #include "consolver_hip.h"
 #include "../../include/consolver_hip_ops.h"
-
-#include <cmath>
 
 namespace {
 struct DConv { f16* w = nullptr; f16* b = nullptr; };
@@ -25,21 +22,20 @@ constexpr int RK[4] = {4, 2, 1, 1};      // reassemble_factors 4, 2, 1, 0.5: the
 
 struct CsDepth {
     CsDepthConfig cfg;
-    int G = 0, NP = 0, T = 0, K = 0, Kpad = 0, I = 0, S = 0, F = 0, HH = 0;   // patch grid, patches, tokens, patch-row length (and padded), MLP width, image size, fusion / head widths
+    ImageTower tower;                      // the DINOv2 backbone, its processor resizing to edge = crop = size: the whole image, no crop
+    int S = 0, F = 0, HH = 0;              // image size, fusion / head widths
     int g[4] = {0, 0, 0, 0};               // sizes of the four reassembled maps: 4 G, 2 G, G, (G - 1) / 2 + 1
     int cp[4] = {0, 0, 0, 0};              // their channel counts as stored (neck_hidden_sizes padded)
-    WeightStore<float> weights;            // fp32 staging: every fold is formed in fp32 and rounded once at upload
-    f16 *wpatch = nullptr, *bpatch = nullptr, *cls = nullptr, *pos = nullptr, *lnfg = nullptr, *lnfb = nullptr;
-    std::vector<PreLnLayer> layers;
     DConv reasm[4];                        // projection (folded with the transposed conv): [k k cp][D]
     DConv down;                            // reassemble layer 3's stride-2 3x3 conv [cp3][9][cp3]
     DConv neck[4];                         // neck.convs [F][9][cp]
     Fusion fus[4];
     DConv head1, head2, head3;
-    image_front_end::PlanCache plans;
 };
 
 namespace {
+
+const TowerNames NAMES = {"depth", "depth", "depth handle is NULL"};
 
 // stored channel count of reassembled map i: a multiple of 32 (the narrow conv's k step) whose GEMM width k k cp fits launch_igemm; map 3 is also the
 // stride-2 conv's input and output (Cin % 64, N % 128 or N % 160)
@@ -51,27 +47,9 @@ int padded_channels(int C, int k, bool conv_operand) {
 }
 
 void build_manifest(CsDepth* c) {          // transformers DepthAnythingForDepthEstimation.state_dict() order
-    WeightManifest& m = c->weights;
-    const int D = c->cfg.hidden_size, I = c->I, P = c->cfg.patch_size, g = c->cfg.image_size / P, F = c->F;
-    const std::string bb = "backbone.";
-    m.expect(bb + "embeddings.cls_token", {1, 1, D});
-    m.expect(bb + "embeddings.mask_token", {1, D});
-    m.expect(bb + "embeddings.position_embeddings", {1, (int64_t)g * g + 1, D});
-    m.expect(bb + "embeddings.patch_embeddings.projection.weight", {D, 3, P, P});
-    m.expect(bb + "embeddings.patch_embeddings.projection.bias", {D});
-    for (int l = 0; l < c->cfg.num_hidden_layers; ++l) {
-        const std::string p = bb + "encoder.layer." + std::to_string(l);
-        m.expect(p + ".norm1.weight", {D}); m.expect(p + ".norm1.bias", {D});
-        for (const char* q : {".attention.attention.query", ".attention.attention.key", ".attention.attention.value", ".attention.output.dense"}) {
-            m.expect(p + q + ".weight", {D, D}); m.expect(p + q + ".bias", {D});
-        }
-        m.expect(p + ".layer_scale1.lambda1", {D});
-        m.expect(p + ".norm2.weight", {D}); m.expect(p + ".norm2.bias", {D});
-        m.expect(p + ".mlp.fc1.weight", {I, D}); m.expect(p + ".mlp.fc1.bias", {I});
-        m.expect(p + ".mlp.fc2.weight", {D, I}); m.expect(p + ".mlp.fc2.bias", {D});
-        m.expect(p + ".layer_scale2.lambda1", {D});
-    }
-    m.expect(bb + "layernorm.weight", {D}); m.expect(bb + "layernorm.bias", {D});
+    WeightManifest& m = c->tower.weights;
+    const int D = c->tower.D, F = c->F;
+    image_tower::expect_dinov2_backbone(m, "backbone.", D, c->tower.I, c->tower.P, c->cfg.image_size / c->cfg.patch_size, c->cfg.num_hidden_layers);
     for (int i = 0; i < 4; ++i) {
         const std::string p = "neck.reassemble_stage.layers." + std::to_string(i);
         const int C = c->cfg.neck_hidden_sizes[i];
@@ -113,15 +91,16 @@ std::vector<float> pad_vector(const std::vector<float>& v, int n) {
 // stride-2 conv | the four neck features | three rotating buffers for the fusion stage and the head
 struct Layout { size_t pe, tap, gemm, map, down, f[4], x, y, z, total; };
 Layout layout(const CsDepth* c, size_t B) {
-    const size_t D = c->cfg.hidden_size, rows = B * c->T, F = c->F;
+    const ImageTower& t = c->tower;
+    const size_t D = t.D, rows = B * t.T, F = c->F, G = t.G;
     Layout L;
-    size_t o = pre_ln_workspace_elems(rows, D, c->I);
-    L.pe = o; o += B * c->NP * D;
+    L.pe = pre_ln_workspace_elems(rows, D, t.I);
+    size_t o = t.workspace_elems(B);          // ... with the patch embeddings
     L.tap = o; o += rows * D;
     size_t nmax = 0, mmax = 0;
     for (int i = 0; i < 4; ++i) {
         nmax = std::max(nmax, (size_t)RK[i] * RK[i] * c->cp[i]);
-        mmax = std::max(mmax, (size_t)c->G * RK[i] * c->G * RK[i] * c->cp[i]);
+        mmax = std::max(mmax, G * RK[i] * G * RK[i] * c->cp[i]);
     }
     L.gemm = o; o += rows * nmax;
     L.map = o; o += B * mmax;
@@ -133,86 +112,12 @@ Layout layout(const CsDepth* c, size_t B) {
     return L;
 }
 
-}  // namespace
-
-extern "C" {
-
-int cs_depth_create(const CsDepthConfig* cfg, CsDepth** out) {
-    if (!cfg || !out) CS_FAIL(CS_E_ARG, "cfg/out is NULL");
-    if (cfg->hidden_size < 128 || cfg->hidden_size % 128 || cfg->mlp_ratio < 1 || (cfg->hidden_size * cfg->mlp_ratio) % 128)
-        CS_FAIL(CS_E_SHAPE, "depth: hidden / MLP size must be multiples of 128");
-    if (cfg->num_attention_heads < 1 || cfg->hidden_size != cfg->num_attention_heads * 64) CS_FAIL(CS_E_UNSUPPORTED, "depth: built for heads of dim 64");
-    if (cfg->num_hidden_layers < 1 || cfg->patch_size < 1 || cfg->image_size < cfg->patch_size || cfg->image_size % cfg->patch_size) CS_FAIL(CS_E_ARG, "depth: bad config");
-    if (cfg->size != cfg->image_size) CS_FAIL(CS_E_UNSUPPORTED, "depth: the processor's size %d must equal image_size %d (the position table is not interpolated)",
-                                              cfg->size, cfg->image_size);
-    if (cfg->size > 2048) CS_FAIL(CS_E_SHAPE, "depth: size %d is larger than 2048", cfg->size);
-    for (int i = 0; i < 4; ++i) {
-        if (cfg->out_indices[i] < 1 || cfg->out_indices[i] > cfg->num_hidden_layers || (i && cfg->out_indices[i] <= cfg->out_indices[i - 1]))
-            CS_FAIL(CS_E_ARG, "depth: out_indices must increase within 1 .. num_hidden_layers");
-        if (cfg->neck_hidden_sizes[i] < 1 || cfg->neck_hidden_sizes[i] > 4096) CS_FAIL(CS_E_ARG, "depth: bad neck_hidden_sizes");
-        if (!(cfg->image_std[i % 3] > 0.f)) CS_FAIL(CS_E_ARG, "depth: image_std must be positive");
-    }
-    if (cfg->fusion_hidden_size != 64) CS_FAIL(CS_E_UNSUPPORTED, "depth: fusion_hidden_size %d (built for 64)", cfg->fusion_hidden_size);
-    if (cfg->head_hidden_size != 32 && cfg->head_hidden_size != 64) CS_FAIL(CS_E_UNSUPPORTED, "depth: head_hidden_size %d (built for 32 and 64)", cfg->head_hidden_size);
-    CsDepth* c = new CsDepth();
-    c->cfg = *cfg;
-    c->S = cfg->size; c->G = cfg->size / cfg->patch_size; c->NP = c->G * c->G; c->T = c->NP + 1;
-    c->K = 3 * cfg->patch_size * cfg->patch_size; c->Kpad = (c->K + 63) / 64 * 64; c->I = cfg->hidden_size * cfg->mlp_ratio;
-    c->F = cfg->fusion_hidden_size; c->HH = cfg->head_hidden_size;
-    c->g[0] = 4 * c->G; c->g[1] = 2 * c->G; c->g[2] = c->G; c->g[3] = (c->G - 1) / 2 + 1;
-    for (int i = 0; i < 4; ++i) c->cp[i] = padded_channels(cfg->neck_hidden_sizes[i], RK[i], i == 3);
-    build_manifest(c);
-    *out = c;
-    return CS_OK;
-}
-
-void cs_depth_destroy(CsDepth* c) {
-    if (!c) return;
-    c->weights.free_device();
-    c->plans.free_device();
-    delete c;
-}
-
-int cs_depth_num_weights(const CsDepth* c) { return c ? c->weights.count() : 0; }
-
-const char* cs_depth_weight_name(const CsDepth* c, int i, int64_t* shape4, int* ndim) { return c ? c->weights.name_at(i, shape4, 4, ndim) : nullptr; }
-
-int cs_depth_set_weight(CsDepth* c, const char* name, const float* data, const int64_t* shape, int ndim) {
-    if (!c) CS_FAIL(CS_E_ARG, "null argument");
-    return c->weights.set(name, data, shape, ndim);
-}
-
-int cs_depth_finalize(CsDepth* c) {
-    if (!c) CS_FAIL(CS_E_ARG, "null");
-    WeightStore<float>& W = c->weights;
-    if (W.finalized) return CS_OK;
-    if (const std::string* n = W.first_missing()) CS_FAIL(CS_E_STATE, "missing weight '%s'", n->c_str());
-    const std::string bb = "backbone.";
+// the backbone's layers up to the last tap (the ones behind it feed nothing), then the neck and the head with the folds of the header comment
+bool pack(CsDepth* c) {
+    WeightStore<float>& W = c->tower.weights;
     auto T = [&](const std::string& n) -> const std::vector<float>& { return W.at(n).data; };
-    const int D = c->cfg.hidden_size, K = c->K, Kpad = c->Kpad, F = c->F;
-    {   // patch projection [D][3 P P] -> [D][Kpad]
-        const auto& w = T(bb + "embeddings.patch_embeddings.projection.weight");
-        std::vector<float> wp((size_t)D * Kpad, 0.f);
-        for (int n = 0; n < D; ++n) std::copy(w.begin() + (size_t)n * K, w.begin() + (size_t)(n + 1) * K, wp.begin() + (size_t)n * Kpad);
-        c->wpatch = W.upload(wp); c->bpatch = W.upload(T(bb + "embeddings.patch_embeddings.projection.bias"));
-    }
-    {   // the position table as it is (the grid is the training grid); the class row pre-added to the CLS token in fp32
-        const auto& pos = T(bb + "embeddings.position_embeddings");
-        const auto& cls = T(bb + "embeddings.cls_token");
-        std::vector<float> cls0(D), table((size_t)c->T * D, 0.f);
-        for (int d = 0; d < D; ++d) cls0[d] = cls[d] + pos[d];
-        std::copy(pos.begin() + D, pos.end(), table.begin() + D);
-        c->cls = W.upload(cls0); c->pos = W.upload(table);
-    }
-    c->lnfg = W.upload(T(bb + "layernorm.weight")); c->lnfb = W.upload(T(bb + "layernorm.bias"));
-    bool ok = c->wpatch && c->bpatch && c->cls && c->pos && c->lnfg && c->lnfb;
-    c->layers.resize(c->cfg.out_indices[3]);                    // the layers behind the last tap feed nothing
-    for (size_t l = 0; l < c->layers.size() && ok; ++l) {
-        const std::string p = bb + "encoder.layer." + std::to_string(l);
-        ok = pack_pre_ln_layer<float>(W, {p + ".attention.attention.query", p + ".attention.attention.key", p + ".attention.attention.value", p + ".attention.output.dense",
-                                          p + ".norm1", p + ".norm2", p + ".mlp.fc1", p + ".mlp.fc2"},
-                                      &W.at(p + ".layer_scale1.lambda1").data, &W.at(p + ".layer_scale2.lambda1").data, c->layers[l]);
-    }
+    const int D = c->tower.D, F = c->F;
+    bool ok = image_tower::pack_dinov2_backbone(c->tower, "backbone.", c->cfg.image_size / c->cfg.patch_size, c->cfg.out_indices[3]);
     for (int i = 0; i < 4 && ok; ++i) {
         // reassemble layer i as one linear map: row (ky k + kx) cp + co of the GEMM = sum_ci resize[ci][co][ky][kx] projection[ci][:] (k = 1: the projection itself)
         const std::string p = "neck.reassemble_stage.layers." + std::to_string(i);
@@ -262,14 +167,61 @@ int cs_depth_finalize(CsDepth* c) {
         if (ok && i) ok = conv(p + ".residual_layer1.convolution1", F, F, f.r1c1) && conv(p + ".residual_layer1.convolution2", F, F, f.r1c2);
     }
     if (ok) ok = conv("head.conv1", F / 2, F, c->head1) && conv("head.conv2", c->HH, F / 2, c->head2) && conv("head.conv3", 1, c->HH, c->head3);
-    if (!ok) CS_FAIL(CS_E_HIP, "depth: weight upload failed (hipMalloc/hipMemcpy)");
-    W.release_host();
-    W.finalized = true;
+    return ok;
+}
+
+}  // namespace
+
+extern "C" {
+
+int cs_depth_create(const CsDepthConfig* cfg, CsDepth** out) {
+    if (!cfg || !out) CS_FAIL(CS_E_ARG, "cfg/out is NULL");
+    const int mlp = cfg->mlp_ratio < 1 ? 0 : cfg->hidden_size * cfg->mlp_ratio;
+    int rc = image_tower::check_encoder_config(NAMES.who, "hidden / MLP size", 0, cfg->hidden_size, mlp, cfg->num_attention_heads, cfg->num_hidden_layers, cfg->patch_size,
+                                               cfg->image_size);
+    if (rc != CS_OK) return rc;
+    if (cfg->size != cfg->image_size) CS_FAIL(CS_E_UNSUPPORTED, "depth: the processor's size %d must equal image_size %d (the position table is not interpolated)",
+                                              cfg->size, cfg->image_size);
+    if (cfg->size > 2048) CS_FAIL(CS_E_SHAPE, "depth: size %d is larger than 2048", cfg->size);
+    if ((rc = image_tower::check_image_std(NAMES.who, cfg->image_std)) != CS_OK) return rc;
+    for (int i = 0; i < 4; ++i) {
+        if (cfg->out_indices[i] < 1 || cfg->out_indices[i] > cfg->num_hidden_layers || (i && cfg->out_indices[i] <= cfg->out_indices[i - 1]))
+            CS_FAIL(CS_E_ARG, "depth: out_indices must increase within 1 .. num_hidden_layers");
+        if (cfg->neck_hidden_sizes[i] < 1 || cfg->neck_hidden_sizes[i] > 4096) CS_FAIL(CS_E_ARG, "depth: bad neck_hidden_sizes");
+    }
+    if (cfg->fusion_hidden_size != 64) CS_FAIL(CS_E_UNSUPPORTED, "depth: fusion_hidden_size %d (built for 64)", cfg->fusion_hidden_size);
+    if (cfg->head_hidden_size != 32 && cfg->head_hidden_size != 64) CS_FAIL(CS_E_UNSUPPORTED, "depth: head_hidden_size %d (built for 32 and 64)", cfg->head_hidden_size);
+    CsDepth* c = new CsDepth();
+    c->cfg = *cfg;
+    c->tower.init(cfg->hidden_size, mlp, cfg->num_attention_heads, cfg->layer_norm_eps, cfg->patch_size, cfg->size, cfg->size, cfg->image_mean, cfg->image_std,
+                  cfg->rescale_factor);
+    c->S = cfg->size; c->F = cfg->fusion_hidden_size; c->HH = cfg->head_hidden_size;
+    const int G = c->tower.G;
+    c->g[0] = 4 * G; c->g[1] = 2 * G; c->g[2] = G; c->g[3] = (G - 1) / 2 + 1;
+    for (int i = 0; i < 4; ++i) c->cp[i] = padded_channels(cfg->neck_hidden_sizes[i], RK[i], i == 3);
+    build_manifest(c);
+    *out = c;
     return CS_OK;
 }
 
-int cs_depth_patch_cols(const CsDepth* c) { return c ? c->Kpad : 0; }
-int cs_depth_num_tokens(const CsDepth* c) { return c ? c->T : 0; }
+void cs_depth_destroy(CsDepth* c) {
+    if (!c) return;
+    c->tower.free_device();
+    delete c;
+}
+
+int cs_depth_num_weights(const CsDepth* c) { return c ? c->tower.weights.count() : 0; }
+
+const char* cs_depth_weight_name(const CsDepth* c, int i, int64_t* shape4, int* ndim) { return c ? c->tower.weights.name_at(i, shape4, 4, ndim) : nullptr; }
+
+int cs_depth_set_weight(CsDepth* c, const char* name, const float* data, const int64_t* shape, int ndim) {
+    return image_tower::set_weight(tower_of(c), name, data, shape, ndim);
+}
+
+int cs_depth_finalize(CsDepth* c) { return image_tower::finalize(NAMES, tower_of(c), [&] { return pack(c); }); }
+
+int cs_depth_patch_cols(const CsDepth* c) { return c ? c->tower.Kpad : 0; }
+int cs_depth_num_tokens(const CsDepth* c) { return c ? c->tower.T : 0; }
 
 size_t cs_depth_workspace_bytes(const CsDepth* c, int batch) {
     if (!c || batch <= 0) return 0;
@@ -278,11 +230,11 @@ size_t cs_depth_workspace_bytes(const CsDepth* c, int batch) {
 
 double cs_depth_flops(const CsDepth* c, int batch) {
     if (!c) return 0;
-    const double D = c->cfg.hidden_size, F = c->F, B = batch;
-    double f = 2.0 * B * c->NP * (double)c->K * D + pre_ln_flops(c->cfg.out_indices[3], batch, c->T, D, c->I);
+    const double D = c->tower.D, F = c->F, B = batch;
+    double f = c->tower.flops(c->cfg.out_indices[3], batch);
     for (int i = 0; i < 4; ++i) {
         const double px = (double)c->g[i] * c->g[i];
-        f += 2.0 * B * c->T * D * RK[i] * RK[i] * c->cp[i];                                   // reassemble GEMM
+        f += 2.0 * B * c->tower.T * D * RK[i] * RK[i] * c->cp[i];                                   // reassemble GEMM
         f += 2.0 * B * px * 9 * c->cp[i] * F;                                                 // neck conv
         const int lvl = 3 - i;                                                                // fusion layer `lvl` runs at this map's size
         const double nxt = i ? (double)c->g[i - 1] * c->g[i - 1] : 4.0 * px;
@@ -294,37 +246,24 @@ double cs_depth_flops(const CsDepth* c, int batch) {
 }
 
 size_t cs_depth_preprocess_workspace_bytes(const CsDepth* c, int batch, int height, int width) {
-    if (!c || batch <= 0 || height <= 0 || width <= 0) return 0;
-    return (size_t)batch * 3 * height * c->S + 256;          // the horizontal pass's rows (at most every input row) x size columns, uint8
+    return image_tower::preprocess_workspace_bytes(tower_of(c), batch, height, width);
 }
 
 int cs_depth_preprocess(CsDepth* c, const void* images, int dtype, int batch, int height, int width, void* patches, unsigned char* crop_u8,
                         void* workspace, size_t workspace_bytes, void* stream) {
-    if (!c) CS_FAIL(CS_E_ARG, "depth handle is NULL");
-    if (batch < 0) CS_FAIL(CS_E_ARG, "negative size");
-    if (height != width) CS_FAIL(CS_E_UNSUPPORTED, "depth: %d x %d image: only square inputs are built (the processor's keep_aspect_ratio rule then gives %d x %d)",
-                                 height, width, c->S, c->S);
-    if (batch == 0) return CS_OK;
-    if (!images || !patches || !workspace) CS_FAIL(CS_E_ARG, "null pointer");
-    const image_front_end::Plan* pl = nullptr;
-    const int rc = c->plans.get_plan("depth", c->S, c->S, height, width, &pl);          // shortest edge = crop = size: the whole image, no crop
-    if (rc != CS_OK) return rc;
-    if (workspace_bytes < (size_t)batch * 3 * pl->dev.nrows * c->S) CS_FAIL(CS_E_ARG, "depth: preprocess workspace too small");
-    return launch_vit_front_end(images, dtype, batch, height, width, pl->dev, c->cfg.image_mean, c->cfg.image_std, c->cfg.rescale_factor,
-                                c->cfg.patch_size, c->G, c->Kpad, (unsigned char*)workspace, (f16*)patches, crop_u8, (hipStream_t)stream);
+    if (c && batch >= 0 && height != width)          // (behind the null-handle and negative-size refusals, in front of the empty batch's return)
+        CS_FAIL(CS_E_UNSUPPORTED, "depth: %d x %d image: only square inputs are built (the processor's keep_aspect_ratio rule then gives %d x %d)", height, width, c->S, c->S);
+    return image_tower::preprocess(NAMES, tower_of(c), images, dtype, batch, height, width, patches, crop_u8, workspace, workspace_bytes, stream);
 }
 
 int cs_depth_forward(CsDepth* c, const void* patches, int batch, float* predicted_depth, void* workspace, size_t workspace_bytes, void* stream) {
-    if (!c) CS_FAIL(CS_E_ARG, "depth handle is NULL");
-    if (!c->weights.finalized) CS_FAIL(CS_E_STATE, "cs_depth_finalize has not been called");
-    if (batch < 0) CS_FAIL(CS_E_ARG, "negative size");
-    if (batch == 0) return CS_OK;
-    if (!patches || !predicted_depth || !workspace) CS_FAIL(CS_E_ARG, "null pointer");
-    if (workspace_bytes < cs_depth_workspace_bytes(c, batch)) CS_FAIL(CS_E_ARG, "depth: workspace too small");
-    const int D = c->cfg.hidden_size, I = c->I, H = c->cfg.num_attention_heads, Tn = c->T, F = c->F, B = batch, G = c->G;
+    bool run = false;
+    int rc = image_tower::begin_forward(NAMES, tower_of(c), batch, patches && predicted_depth && workspace, workspace_bytes, cs_depth_workspace_bytes(c, batch), &run);
+    if (!run) return rc;
+    const ImageTower& t = c->tower;
+    const int D = t.D, I = t.I, H = t.heads, Tn = t.T, F = c->F, B = batch, G = t.G;
     const Layout L = layout(c, (size_t)B);
-    if ((long)B * Tn > 0x7fffffffL / std::max(std::max(I, 3 * D), 16 * c->cp[0]) || (long)B * c->S * c->S > 0x7fffffffL / 64)
-        CS_FAIL(CS_E_SHAPE, "depth: batch too large for one call");
+    if (t.too_many_rows(B, 16 * c->cp[0]) || (long)B * c->S * c->S > 0x7fffffffL / 64) CS_FAIL(CS_E_SHAPE, "depth: batch too large for one call");
     hipStream_t s = (hipStream_t)stream;
     const long rows = (long)B * Tn;
     const PreLnWorkspace w = carve_pre_ln(workspace, rows, D, I);
@@ -345,14 +284,13 @@ int cs_depth_forward(CsDepth* c, const void* patches, int batch, float* predicte
     };
 
     // ---- backbone, tapped after out_indices[i] layers: final LayerNorm -> reassemble layer i -> neck conv i ----
-    int rc = linear((const f16*)patches, B * c->NP, c->Kpad, c->wpatch, c->bpatch, D, nullptr, pe, s);
-    if (rc == CS_OK) rc = launch_vit_tokens(pe, c->cls, c->pos, w.x, B, c->NP, D, s);
+    rc = image_tower::embed_patches(t, patches, B, pe, w.x, s);
     size_t done = 0;
     for (int i = 0; i < 4 && rc == CS_OK; ++i) {
         const int k = RK[i], cp = c->cp[i];
-        rc = run_pre_ln_layers(c->layers, w, B, Tn, D, I, H, c->cfg.layer_norm_eps, 0, launch_gelu_erf, s, done, (size_t)c->cfg.out_indices[i]);
+        rc = run_pre_ln_layers(t.layers, w, B, Tn, D, I, H, t.eps, 0, launch_gelu_erf, s, done, (size_t)c->cfg.out_indices[i]);
         done = (size_t)c->cfg.out_indices[i];
-        if (rc == CS_OK) rc = launch_layer_norm(w.x, c->lnfg, c->lnfb, tap, (int)rows, D, c->cfg.layer_norm_eps, s);
+        if (rc == CS_OK) rc = launch_layer_norm(w.x, t.lnfg, t.lnfb, tap, (int)rows, D, t.eps, s);
         if (rc == CS_OK) rc = linear(tap, (int)rows, D, c->reasm[i].w, c->reasm[i].b, k * k * cp, nullptr, gemm, s);
         if (rc == CS_OK) rc = launch_dpt_pixel_shuffle(gemm, B, G, k, cp, 1, map, s);               // drops the CLS rows
         const f16* src = map;

@@ -1,5 +1,5 @@
-// The resize plans of the image front end (launch_vit_front_end), shared by the executors whose processor is "PIL bicubic resize to a shortest edge,
-// center crop, rescale, normalise" (vit.cpp: DINOv2; clip_vision.cpp: CLIP).  Host only: PIL's tap tables for the crop window of one (height, width),
+// The resize plans of the image front end (launch_vit_front_end), used through image_tower.h by the executors whose processor is "PIL bicubic resize to a
+// shortest edge, center crop, rescale, normalise" (vit.cpp: DINOv2; clip_vision.cpp: CLIP; depth.cpp: Depth Anything, edge = crop = size).  Host only: PIL's tap tables for the crop window of one (height, width),
 // built in double as ImagingResample does, uploaded once per size and kept in a bounded cache that the handle owns.
 #pragma once
 #include "ops.h"

@@ -60,20 +60,18 @@ def depth_psnr_tail(pred_depth, target_depth):
     return _psnr(pred_depth, target_depth, 0.0)
 
 
+# reward types computed by a model of reward_model.py -> its function there
+_MODEL_REWARDS = {"dino": "calculate_dino_reward", "clip": "calculate_clip_reward", "depth": "calculate_depth_reward"}
+
+
 def calculate_reward(reward_type, reward_model, reward_model_processor, model_pred, target, device=None):
     """edit_ppo/reward_model.py:138-161.  decode_latents already maps to [0, 1], so the clamp at :141-142 is a no-op here (the "dino" / "clip"
     front end clamps to [0, 1] unconditionally)."""
     if reward_type == "image_psnr":
         return calculate_image_psnr_reward(reward_model_processor, model_pred, target, device)
-    if reward_type == "dino":
-        from .reward_model import calculate_dino_reward
-        return calculate_dino_reward(reward_model, reward_model_processor, model_pred, target, device)
-    if reward_type == "clip":
-        from .reward_model import calculate_clip_reward
-        return calculate_clip_reward(reward_model, reward_model_processor, model_pred, target, device)
-    if reward_type == "depth":
-        from .reward_model import calculate_depth_reward
-        return calculate_depth_reward(reward_model, reward_model_processor, model_pred, target, device)
+    if reward_type in _MODEL_REWARDS:
+        from . import reward_model as rm          # lazy: the model rewards are not needed for image_psnr
+        return getattr(rm, _MODEL_REWARDS[reward_type])(reward_model, reward_model_processor, model_pred, target, device)
     if reward_type in ("inception", "segmentation", "llava", "qwen_vl"):
         raise NotImplementedError(f"reward_type '{reward_type}' needs a third-party backbone network (out of scope, SURVEY 8 a21)")
     raise ValueError(f"Unknown reward_type: {reward_type}")

@@ -68,9 +68,9 @@ class _VitOutput(tuple):
     pooler_output = property(lambda self: self[1])
 
 
-class _HipImageEncoder:
-    """What the two image-reward models share: a handle of the C ABI family ``cs_<_prefix>_*`` (create / weights / preprocess / forward), the front end,
-    and the chunked encoder call.  Subclasses create the handle from their config struct and name the width of the features (``_feature_dim``)."""
+class _HipImageModel:
+    """What the image-reward models share (csrc/image_tower.h on the C side): a handle of the C ABI family ``cs_<_prefix>_*`` (create / weights / preprocess /
+    forward), the front end, and the chunked forward call.  Subclasses create the handle from their config struct."""
     is_consolver_hip = True
     dtype = torch.float16
     max_batch = 64             # images per encoder call (bounds the workspace)
@@ -157,15 +157,15 @@ class _HipImageEncoder:
         out[:, :3 * P * P] = rows
         return out
 
-    # ---- encoder --------------------------------------------------------------------------------------------------
-    def encode_patches(self, patches):
-        """patch rows -> features [B, _feature_dim] fp32 (dino: ``last_hidden_state[:, 0]`` after the final LayerNorm; clip: ``image_embeds``)"""
+    # ---- model --------------------------------------------------------------------------------------------------
+    def _forward(self, patches, *out_shape):
+        """patch rows -> cs_<_prefix>_forward's fp32 output [B, *out_shape], ``max_batch`` images per call"""
         if not self._finalized:
             raise RuntimeError("weights not loaded")
         L.require_cuda(patches, "patches")
         g = self.crop // self.patch
         B = patches.shape[0] // (g * g)
-        out = torch.empty(B, self._feature_dim, dtype=torch.float32, device=patches.device)
+        out = torch.empty(B, *out_shape, dtype=torch.float32, device=patches.device)
         for s in range(0, B, self.max_batch):
             n = min(self.max_batch, B - s)
             need = int(self._fn("workspace_bytes")(self._h, n))
@@ -174,6 +174,14 @@ class _HipImageEncoder:
             L.check(self._fn("forward")(self._h, L.ptr(patches[s * g * g:]), n, L.ptr(out[s:]), L.ptr(self._ws), self._ws.numel(),
                                         L.stream_ptr(patches.device)))
         return out
+
+
+class _HipImageEncoder(_HipImageModel):
+    """The models whose forward gives one feature vector per image; subclasses name its width (``_feature_dim``)."""
+
+    def encode_patches(self, patches):
+        """patch rows -> features [B, _feature_dim] fp32 (dino: ``last_hidden_state[:, 0]`` after the final LayerNorm; clip: ``image_embeds``)"""
+        return self._forward(patches, self._feature_dim)
 
     def image_features(self, images):
         """[B,3,H,W] in [0,1] -> features [B, _feature_dim] fp32: the whole per-image path of the reward up to F.normalize"""
@@ -272,7 +280,7 @@ class _DepthOutput(tuple):
     predicted_depth = property(lambda self: self[0])
 
 
-class HipDepthAnythingModel(_HipImageEncoder):
+class HipDepthAnythingModel(_HipImageModel):
     """``transformers.DepthAnythingForDepthEstimation`` (default: the V2-Small shape).  ``model(pixel_values=...).predicted_depth`` is the call the reference
     makes; ``predicted_depth(images)`` and ``normalized_depth(images)`` run the processor's arithmetic and the post-processing on the GPU as well."""
     workspace_budget = 600 << 20          # bytes of workspace one call may take: max_batch is sized from it (V2-Small: 72.7 MB per image -> 8 images per call)
@@ -291,24 +299,11 @@ class HipDepthAnythingModel(_HipImageEncoder):
         h = C.c_void_p()
         L.check(L.lib().cs_depth_create(C.byref(c), C.byref(h)))
         self._init_handle(h, size, cfg["patch_size"])
-        self.max_batch = max(1, min(_HipImageEncoder.max_batch, self.workspace_budget // int(self._fn("workspace_bytes")(h, 1))))
+        self.max_batch = max(1, min(_HipImageModel.max_batch, self.workspace_budget // int(self._fn("workspace_bytes")(h, 1))))
 
     def depth_from_patches(self, patches):
         """patch rows -> ``predicted_depth`` [B, size, size] fp32, ``max_batch`` images per call"""
-        if not self._finalized:
-            raise RuntimeError("weights not loaded")
-        L.require_cuda(patches, "patches")
-        g = self.crop // self.patch
-        B = patches.shape[0] // (g * g)
-        out = torch.empty(B, self.crop, self.crop, dtype=torch.float32, device=patches.device)
-        for s in range(0, B, self.max_batch):
-            n = min(self.max_batch, B - s)
-            need = int(self._fn("workspace_bytes")(self._h, n))
-            if self._ws is None or self._ws.numel() < need or self._ws.device != patches.device:
-                self._ws = torch.empty(need, dtype=torch.uint8, device=patches.device)
-            L.check(self._fn("forward")(self._h, L.ptr(patches[s * g * g:]), n, L.ptr(out[s:]), L.ptr(self._ws), self._ws.numel(),
-                                        L.stream_ptr(patches.device)))
-        return out
+        return self._forward(patches, self.crop, self.crop)
 
     @torch.no_grad()
     def __call__(self, pixel_values=None, **_ignored):
@@ -389,9 +384,9 @@ def cosine_reward(pred_features, target_features):
     return out
 
 
-def _feature_cosine_reward(reward_model, reward_model_processor, model_pred, target):
-    """the part the image-similarity rewards share: processor check, one front-end and one encoder pass for the 2 B images (a [1,3,H,W] target is
-    encoded once), the cosine tail"""
+def _paired_image_pass(reward_model, reward_model_processor, model_pred, target, per_image):
+    """the part the model rewards share: processor check, argument checks, and ``per_image`` ([n,3,H,W] -> [n, ...]) in one pass over the 2 B images
+    (a [1,3,H,W] target shared by the batch, or one of another dtype, goes through on its own) -> (of model_pred [B, ...], of target [B or 1, ...])"""
     if reward_model_processor is not None and reward_model_processor.constants() != reward_model.processor.constants():
         raise ValueError("the processor's constants differ from the ones the model's front end was built with")
     L.require_cuda(model_pred, "model_pred")
@@ -400,9 +395,14 @@ def _feature_cosine_reward(reward_model, reward_model_processor, model_pred, tar
     if target.shape[0] not in (B, 1) or target.shape[1:] != model_pred.shape[1:]:
         raise ValueError(f"shape mismatch {tuple(model_pred.shape)} vs {tuple(target.shape)}")
     if target.dtype != model_pred.dtype or target.shape[0] != B:
-        return cosine_reward(reward_model.image_features(model_pred), reward_model.image_features(target))
-    feats = reward_model.image_features(torch.cat([model_pred, target]))            # one front-end and one encoder pass for the 2 B images
-    return cosine_reward(feats[:B], feats[B:])
+        return per_image(model_pred), per_image(target)
+    out = per_image(torch.cat([model_pred, target]))            # one front-end and one model pass for the 2 B images
+    return out[:B], out[B:]
+
+
+def _feature_cosine_reward(reward_model, reward_model_processor, model_pred, target):
+    """the image-similarity rewards: the features of pred and target (a [1,3,H,W] target is encoded once), the cosine tail"""
+    return cosine_reward(*_paired_image_pass(reward_model, reward_model_processor, model_pred, target, reward_model.image_features))
 
 
 def calculate_dino_reward(reward_model, reward_model_processor, model_pred, target, device=None):
@@ -430,19 +430,8 @@ def calculate_depth_reward(reward_model, reward_model_processor, model_pred, tar
     if not isinstance(reward_model, HipDepthAnythingModel):
         raise NotImplementedError("reward_type 'depth' needs a HipDepthAnythingModel (load_depth_reward(device, config)); the eager transformers path is "
                                   "not implemented")
-    if reward_model_processor is not None and reward_model_processor.constants() != reward_model.processor.constants():
-        raise ValueError("the processor's constants differ from the ones the model's front end was built with")
-    L.require_cuda(model_pred, "model_pred")
-    L.require_cuda(target, "target")
-    B = model_pred.shape[0]
-    if target.shape[0] not in (B, 1) or target.shape[1:] != model_pred.shape[1:]:
-        raise ValueError(f"shape mismatch {tuple(model_pred.shape)} vs {tuple(target.shape)}")
-    if target.dtype != model_pred.dtype or target.shape[0] != B:
-        pred_maps, target_maps = reward_model.normalized_depth(model_pred), reward_model.normalized_depth(target)
-        if target_maps.shape[0] != B:
-            target_maps = target_maps.expand(B, -1, -1)
-    else:
-        maps = reward_model.normalized_depth(torch.cat([model_pred, target]))            # one pass for the 2 B images
-        pred_maps, target_maps = maps[:B], maps[B:]
+    pred_maps, target_maps = _paired_image_pass(reward_model, reward_model_processor, model_pred, target, reward_model.normalized_depth)
+    if target_maps.shape[0] != pred_maps.shape[0]:
+        target_maps = target_maps.expand(pred_maps.shape[0], -1, -1)
     from .ppo import depth_psnr_tail
     return depth_psnr_tail(pred_maps, target_maps)

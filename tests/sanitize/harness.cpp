@@ -1,10 +1,10 @@
 // Sanitizer harness for the HOST side of libconsolver_hip (the reference has no sanitizer story; this is ours).
-// Built by tests/test_sanitize_host.py with -fsanitize=address,undefined -fno-gpu-sanitize from the real unet.cpp / vae.cpp / flux.cpp / clip.cpp / vit.cpp / ops_api.cpp /
+// Built by tests/test_sanitize_host.py with -fsanitize=address,undefined -fno-gpu-sanitize from the real unet.cpp / vae.cpp / flux.cpp / clip.cpp / vit.cpp / clip_vision.cpp / depth.cpp / ops_api.cpp /
 // api.cpp (and through them weights.h, the weight store of every handle, and encoder.h, the CLIP / ViT layer loop) plus tests/sanitize/stubs.cpp (host malloc as
 // device memory, launch stubs that touch every tensor's first and last byte).  Drives, without a GPU:
 //   weight registration and repacking, finalize, the dry-run workspace sizing (every execution variant, both residual-stream modes), forwards through the
 //   first-fit arena with a workspace of EXACTLY the size the library asked for, the profiling event pool, and the error paths;
-//   the CLIP and ViT handles at their smallest legal shapes; a finalize with one weight missing on each of the five handles.
+//   the CLIP, ViT, CLIP vision and Depth Anything handles at their smallest legal shapes; a finalize with one weight missing on each of the seven handles.
 #include "../../include/consolver_hip.h"
 #include "../../include/consolver_hip_ops.h"
 #include <cstdio>
@@ -39,7 +39,8 @@ static CsFluxConfig flux_config() {
     c.guidance_embeds = 1; c.axes_dims_rope[0] = 16; c.axes_dims_rope[1] = 56; c.axes_dims_rope[2] = 56; c.dtype = CS_BF16;
     return c;
 }
-// CLIP and ViT at the smallest shapes their create accepts: hidden 128 = 2 heads of 64, 2 layers, MLP width 128
+// CLIP and ViT at the smallest shapes their create accepts: hidden 128 = 2 heads of 64, 2 layers, MLP width 128 (ViT: a 3 x 3 training grid, so the position
+// table is interpolated to the crop's 2 x 2)
 static CsClipConfig clip_config() {
     CsClipConfig c{};
     c.vocab_size = 50; c.hidden_size = 128; c.intermediate_size = 128; c.num_hidden_layers = 2; c.num_attention_heads = 2; c.max_position_embeddings = 8; c.layer_norm_eps = 1e-5f;
@@ -47,8 +48,27 @@ static CsClipConfig clip_config() {
 }
 static CsVitConfig vit_config() {
     CsVitConfig c{};
-    c.hidden_size = 128; c.num_hidden_layers = 2; c.num_attention_heads = 2; c.mlp_ratio = 1; c.image_size = 28; c.patch_size = 14; c.layer_norm_eps = 1e-6f;
+    c.hidden_size = 128; c.num_hidden_layers = 2; c.num_attention_heads = 2; c.mlp_ratio = 1; c.image_size = 42; c.patch_size = 14; c.layer_norm_eps = 1e-6f;
     c.resize_shortest_edge = 28; c.crop_size = 28; c.rescale_factor = 1.0 / 255;
+    for (int i = 0; i < 3; ++i) { c.image_mean[i] = 0.5f; c.image_std[i] = 0.25f; }
+    return c;
+}
+// the CLIP vision tower at its smallest shapes, with a projection width that is no multiple of anything
+static CsClipVisionConfig clipv_config() {
+    CsClipVisionConfig c{};
+    c.hidden_size = 128; c.intermediate_size = 128; c.num_hidden_layers = 2; c.num_attention_heads = 2; c.image_size = 28; c.patch_size = 14; c.projection_dim = 24;
+    c.layer_norm_eps = 1e-5f; c.resize_shortest_edge = 28; c.crop_size = 28; c.rescale_factor = 1.0 / 255;
+    for (int i = 0; i < 3; ++i) { c.image_mean[i] = 0.5f; c.image_std[i] = 0.25f; }
+    return c;
+}
+// Depth Anything at the smallest shapes that take every branch: an odd patch grid (G = 5: the stride-2 map is (G - 1) / 2 + 1 = 3, not G / 2), a tap after every
+// layer, neck widths that are padded (48 -> 64, 192 -> 256) and ones that are not
+static CsDepthConfig depth_config() {
+    CsDepthConfig c{};
+    c.hidden_size = 128; c.num_hidden_layers = 4; c.num_attention_heads = 2; c.mlp_ratio = 1; c.image_size = 70; c.patch_size = 14; c.layer_norm_eps = 1e-6f;
+    const int nh[4] = {48, 96, 192, 384};
+    for (int i = 0; i < 4; ++i) { c.out_indices[i] = i + 1; c.neck_hidden_sizes[i] = nh[i]; }
+    c.fusion_hidden_size = 64; c.head_hidden_size = 32; c.max_depth = 1.f; c.size = 70; c.rescale_factor = 1.0 / 255;
     for (int i = 0; i < 3; ++i) { c.image_mean[i] = 0.5f; c.image_std[i] = 0.25f; }
     return c;
 }
@@ -360,6 +380,104 @@ static void vit_part() {
     cs_vit_destroy(nullptr);
 }
 
+static void clipv_part() {
+    const CsClipVisionConfig c = clipv_config();
+    CsClipVision* h = nullptr;
+    CsClipVisionConfig bad = c; bad.crop_size = 14;
+    EXPECT(cs_clipv_create(&bad, &h) == CS_E_UNSUPPORTED && cs_clipv_create(nullptr, &h) != CS_OK);
+    EXPECT(cs_clipv_create(&c, &h) == CS_OK);
+    if (!h) return;
+    const int B = 2, NP = 4, Kpad = cs_clipv_patch_cols(h);
+    EXPECT(Kpad == 640 && cs_clipv_num_tokens(h) == NP + 1);
+    const size_t wsb = cs_clipv_workspace_bytes(h, B);
+    char* ws = (char*)malloc(wsb);
+    std::vector<char> patches((size_t)B * NP * Kpad * 2);
+    std::vector<float> embeds((size_t)B * c.projection_dim);
+    EXPECT(cs_clipv_forward(h, patches.data(), B, embeds.data(), ws, wsb, nullptr) == CS_E_STATE);       // not finalized
+    EXPECT(cs_clipv_set_weight(nullptr, "x", nullptr, nullptr, 0) == CS_E_ARG);
+    load_all_weights(cs_clipv_num_weights(h), [&](int i, int64_t* sh, int* nd) { return cs_clipv_weight_name(h, i, sh, nd); },
+                     [&](const char* n, const float* d, const int64_t* sh, int nd) { return cs_clipv_set_weight(h, n, d, sh, nd); }, [&] { return cs_clipv_finalize(h); });
+    EXPECT(wsb > 0 && cs_clipv_workspace_bytes(h, B) == wsb && cs_clipv_flops(h, B) > 0);
+    {   // the front end on an image that is resized and cropped, its workspace exactly what the library asked for
+        const int H = 40, W = 56;
+        const size_t pwb = cs_clipv_preprocess_workspace_bytes(h, B, H, W);
+        char* pws = (char*)malloc(pwb);
+        std::vector<float> img((size_t)B * 3 * H * W, 0.5f);
+        std::vector<unsigned char> crop((size_t)B * 3 * c.crop_size * c.crop_size);
+        EXPECT(pwb > 0 && cs_clipv_preprocess(h, img.data(), CS_F32, B, H, W, patches.data(), crop.data(), pws, pwb, nullptr) == CS_OK);
+        EXPECT(cs_clipv_preprocess(h, img.data(), CS_F32, B, 14, 14 * 3, patches.data(), nullptr, pws, pwb, nullptr) == CS_OK);      // a second size: a second table
+        EXPECT(cs_clipv_preprocess(h, img.data(), CS_F32, B, H, W, patches.data(), nullptr, pws, 16, nullptr) != CS_OK);
+        EXPECT(cs_clipv_preprocess(h, nullptr, CS_F32, B, H, W, patches.data(), nullptr, pws, pwb, nullptr) == CS_E_ARG);
+        EXPECT(cs_clipv_preprocess(h, nullptr, CS_F32, 0, H, W, nullptr, nullptr, nullptr, 0, nullptr) == CS_OK);                   // empty batch: no-op
+        free(pws);
+    }
+    EXPECT(cs_clipv_forward(h, patches.data(), B, embeds.data(), ws, wsb, nullptr) == CS_OK);
+    EXPECT(cs_clipv_forward(h, patches.data(), B, embeds.data(), ws, wsb - 1, nullptr) != CS_OK);
+    EXPECT(cs_clipv_forward(h, nullptr, B, embeds.data(), ws, wsb, nullptr) != CS_OK);
+    EXPECT(cs_clipv_forward(h, patches.data(), B, nullptr, ws, wsb, nullptr) != CS_OK && cs_clipv_forward(h, patches.data(), B, embeds.data(), nullptr, wsb, nullptr) != CS_OK);
+    EXPECT(cs_clipv_forward(nullptr, patches.data(), B, embeds.data(), ws, wsb, nullptr) == CS_E_ARG && cs_clipv_forward(h, patches.data(), -1, embeds.data(), ws, wsb, nullptr) == CS_E_ARG);
+    EXPECT(cs_clipv_forward(h, patches.data(), 0, embeds.data(), ws, wsb, nullptr) == CS_OK);            // empty batch: no-op
+    free(ws);
+    cs_clipv_destroy(h);
+    cs_clipv_destroy(nullptr);
+}
+
+static void depth_part() {
+    const CsDepthConfig c = depth_config();
+    CsDepth* h = nullptr;
+    CsDepthConfig bad = c; bad.out_indices[2] = 2;
+    EXPECT(cs_depth_create(&bad, &h) == CS_E_ARG && cs_depth_create(nullptr, &h) != CS_OK);
+    bad = c; bad.size = 84;
+    EXPECT(cs_depth_create(&bad, &h) == CS_E_UNSUPPORTED);
+    EXPECT(cs_depth_create(&c, &h) == CS_OK);
+    if (!h) return;
+    const int B = 2, S = c.size, NP = 25, Kpad = cs_depth_patch_cols(h);
+    EXPECT(Kpad == 640 && cs_depth_num_tokens(h) == NP + 1);
+    const size_t wsb = cs_depth_workspace_bytes(h, B);
+    char* ws = (char*)malloc(wsb);
+    std::vector<char> patches((size_t)B * NP * Kpad * 2);
+    std::vector<float> depth((size_t)B * S * S);
+    EXPECT(cs_depth_forward(h, patches.data(), B, depth.data(), ws, wsb, nullptr) == CS_E_STATE);        // not finalized
+    EXPECT(cs_depth_set_weight(nullptr, "x", nullptr, nullptr, 0) == CS_E_ARG);
+    load_all_weights(cs_depth_num_weights(h), [&](int i, int64_t* sh, int* nd) { return cs_depth_weight_name(h, i, sh, nd); },
+                     [&](const char* n, const float* d, const int64_t* sh, int nd) { return cs_depth_set_weight(h, n, d, sh, nd); }, [&] { return cs_depth_finalize(h); });
+    EXPECT(wsb > 0 && cs_depth_workspace_bytes(h, B) == wsb && cs_depth_flops(h, B) > 0);
+    {   // the front end on a square image that is resized (up, then down), its workspace exactly what the library asked for; other shapes are refused
+        const int H = 40;
+        const size_t pwb = cs_depth_preprocess_workspace_bytes(h, B, H, H);
+        char* pws = (char*)malloc(pwb);
+        std::vector<float> img((size_t)B * 3 * 96 * 96, 0.5f);
+        std::vector<unsigned char> crop((size_t)B * 3 * S * S);
+        EXPECT(pwb > 0 && cs_depth_preprocess(h, img.data(), CS_F32, B, H, H, patches.data(), crop.data(), pws, pwb, nullptr) == CS_OK);
+        EXPECT(cs_depth_preprocess(h, img.data(), CS_F32, B, H, H, patches.data(), nullptr, pws, 16, nullptr) != CS_OK);
+        EXPECT(cs_depth_preprocess(h, img.data(), CS_F32, B, H, 56, patches.data(), nullptr, pws, pwb, nullptr) == CS_E_UNSUPPORTED);   // not square
+        EXPECT(cs_depth_preprocess(h, img.data(), CS_F32, 0, H, 56, patches.data(), nullptr, pws, pwb, nullptr) == CS_E_UNSUPPORTED);   // ... refused before the empty batch returns
+        EXPECT(cs_depth_preprocess(h, nullptr, CS_F32, B, H, H, patches.data(), nullptr, pws, pwb, nullptr) == CS_E_ARG);
+        EXPECT(cs_depth_preprocess(h, nullptr, CS_F32, 0, H, H, nullptr, nullptr, nullptr, 0, nullptr) == CS_OK);                        // empty batch: no-op
+        free(pws);
+        const size_t pwb2 = cs_depth_preprocess_workspace_bytes(h, B, 96, 96);
+        pws = (char*)malloc(pwb2);
+        EXPECT(pwb2 > pwb && cs_depth_preprocess(h, img.data(), CS_F32, B, 96, 96, patches.data(), nullptr, pws, pwb2, nullptr) == CS_OK);   // a second size: a second table
+        free(pws);
+    }
+    EXPECT(cs_depth_forward(h, patches.data(), B, depth.data(), ws, wsb, nullptr) == CS_OK);
+    EXPECT(cs_depth_forward(h, patches.data(), B, depth.data(), ws, wsb - 1, nullptr) != CS_OK);
+    EXPECT(cs_depth_forward(h, nullptr, B, depth.data(), ws, wsb, nullptr) != CS_OK);
+    EXPECT(cs_depth_forward(h, patches.data(), B, nullptr, ws, wsb, nullptr) != CS_OK && cs_depth_forward(h, patches.data(), B, depth.data(), nullptr, wsb, nullptr) != CS_OK);
+    EXPECT(cs_depth_forward(nullptr, patches.data(), B, depth.data(), ws, wsb, nullptr) == CS_E_ARG && cs_depth_forward(h, patches.data(), -1, depth.data(), ws, wsb, nullptr) == CS_E_ARG);
+    EXPECT(cs_depth_forward(h, patches.data(), 0, depth.data(), ws, wsb, nullptr) == CS_OK);             // empty batch: no-op
+    {   // the post-processing to a size that is not the model's
+        const int H = 40, W = 56;
+        std::vector<float> maps((size_t)B * H * W);
+        EXPECT(cs_depth_normalized_maps(h, depth.data(), B, H, W, maps.data(), nullptr) == CS_OK);
+        EXPECT(cs_depth_normalized_maps(h, depth.data(), B, 0, W, maps.data(), nullptr) == CS_E_ARG && cs_depth_normalized_maps(h, nullptr, B, H, W, maps.data(), nullptr) == CS_E_ARG);
+        EXPECT(cs_depth_normalized_maps(nullptr, depth.data(), B, H, W, maps.data(), nullptr) == CS_E_ARG && cs_depth_normalized_maps(h, depth.data(), 0, H, W, maps.data(), nullptr) == CS_OK);
+    }
+    free(ws);
+    cs_depth_destroy(h);
+    cs_depth_destroy(nullptr);
+}
+
 // every weight but the last one set: finalize refuses with CS_E_STATE and names the tensor; what was staged is released by destroy (leak checking)
 template <typename NameAt, typename Set, typename Finalize>
 static void finalize_with_one_missing(int n, NameAt name_at, Set set, Finalize finalize) {
@@ -409,6 +527,22 @@ static void missing_weight_part() {
         cs_vit_destroy(h);
     }
     {
+        const CsClipVisionConfig c = clipv_config(); CsClipVision* h = nullptr;
+        EXPECT(cs_clipv_create(&c, &h) == CS_OK);
+        finalize_with_one_missing(cs_clipv_num_weights(h), [&](int i, int64_t* sh, int* nd) { return cs_clipv_weight_name(h, i, sh, nd); },
+                                  [&](const char* n, size_t cnt, const int64_t* sh, int nd) { buf.assign(cnt, 0.01f); return cs_clipv_set_weight(h, n, buf.data(), sh, nd); },
+                                  [&] { return cs_clipv_finalize(h); });
+        cs_clipv_destroy(h);
+    }
+    {
+        const CsDepthConfig c = depth_config(); CsDepth* h = nullptr;
+        EXPECT(cs_depth_create(&c, &h) == CS_OK);
+        finalize_with_one_missing(cs_depth_num_weights(h), [&](int i, int64_t* sh, int* nd) { return cs_depth_weight_name(h, i, sh, nd); },
+                                  [&](const char* n, size_t cnt, const int64_t* sh, int nd) { buf.assign(cnt, 0.01f); return cs_depth_set_weight(h, n, buf.data(), sh, nd); },
+                                  [&] { return cs_depth_finalize(h); });
+        cs_depth_destroy(h);
+    }
+    {
         const CsFluxConfig c = flux_config(); CsFlux* h = nullptr;
         EXPECT(cs_flux_create(&c, &h) == CS_OK);
         finalize_with_one_missing(cs_flux_num_weights(h), [&](int i, int64_t* sh, int* nd) { return cs_flux_weight_name(h, i, sh, nd); },
@@ -428,6 +562,8 @@ int main() {
     flux_part();
     clip_part();
     vit_part();
+    clipv_part();
+    depth_part();
     missing_weight_part();
     if (g_fail) { fprintf(stderr, "%d expectation(s) failed\n", g_fail); return 1; }
     printf("sanitize harness: ok\n");

@@ -1,6 +1,6 @@
 // Host-only stand-ins for the sanitizer harness (tests/sanitize/harness.cpp; TEST INFRASTRUCTURE, never linked into libconsolver_hip.so).
 //
-// The executors (unet.cpp / vae.cpp / flux.cpp / clip.cpp / vit.cpp / ops_api.cpp / api.cpp, with weights.h / encoder.h) are host code: weight repacking, a first-fit arena over the caller's
+// The executors (unet.cpp / vae.cpp / flux.cpp / clip.cpp / vit.cpp / clip_vision.cpp / depth.cpp / ops_api.cpp / api.cpp, with weights.h / encoder.h) are host code: weight repacking, a first-fit arena over the caller's
 // workspace, the dry-run workspace sizing and the launch sequence.  They are compiled here with -fsanitize=address,undefined -fno-gpu-sanitize (hipcc --cuda-host-only) and
 // linked against THIS file instead of the HIP kernels and the HIP runtime:
 //   * "device" memory is host malloc, so AddressSanitizer sees every buffer the executors carve out of the workspace;
@@ -122,6 +122,33 @@ int launch_vit_cls_layer_norm(const f16* x, long sample_stride, const f16* g, co
 int launch_cosine_reward(const float* pred, const float* target, long target_stride, int B, int D, float* out, hipStream_t) {
     rd(pred, (size_t)B * D * 4); rd(target, ((size_t)(B - 1) * target_stride + D) * 4); wr(out, (size_t)B * 4); return CS_OK;
 }
+// ---- clip_vision.cpp's two ends (vit_ops.hip)
+int launch_clipv_tokens_ln(const f16* pe, const f16* cls, const f16* pos, const f16* g, const f16* b, float, f16* x, int B, int NP, int D, hipStream_t) {
+    rd(pe, (size_t)B * NP * D * 2); rd(cls, (size_t)D * 2); rd(pos, (size_t)(NP + 1) * D * 2); rd(g, (size_t)D * 2); rd(b, (size_t)D * 2);
+    wr(x, (size_t)B * (NP + 1) * D * 2); return CS_OK;
+}
+int launch_clipv_head(const f16* x, long sample_stride, const f16* g, const f16* b, float, const f16* w, int B, int D, int P, float* out, hipStream_t) {
+    rd(x, ((size_t)(B - 1) * sample_stride + D) * 2); rd(g, (size_t)D * 2); rd(b, (size_t)D * 2); rd(w, (size_t)P * D * 2); wr(out, (size_t)B * P * 4); return CS_OK;
+}
+// ---- dpt_ops.hip
+int launch_dpt_conv(const DptConvArgs& a, hipStream_t) {
+    const size_t M = (size_t)a.B * a.H * a.W;
+    rd(a.x, M * a.Cin * 2); rd(a.w, (size_t)a.Cout * a.taps * a.Cin * 2); rd(a.bias, (size_t)a.Cout * 2); rd(a.res, M * a.Cout * 2); rd(a.res2, M * a.Cout * 2);
+    wr(a.out, M * a.Cout * 2); return CS_OK;
+}
+int launch_dpt_bilinear(const f16* x, int B, int Hi, int Wi, int C, int Ho, int Wo, f16* out, hipStream_t) {
+    rd(x, (size_t)B * Hi * Wi * C * 2); wr(out, (size_t)B * Ho * Wo * C * 2); return CS_OK;
+}
+int launch_dpt_pixel_shuffle(const f16* y, int B, int G, int k, int C, int skip, f16* out, hipStream_t) {
+    rd(y, (size_t)B * (skip + G * G) * k * k * C * 2); wr(out, (size_t)B * G * k * G * k * C * 2); return CS_OK;
+}
+int launch_dpt_head(const f16* x, long M, int C, const f16* w, const f16* bias, float, float* out, hipStream_t) {
+    rd(x, (size_t)M * C * 2); rd(w, (size_t)C * 2); rd(bias, 2); wr(out, (size_t)M * 4); return CS_OK;
+}
+int launch_dpt_bicubic(const float* x, int B, int Hi, int Wi, int Ho, int Wo, float* out, hipStream_t) {
+    rd(x, (size_t)B * Hi * Wi * 4); wr(out, (size_t)B * Ho * Wo * 4); return CS_OK;
+}
+int launch_dpt_minmax_normalize(float* x, int B, long n, hipStream_t) { wr(x, (size_t)B * n * 4); return CS_OK; }
 int launch_gemm2(const Gemm2Args& a, hipStream_t) {
     rd(a.a, 2); rd(a.w, (size_t)((a.N + 255) / 256 * 256) * a.K * 2); wr(a.out, 2);
     if (!a.c_seg_rows) wr(a.out, (((size_t)a.M - 1 + a.c_row_off) * a.ldc + a.c_col_off + a.N) * 2);

@@ -4,8 +4,8 @@ The executors' host code -- weight repacking, the first-fit arena over the calle
 variants, the launch sequences -- is compiled from the real sources with ``-fsanitize=address,undefined -fno-gpu-sanitize`` (hipcc ``--cuda-host-only``: no device code,
 no GPU) and linked with tests/sanitize/stubs.cpp (host malloc stands in for device memory; every launch stub touches the first and last byte of each
 tensor the kernel would access).  tests/sanitize/harness.cpp then drives create -> set_weight -> finalize -> workspace_bytes -> forward through the
-arena with a workspace of exactly the requested size, in both residual-stream modes and every knob variant, plus the error paths; the CLIP and ViT
-handles go through the same sequence at their smallest legal shapes, and every handle is finalized once with a weight missing.
+arena with a workspace of exactly the requested size, in both residual-stream modes and every knob variant, plus the error paths; the CLIP, ViT, CLIP vision
+and Depth Anything handles go through the same sequence at their smallest legal shapes, and every handle is finalized once with a weight missing.
 GPU-side sanitizers are not available on this pool (xnack), so this is the sanitizer coverage the tree has.
 """
 import os
@@ -16,7 +16,7 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "consolver_amd", "csrc")
-HOST_SOURCES = ["api.cpp", "unet.cpp", "vae.cpp", "flux.cpp", "clip.cpp", "vit.cpp", "ops_api.cpp"]
+HOST_SOURCES = ["api.cpp", "unet.cpp", "vae.cpp", "flux.cpp", "clip.cpp", "vit.cpp", "clip_vision.cpp", "depth.cpp", "ops_api.cpp"]
 
 
 def _hipcc():

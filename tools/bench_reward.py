@@ -1,0 +1,131 @@
+"""Times one of the model rewards of the PPO trainer on a batch of predicted + teacher images at 512 x 512 fp16, split into its stages.  Synthetic weights;
+medians of ``--reps`` runs after ``--warmup``; one JSON line at the end.
+
+    python tools/bench_reward.py --reward dino  [--batch 80] [--reps 7] [--no-vae] [--out profiles/dino_reward_bench.txt]
+    python tools/bench_reward.py --reward clip  [--batch 16] [--reps 7] [--out profiles/clip_reward_bench.txt]
+    python tools/bench_reward.py --reward depth [--batch 8]  [--reps 7] [--out profiles/depth_reward_bench.txt]
+
+* ``dino`` (config 5's batch, 80 + 80 images): front end (quantise + PIL-exact resize + crop + normalise + patch rows), encoder (12 layers, 257 tokens per
+  image), tail (normalise, cosine, scale) and, in the same process, the VAE decode of those 160 images for scale.
+* ``clip``: the same front end, the tower (embeddings + pre_layrnorm, 24 layers at 257 tokens per image, post_layernorm + projection) with its rate as a
+  fraction of the fp16 MFMA peak from ``flops()``, the tail.
+* ``depth``: front end (resize to 518 x 518), model (DINOv2-small backbone at 1370 tokens tapped four times, DPT neck and head), post-processing (bicubic to
+  512 x 512, min / max normalisation), tail (PSNR) and the whole ``calculate_depth_reward`` call.
+"""
+import argparse
+import json
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch
+
+from consolver_amd import synth
+from consolver_amd.ppo import depth_psnr_tail
+from consolver_amd.reward_model import calculate_depth_reward, cosine_reward, load_depth_reward, load_reward_model
+
+DEV = "cuda:0"
+PEAK_F16_TFLOPS = 2500.0
+DEFAULT_BATCH = {"dino": 80, "clip": 16, "depth": 8}
+
+
+def timed(fn, warmup, reps):
+    for _ in range(warmup):
+        fn()
+    ms = []
+    for _ in range(reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        ms.append(a.elapsed_time(b))
+    return sorted(ms)[len(ms) // 2]
+
+
+def random_images(a, n):
+    return torch.rand(n, 3, a.size, a.size, device=DEV, dtype=torch.float16)
+
+
+def bench_features(a, res, B, n):
+    """dino / clip: front end, encoder (clip: "tower"), cosine tail"""
+    enc = "encoder" if a.reward == "dino" else "tower"
+    model, _ = load_reward_model(a.reward, device=DEV)
+    state_dict = synth.synthetic_dinov2_state_dict if a.reward == "dino" else synth.synthetic_clip_vision_state_dict
+    model.load_state_dict(state_dict(model.manifest()))
+    images = random_images(a, n)
+    patches = model.preprocess(images)
+    feats = model.encode_patches(patches)
+    res["front_end_ms"] = timed(lambda: model.preprocess(images), a.warmup, a.reps)
+    res[enc + "_ms"] = timed(lambda: model.encode_patches(patches), a.warmup, a.reps)
+    res["tail_ms"] = timed(lambda: cosine_reward(feats[:B], feats[B:]), a.warmup, a.reps)
+    res["reward_total_ms"] = res["front_end_ms"] + res[enc + "_ms"] + res["tail_ms"]
+    res[enc + "_tflop"] = model.flops(n) / 1e12
+    res[enc + "_tflops"] = model.flops(n) / res[enc + "_ms"] / 1e9
+    rate = f"({res[enc + '_tflop']:.2f} TFLOP, {res[enc + '_tflops']:.0f} TFLOP/s"
+    if a.reward == "clip":
+        res["tower_frac_of_fp16_mfma_peak"] = res["tower_tflops"] / PEAK_F16_TFLOPS
+        rate += f", {100 * res['tower_frac_of_fp16_mfma_peak']:.1f} % of the fp16 MFMA peak"
+    lines = [f"  front end  {res['front_end_ms']:9.3f} ms", f"  {enc:<9s}  {res[enc + '_ms']:9.3f} ms  {rate})",
+             f"  tail       {res['tail_ms']:9.3f} ms", f"  total      {res['reward_total_ms']:9.3f} ms"]
+    if a.reward == "dino" and not a.no_vae:
+        from consolver_amd.vae import HipAutoencoderKL, decode_latents
+        vae = HipAutoencoderKL({}, device=DEV)
+        vae.load_state_dict(synth.synthetic_vae_state_dict(vae.manifest()))
+        lat = torch.randn(n, 4, a.size // 8, a.size // 8, device=DEV, dtype=torch.float16) * 0.18
+        res["vae_decode_ms"] = timed(lambda: decode_latents(vae, lat, 8), 1, 3)
+        res["vae_decode_tflop"] = vae.flops(n) / 1e12
+        res["reward_over_decode"] = res["reward_total_ms"] / res["vae_decode_ms"]
+        lines.append(f"  VAE decode of the same {n} images {res['vae_decode_ms']:9.3f} ms ({res['vae_decode_tflop']:.0f} TFLOP): reward / decode = {res['reward_over_decode']:.3f}")
+    return lines
+
+
+def bench_depth(a, res, B, n):
+    model, proc = load_depth_reward(device=DEV)
+    model.load_state_dict(synth.synthetic_depth_anything_state_dict(model.manifest()))
+    images = random_images(a, n)
+    patches = model.preprocess(images)
+    depth = model.depth_from_patches(patches)
+    maps = model.post_process(depth, a.size, a.size)
+    res["max_batch"] = model.max_batch
+    res["front_end_ms"] = timed(lambda: model.preprocess(images), a.warmup, a.reps)
+    res["model_ms"] = timed(lambda: model.depth_from_patches(patches), a.warmup, a.reps)
+    res["post_process_ms"] = timed(lambda: model.post_process(depth, a.size, a.size), a.warmup, a.reps)
+    res["tail_ms"] = timed(lambda: depth_psnr_tail(maps[:B], maps[B:]), a.warmup, a.reps)
+    res["reward_call_ms"] = timed(lambda: calculate_depth_reward(model, proc, images[:B], images[B:], DEV), a.warmup, a.reps)
+    res["model_tflop"] = model.flops(n) / 1e12
+    res["model_tflops"] = model.flops(n) / res["model_ms"] / 1e9
+    res["workspace_mb_per_image"] = int(model._fn("workspace_bytes")(model._h, 1)) / 1e6
+    return [f"  front end     {res['front_end_ms']:9.3f} ms",
+            f"  model         {res['model_ms']:9.3f} ms  ({res['model_tflop']:.2f} TFLOP, {res['model_tflops']:.0f} TFLOP/s)",
+            f"  post-process  {res['post_process_ms']:9.3f} ms", f"  tail          {res['tail_ms']:9.3f} ms",
+            f"  calculate_depth_reward, whole call {res['reward_call_ms']:9.3f} ms"]
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reward", choices=sorted(DEFAULT_BATCH), required=True)
+    ap.add_argument("--batch", type=int, default=None, help="pred / target pairs (default: 80 dino, 16 clip, 8 depth)")
+    ap.add_argument("--size", type=int, default=512)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--reps", type=int, default=7)
+    ap.add_argument("--no-vae", action="store_true", help="dino: skip the VAE decode of the same images")
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    B = a.batch if a.batch is not None else DEFAULT_BATCH[a.reward]
+    n = 2 * B
+    res = {"batch_pairs": B, "images": n, "size": a.size}
+    stages = (bench_depth if a.reward == "depth" else bench_features)(a, res, B, n)
+    model_name = ", ViT-L/14" if a.reward == "clip" else ""
+    lines = [f"{a.reward} reward, {n} images ({B} pred + {B} target) at {a.size}^2 fp16{model_name}, synthetic weights, medians of {a.reps}"] + stages
+    lines.append(json.dumps(res))
+    text = "\n".join(lines)
+    print(text)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(text + "\n")
+
+
+if __name__ == "__main__":
+    main()
