@@ -82,6 +82,11 @@ class CsGemm2Problem(C.Structure):
                 ("out", C.c_void_p), ("ldc", C.c_long), ("col_off", C.c_int)]
 
 
+class CsGemm2Addressing(C.Structure):
+    _fields_ = [("lda", C.c_long), ("a_seg_rows", C.c_int), ("a_seg_stride", C.c_int), ("a_row_off", C.c_long),
+                ("c_seg_rows", C.c_int), ("c_seg_stride", C.c_int), ("c_row_off", C.c_long), ("res_lo", C.c_void_p), ("out_lo", C.c_void_p)]
+
+
 # every symbol declared in include/consolver_hip.h: name -> (restype, argtypes)
 SYMBOLS = {
     "cs_abi_version": (C.c_int, []),
@@ -185,6 +190,16 @@ SYMBOLS = {
                                      C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
     "cs_op_gemm2_pair": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
     "cs_op_gemm2_workspace": (C.c_size_t, [C.c_int, C.c_int]),
+    "cs_op_gemm2_ex": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "cs_op_qk_norm_rope": (C.c_int, [C.c_void_p, C.c_long, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_int, C.c_void_p, C.c_void_p, C.c_float, C.c_int, C.c_void_p]),
+    "cs_op_small_linear": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "cs_op_ln_modulate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_long, C.c_float,
+                                    C.c_int, C.c_void_p]),
+    "cs_op_sinusoid_f32": (C.c_int, [C.c_void_p, C.c_float, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "cs_op_add3_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "cs_op_cast_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p]),
+    "cs_op_planes_to_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p]),
     "cs_op_attention_causal": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
                                          C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p]),
     "cs_op_rms_norm": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_int, C.c_void_p]),

@@ -317,6 +317,43 @@ int cs_op_gemm2_pair(const CsGemm2Problem* a, const CsGemm2Problem* b, int dtype
 }
 size_t cs_op_gemm2_workspace(int tiles, int K) { return gemm2_tail_workspace_bytes(tiles, K); }
 
+static Gemm2Args g2_from(const CsGemm2Problem& q, const CsGemm2Addressing* ad, int dtype) {
+    Gemm2Args g = g2_from(q, dtype);
+    if (ad) {
+        g.lda = ad->lda; g.a_seg_rows = ad->a_seg_rows; g.a_seg_stride = ad->a_seg_stride; g.a_row_off = ad->a_row_off;
+        g.c_seg_rows = ad->c_seg_rows; g.c_seg_stride = ad->c_seg_stride; g.c_row_off = ad->c_row_off; g.res_lo = ad->res_lo; g.out_lo = ad->out_lo;
+    }
+    return g;
+}
+int cs_op_gemm2_ex(const CsGemm2Problem* a, const CsGemm2Addressing* a_addr, const CsGemm2Problem* b, const CsGemm2Addressing* b_addr, int dtype,
+                   void* workspace, size_t workspace_bytes, void* stream) {
+    if (!a) CS_FAIL(CS_E_ARG, "gemm2: null problem");
+    Gemm2Args ga = g2_from(*a, a_addr, dtype);
+    ga.tail_ws = workspace; ga.tail_ws_bytes = workspace_bytes;
+    if (!b) return launch_gemm2(ga, (hipStream_t)stream);
+    return launch_gemm2_pair(ga, g2_from(*b, b_addr, dtype), (hipStream_t)stream);
+}
+
+int cs_op_qk_norm_rope(void* qkv, long ld, int rows, int seq, int heads, int dh, int q_col, int k_col, const void* wq, const void* wk, const void* wq_ctx,
+                       const void* wk_ctx, int ctx_rows, const float* cosv, const float* sinv, float eps, int dtype, void* stream) {
+    return launch_qk_norm_rope(qkv, ld, rows, seq, heads, dh, q_col, k_col, wq, wk, wq_ctx, wk_ctx, ctx_rows, cosv, sinv, eps, dtype, (hipStream_t)stream);
+}
+int cs_op_small_linear(const float* x, int R, int K, const void* w, const void* bias, int N, float* out, int silu_in, int silu_out, int dtype, void* stream) {
+    return launch_small_linear(x, R, K, w, bias, N, out, silu_in, silu_out, dtype, (hipStream_t)stream);
+}
+int cs_op_ln_modulate(const void* x, const void* x_lo, void* y, void* y_lo, int M, int C, int rows_per_sample, const float* shift, const float* scale,
+                      long mod_stride, float eps, int dtype, void* stream) {
+    return launch_ln_modulate(x, y, M, C, rows_per_sample, shift, scale, mod_stride, eps, dtype, (hipStream_t)stream, x_lo, y_lo);
+}
+int cs_op_sinusoid_f32(const float* t, float mult, int R, int C, float* out, void* stream) { return launch_sinusoid_f32(t, mult, R, C, out, (hipStream_t)stream); }
+int cs_op_add3_f32(const float* a, const float* b, const float* c, float* out, int64_t n, void* stream) {
+    return launch_add3_f32(a, b, c, out, (long)n, (hipStream_t)stream);
+}
+int cs_op_cast_f32(const float* x, void* out, int64_t n, int dtype, void* stream) { return launch_cast_f32(x, out, (long)n, dtype, (hipStream_t)stream); }
+int cs_op_planes_to_f32(const void* hi, const void* lo, float* out, int64_t n, int dtype, void* stream) {
+    return launch_planes_to_f32(hi, lo, out, (long)n, dtype, (hipStream_t)stream);
+}
+
 int cs_op_attention_ex(const void* q, int q_stride, const void* k, int k_stride, const void* v, int v_stride, void* out, int out_stride,
                        int B, int H, int Nq, int Nk, int dh, float scale, int dtype, void* stream) {
     AttnArgs a{};

@@ -172,6 +172,42 @@ int cs_op_gemm2_pair(const CsGemm2Problem* a, const CsGemm2Problem* b /* may be 
  * tiles and summed (same rounding points as the unsplit epilogue; the fp32 summation order differs).  0: the launch never splits;
  * workspace may be NULL (no split). */
 size_t cs_op_gemm2_workspace(int tiles, int K);
+/* The rest of the transformer GEMM's addressing, as the FLUX blocks use it (all zero / NULL: cs_op_gemm2_pair's plain form).
+ *   lda: elements between rows of x (0: K);
+ *   a_seg_rows / a_seg_stride / a_row_off: x row r is read at buffer row (r / seg) * stride + r % seg + off (seg = 0: r + off) -- the [context | image]
+ *     token ranges of the joint sequence; c_seg_rows / c_seg_stride / c_row_off: the same map for the rows of out, res, out_lo and res_lo;
+ *   res_lo / out_lo: the split residual stream of cs_op_gemm2_x2 (both or neither, need res, exclude an activation), addressed like res / out.
+ * The gate row is m / rows_per_sample of the UNMAPPED row m. */
+typedef struct CsGemm2Addressing {
+    long lda; int a_seg_rows, a_seg_stride; long a_row_off;
+    int c_seg_rows, c_seg_stride; long c_row_off;
+    const void* res_lo; void* out_lo;
+} CsGemm2Addressing;
+/* cs_op_gemm2_pair with every addressing field: one problem (b = NULL) or two in one launch; a_addr / b_addr may be NULL.  Two problems whose activation or
+ * split form differ run as two launches; workspace as for cs_op_gemm2_pair. */
+int cs_op_gemm2_ex(const CsGemm2Problem* a, const CsGemm2Addressing* a_addr, const CsGemm2Problem* b /* may be NULL */, const CsGemm2Addressing* b_addr, int dtype,
+                   void* workspace, size_t workspace_bytes, void* stream);
+
+/* FLUX DiT glue (dtype = CS_F16 1 | CS_BF16 2).
+ * In place on a fused qkv buffer [rows][ld]: per head RMSNorm over dh of q (columns q_col + h dh ...) and k (k_col + h dh ...), times weight, then the rotary
+ * embedding of the (2i, 2i+1) pairs with cos / sin [seq][dh / 2] (fp32) at position row % seq.  Rows with row % seq < ctx_rows take wq_ctx / wk_ctx (NULL: wq / wk).
+ * dh / 8 must be a power of two <= 32.  Nothing else of the buffer is touched. */
+int cs_op_qk_norm_rope(void* qkv, long ld, int rows, int seq, int heads, int dh, int q_col, int k_col, const void* wq, const void* wk, const void* wq_ctx,
+                       const void* wk_ctx, int ctx_rows, const float* cosv, const float* sinv, float eps, int dtype, void* stream);
+/* tiny-M linear of the conditioning path: out[r][n] = silu_out?(sum_k silu_in?(x[r][k]) w[n][k] + bias[n]); x / out fp32, w [N][K] / bias (may be NULL) of dtype;
+ * K % 8 == 0 */
+int cs_op_small_linear(const float* x, int R, int K, const void* w, const void* bias, int N, float* out, int silu_in, int silu_out, int dtype, void* stream);
+/* cs_op_ln_modulate_x2 with the result as two planes too: y_lo (may be NULL; needs x_lo) = T(o - float(y)), the output head's LayerNorm.  C % 8 == 0, C <= 4096 */
+int cs_op_ln_modulate(const void* x, const void* x_lo, void* y, void* y_lo, int M, int C, int rows_per_sample, const float* shift, const float* scale,
+                      long mod_stride, float eps, int dtype, void* stream);
+/* timestep embedding: out[r] = [cos(a_k) | sin(a_k)], a_k = t[r] mult exp(-ln(1e4) k / (C / 2)), k < C / 2; fp32 */
+int cs_op_sinusoid_f32(const float* t, float mult, int R, int C, float* out, void* stream);
+/* out = a + b + c in fp32 (b and c may be NULL) */
+int cs_op_add3_f32(const float* a, const float* b, const float* c, float* out, int64_t n, void* stream);
+/* out = T(x), round to nearest even */
+int cs_op_cast_f32(const float* x, void* out, int64_t n, int dtype, void* stream);
+/* out = float(hi) + float(lo): a tensor kept as two planes of dtype, handed out in fp32 */
+int cs_op_planes_to_f32(const void* hi, const void* lo, float* out, int64_t n, int dtype, void* stream);
 /* cs_op_attention with an explicit dtype (bf16: head dim 128) */
 int cs_op_attention_ex(const void* q, int q_stride, const void* k, int k_stride, const void* v, int v_stride, void* out, int out_stride,
                        int B, int H, int Nq, int Nk, int dh, float scale, int dtype, void* stream);
