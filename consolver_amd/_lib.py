@@ -76,6 +76,12 @@ class CsDepthConfig(C.Structure):
                 ("size", C.c_int), ("image_mean", C.c_float * 3), ("image_std", C.c_float * 3), ("rescale_factor", C.c_double)]
 
 
+class CsSegConfig(C.Structure):
+    _fields_ = [("hidden_sizes", C.c_int * 4), ("depths", C.c_int * 4), ("num_attention_heads", C.c_int * 4), ("sr_ratios", C.c_int * 4), ("mlp_ratio", C.c_int),
+                ("decoder_hidden_size", C.c_int), ("num_labels", C.c_int), ("size", C.c_int), ("image_mean", C.c_float * 3), ("image_std", C.c_float * 3),
+                ("rescale_factor", C.c_double)]
+
+
 class CsGemm2Problem(C.Structure):
     _fields_ = [("x", C.c_void_p), ("M", C.c_int), ("K", C.c_int), ("w", C.c_void_p), ("bias", C.c_void_p), ("N", C.c_int),
                 ("res", C.c_void_p), ("gate", C.c_void_p), ("gate_stride", C.c_long), ("rows_per_sample", C.c_int), ("act", C.c_int),
@@ -265,10 +271,20 @@ SYMBOLS = {
     "cs_op_dpt_head": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]),
     "cs_op_dpt_bicubic": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "cs_op_dpt_minmax_normalize": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_void_p]),
+    "cs_seg_masks": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "cs_seg_set_stage_limit": (C.c_int, [C.c_void_p, C.c_int]),
+    "cs_seg_agreement": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_void_p, C.c_void_p]),
+    "cs_op_seg_dwconv_gelu": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cs_op_seg_im2col": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "cs_op_seg_patchify": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "cs_op_seg_bilinear": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_void_p]),
+    "cs_op_seg_argmax": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_void_p, C.c_void_p]),
+    "cs_op_seg_logits": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_void_p, C.c_void_p]),
+    "cs_op_seg_relu": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p]),
 }
 
-# the three image-tower handle families (csrc/image_tower.h) declare the same 13 entry points, each over its own config struct
-for _prefix, _config in (("vit", CsVitConfig), ("clipv", CsClipVisionConfig), ("depth", CsDepthConfig)):
+# the image-tower handle families (csrc/image_tower.h) declare the same 13 entry points, each over its own config struct
+for _prefix, _config in (("vit", CsVitConfig), ("clipv", CsClipVisionConfig), ("depth", CsDepthConfig), ("seg", CsSegConfig)):
     SYMBOLS.update({
         f"cs_{_prefix}_create": (C.c_int, [C.POINTER(_config), C.POINTER(C.c_void_p)]),
         f"cs_{_prefix}_destroy": (None, [C.c_void_p]),

@@ -34,6 +34,8 @@ SOURCES = {
     "clip_vision.cpp": [],
     "dpt_ops.hip": [],
     "depth.cpp": [],
+    "seg_ops.hip": [],
+    "segformer.cpp": [],
     "ppo.hip": [],
     "ops_api.cpp": [],
 }

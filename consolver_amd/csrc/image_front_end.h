@@ -12,8 +12,9 @@
 
 namespace image_front_end {
 
-// one pass of PIL's ImagingResample (BICUBIC: Keys cubic a = -0.5, support 2 * max(scale, 1)) for output indices win0 .. win0 + win: taps normalised in double,
-// converted as int(+-0.5 + k 2^22)
+// one pass of PIL's ImagingResample (BICUBIC: Keys cubic a = -0.5, support 2 * max(scale, 1); BILINEAR: the triangle filter, support max(scale, 1)) for output
+// indices win0 .. win0 + win: taps normalised in double, converted as int(+-0.5 + k 2^22)
+enum Filter { PIL_BILINEAR = 2, PIL_BICUBIC = 3 };          // PIL.Image.Resampling values
 struct Taps { std::vector<int> lo, cnt, kk; int ksize; };
 inline double pil_cubic(double x) {
     const double a = -0.5;
@@ -22,9 +23,13 @@ inline double pil_cubic(double x) {
     if (x < 2.0) return (((x - 5) * x + 8) * x - 4) * a;
     return 0.0;
 }
-inline Taps pil_taps(int in, int out, int win0, int win) {
+inline double pil_triangle(double x) {
+    x = std::fabs(x);
+    return x < 1.0 ? 1.0 - x : 0.0;
+}
+inline Taps pil_taps(int in, int out, int win0, int win, Filter filter = PIL_BICUBIC) {
     Taps t;
-    const double scale = (double)in / out, fs = std::max(scale, 1.0), support = 2.0 * fs, ww = 1.0 / fs;
+    const double scale = (double)in / out, fs = std::max(scale, 1.0), support = (filter == PIL_BILINEAR ? 1.0 : 2.0) * fs, ww = 1.0 / fs;
     t.ksize = (int)std::ceil(support) * 2 + 1;
     t.lo.resize(win); t.cnt.resize(win); t.kk.assign((size_t)win * t.ksize, 0);
     std::vector<double> w(t.ksize);
@@ -32,7 +37,11 @@ inline Taps pil_taps(int in, int out, int win0, int win) {
         const double center = (win0 + i + 0.5) * scale;
         const int xmin = std::max((int)(center - support + 0.5), 0), n = std::min((int)(center + support + 0.5), in) - xmin;
         double tot = 0;
-        for (int x = 0; x < n; ++x) { w[x] = pil_cubic((x + xmin - center + 0.5) * ww); tot += w[x]; }
+        for (int x = 0; x < n; ++x) {
+            const double a = (x + xmin - center + 0.5) * ww;
+            w[x] = filter == PIL_BILINEAR ? pil_triangle(a) : pil_cubic(a);
+            tot += w[x];
+        }
         for (int x = 0; x < n; ++x) {
             const double k = tot != 0.0 ? w[x] / tot : w[x];
             t.kk[(size_t)i * t.ksize + x] = k < 0 ? (int)(-0.5 + k * (1 << 22)) : (int)(0.5 + k * (1 << 22));
@@ -49,6 +58,7 @@ struct Plan { VitResizePlan dev; };
 // tables live on the device that is current when a size is first seen: callers run a handle on one device (the Python wrapper selects the tensor's).
 struct PlanCache {
     static constexpr size_t MAX_PLANS = 16;
+    Filter filter = PIL_BICUBIC;                            // the processor's resample (set once, before the first plan)
     std::map<std::pair<int, int>, Plan> plans;
     std::vector<void*> plan_allocs;
 
@@ -61,7 +71,7 @@ struct PlanCache {
         const int shrt = std::min(H, W), lng = std::max(H, W), nl = (int)((double)((int64_t)edge * lng) / shrt);
         const int nh = H <= W ? edge : nl, nw = H <= W ? nl : edge;
         if (nh < C || nw < C) CS_FAIL(CS_E_UNSUPPORTED, "%s: resized image %d x %d is smaller than the %d crop (the processor would pad)", who, nh, nw, C);
-        const Taps th = pil_taps(W, nw, (nw - C) / 2, C), tv = pil_taps(H, nh, (nh - C) / 2, C);
+        const Taps th = pil_taps(W, nw, (nw - C) / 2, C, filter), tv = pil_taps(H, nh, (nh - C) / 2, C, filter);
         Plan p{};
         int row0 = H, row1 = 0, col0 = W, col1 = 0;
         for (int i = 0; i < C; ++i) {

@@ -310,3 +310,23 @@ int launch_dpt_head(const f16* x, long M, int C, const f16* w, const f16* bias, 
 int launch_dpt_bicubic(const float* x, int B, int Hi, int Wi, int Ho, int Wo, float* out, hipStream_t s);
 // x[b] <- (x[b] - min) / (max - min + 1e-8) over the n elements of every map, in place (one workgroup per map)
 int launch_dpt_minmax_normalize(float* x, int B, long n, hipStream_t s);
+
+// ---- SegFormer segmentation reward (seg_ops.hip / segformer.cpp): the glue of the MiT encoder and the all-MLP head, and the reward's tail -----------------
+// Mix-FFN: out = gelu_erf(depthwise 3x3 conv (pad 1) of x [B][H][W][C] + bias); w [9][C] (tap ky * 3 + kx major), bias [C] or null; C a multiple of 64 up to
+// 2048, any H x W; fp32 arithmetic, one rounding.  out must not alias x.
+int launch_seg_dwconv_gelu(const f16* x, int B, int H, int W, int C, const f16* w, const f16* bias, f16* out, hipStream_t s);
+// rows of a k x k conv (stride, pad) over the first C channels of x [B][H][W][Cs] in F.unfold order: out [B * Ho * Wo][Kp], column c k k + ky k + kx, zero
+// where the tap is outside the image and in the columns C k k .. Kp
+int launch_seg_im2col(const f16* x, int B, int H, int W, int Cs, int C, int k, int stride, int pad, int Kp, f16* out, hipStream_t s);
+// rows of a kernel = stride = sr conv: x [B][H][W][C] -> out [B * (H / sr) * (W / sr)][sr * sr * C], column (ky * sr + kx) * C + c; C % 8 == 0
+int launch_seg_patchify(const f16* x, int B, int H, int W, int C, int sr, f16* out, hipStream_t s);
+// F.interpolate(mode="bilinear", align_corners=False) of x [B][Hi][Wi][C] into the columns col .. col + C of out [B * Ho * Wo][ld]; C, col, ld multiples of 8
+int launch_seg_bilinear(const f16* x, int B, int Hi, int Wi, int C, int Ho, int Wo, f16* out, long ld, int col, hipStream_t s);
+// x <- max(x, 0) in place; n % 8 == 0
+int launch_seg_relu(f16* x, long n, hipStream_t s);
+// out[m] = argmax over the first n columns of x [M][ld]; a tie goes to the lowest index
+int launch_seg_argmax(const f16* x, long M, long ld, int n, int* out, hipStream_t s);
+// x [B * HW][ld] fp16 -> out [B][n][HW] fp32 (the first n columns): the logits as transformers lays them out
+int launch_seg_logits(const f16* x, int B, long HW, long ld, int n, float* out, hipStream_t s);
+// out[b] = 100 * mean(pred[b][i] == target[b * target_stride + i], i < n) in fp32; target_stride 0 shares one target
+int launch_seg_agreement(const int* pred, const int* target, long target_stride, int B, long n, float* out, hipStream_t s);

@@ -25,6 +25,12 @@ square image to 518 x 518, bit-identical on the uint8 image), the DINOv2-small b
 torch's bicubic resize back to the images' size with the per-map min / max normalisation (cs_depth_normalized_maps) and the PSNR tail
 (``ppo.depth_psnr_tail``).  Weights load under their ``transformers.DepthAnythingForDepthEstimation`` names.  The fp32 restatement lives in
 tests/depth_oracle.py.
+
+``segmentation`` (:110-117, :425-481): ``load_segmentation_reward()`` -> a ``HipSegformerModel`` of the ``nvidia/segformer-b4-finetuned-ade-512-512`` shape
+and a ``SegImageProcessor``; ``calculate_segmentation_reward`` runs the front end (PIL BILINEAR resize of the square image to 512 x 512, bit-identical on the
+uint8 image), the MiT-B4 encoder and the all-MLP head (cs_seg_forward), the class argmax at a quarter of the processor's size (cs_seg_masks) and the
+agreement tail 100 * mean(mask_pred == mask_target) (cs_seg_agreement).  Weights load under their ``transformers.SegformerForSemanticSegmentation`` names.
+The fp32 restatement lives in tests/segformer_oracle.py.
 """
 import ctypes as C
 
@@ -41,6 +47,9 @@ CLIP_VIT_L14_CONFIG = dict(hidden_size=1024, intermediate_size=4096, num_hidden_
 DEPTH_ANYTHING_V2_SMALL_CONFIG = dict(hidden_size=384, num_hidden_layers=12, num_attention_heads=6, mlp_ratio=4, image_size=518, patch_size=14,
                                       layer_norm_eps=1e-6, out_indices=(3, 6, 9, 12), neck_hidden_sizes=(48, 96, 192, 384), fusion_hidden_size=64,
                                       head_hidden_size=32, max_depth=1.0)
+# nvidia/segformer-b4-finetuned-ade-512-512 (its config.json, from memory: no hub access here): MiT-B4 + the all-MLP head over the 150 ADE20K classes
+SEGFORMER_B4_ADE_CONFIG = dict(hidden_sizes=(64, 128, 320, 512), depths=(3, 8, 27, 3), num_attention_heads=(1, 2, 5, 8), sr_ratios=(8, 4, 2, 1), mlp_ratio=4,
+                               decoder_hidden_size=768, num_labels=150, image_size=512)
 _DT = {torch.float32: L.CS_F32, torch.float16: L.CS_F16}
 
 
@@ -335,6 +344,119 @@ class HipDepthAnythingModel(_HipImageModel):
         return self.post_process(self.predicted_depth(images), images.shape[-2], images.shape[-1])
 
 
+class SegImageProcessor:
+    """The preprocessing constants of ``nvidia/segformer-b4-finetuned-ade-512-512`` (its preprocessor_config.json, a SegformerImageProcessor; from memory: no
+    hub access here): resize to 512 x 512 with PIL BILINEAR, no crop, rescale 1/255, normalise with the ImageNet mean / std, labels not reduced.  A plain
+    holder: the arithmetic runs in ``HipSegformerModel.preprocess`` (square inputs; others are refused by the front end)."""
+    do_resize = do_rescale = do_normalize = True
+    do_reduce_labels = False
+    resample = 2                                   # PIL.Image.BILINEAR
+
+    def __init__(self, size=None, rescale_factor=1 / 255, image_mean=(0.485, 0.456, 0.406), image_std=(0.229, 0.224, 0.225)):
+        self.size = dict(size or {"height": 512, "width": 512})
+        if set(self.size) != {"height", "width"} or self.size["height"] != self.size["width"] or self.size["height"] % 32:
+            raise ValueError("the HIP front end implements a square size that is a multiple of 32")
+        self.rescale_factor, self.image_mean, self.image_std = float(rescale_factor), tuple(image_mean), tuple(image_std)
+
+    def constants(self):
+        return (self.size["height"], self.resample, self.rescale_factor, self.image_mean, self.image_std)
+
+
+class _SegConfigView:
+    """``model.config.num_labels`` / ``.num_classes`` as the reference reads them, and the config dict's keys"""
+
+    def __init__(self, cfg):
+        self.__dict__.update(cfg)
+        self.num_classes = cfg["num_labels"]
+
+    def __eq__(self, other):
+        return {k: v for k, v in self.__dict__.items() if k != "num_classes"} == (other if isinstance(other, dict) else getattr(other, "__dict__", None))
+
+    def __getitem__(self, k):
+        return self.__dict__[k]
+
+
+class _SegOutput(tuple):
+    """(logits,): ``outputs.logits`` [B, num_labels, size / 4, size / 4] fp32, as transformers' SemanticSegmenterOutput names it"""
+    logits = property(lambda self: self[0])
+
+
+class HipSegformerModel(_HipImageModel):
+    """``transformers.SegformerForSemanticSegmentation`` (default: the MiT-B4 ADE shape).  ``model(pixel_values=...).logits`` is the call the reference
+    makes; ``masks(images)`` runs the processor's arithmetic and the class argmax on the GPU as well."""
+    workspace_budget = 2048 << 20         # bytes of workspace one call may take: max_batch is sized from it (B4 at 512: 167 MB per image -> 12 images per call)
+    _prefix = "seg"
+
+    def __init__(self, config=None, device="cuda:0", processor=None):
+        cfg = dict(SEGFORMER_B4_ADE_CONFIG)
+        cfg.update(config or {})
+        self.config = _SegConfigView(cfg)
+        self.device = torch.device(device)
+        self.processor = processor or SegImageProcessor({"height": cfg["image_size"], "width": cfg["image_size"]})
+        size, _, rescale, mean, std = self.processor.constants()
+        if size != cfg["image_size"]:
+            raise ValueError(f"the processor resizes to {size}, the model was configured for {cfg['image_size']}")
+        i4 = lambda k: (C.c_int * 4)(*cfg[k])
+        c = L.CsSegConfig(i4("hidden_sizes"), i4("depths"), i4("num_attention_heads"), i4("sr_ratios"), cfg["mlp_ratio"], cfg["decoder_hidden_size"],
+                          cfg["num_labels"], size, (C.c_float * 3)(*mean), (C.c_float * 3)(*std), rescale)
+        h = C.c_void_p()
+        L.check(L.lib().cs_seg_create(C.byref(c), C.byref(h)))
+        self._init_handle(h, size, 1)
+        self.grid, self.num_labels = size // 4, cfg["num_labels"]
+        self.max_batch = max(1, min(_HipImageModel.max_batch, self.workspace_budget // int(self._fn("workspace_bytes")(h, 1))))
+
+    def _run(self, patches, want_logits, want_masks):
+        """the normalised image rows -> (logits [B, num_labels, g, g] fp32 | None, masks [B, g, g] int32 | None), ``max_batch`` images per call"""
+        if not self._finalized:
+            raise RuntimeError("weights not loaded")
+        L.require_cuda(patches, "patches")
+        px, g = self.crop * self.crop, self.grid
+        B = patches.shape[0] // px
+        logits = torch.empty(B, self.num_labels, g, g, dtype=torch.float32, device=patches.device) if want_logits else None
+        masks = torch.empty(B, g, g, dtype=torch.int32, device=patches.device) if want_masks else None
+        st = L.stream_ptr(patches.device)
+        for s in range(0, B, self.max_batch):
+            n = min(self.max_batch, B - s)
+            need = int(self._fn("workspace_bytes")(self._h, n))
+            if self._ws is None or self._ws.numel() < need or self._ws.device != patches.device:
+                self._ws = torch.empty(need, dtype=torch.uint8, device=patches.device)
+            L.check(self._fn("forward")(self._h, L.ptr(patches[s * px:]), n, L.ptr(logits[s:]) if want_logits else None, L.ptr(self._ws), self._ws.numel(), st))
+            if want_masks:
+                L.check(self._fn("masks")(self._h, n, L.ptr(self._ws), self._ws.numel(), L.ptr(masks[s:]), st))
+        return logits, masks
+
+    @torch.no_grad()
+    def __call__(self, pixel_values=None, **_ignored):
+        """``reward_model(**inputs)`` with the processor's ``pixel_values`` [B,3,size,size] -> see ``_SegOutput``"""
+        if pixel_values is None:
+            raise ValueError("You have to specify pixel_values")
+        L.require_cuda(pixel_values, "pixel_values")
+        return _SegOutput((self._run(self.pixel_values_to_patches(pixel_values), True, False)[0],))
+
+    def logits_and_masks(self, images):
+        """[B,3,H,H] in [0,1] -> (logits [B, num_labels, g, g] fp32, masks [B, g, g] int32) of one pass"""
+        return self._run(self.preprocess(images), True, True)
+
+    def masks(self, images):
+        """[B,3,H,H] in [0,1] -> the class masks [B, size / 4, size / 4] int32 (argmax of the logits, a tie to the lowest class): the whole per-image path of
+        the reward up to the comparison"""
+        return self._run(self.preprocess(images), False, True)[1]
+
+
+def mask_agreement(pred_masks, target_masks):
+    """int32 masks [B,h,w] x ([B,h,w] or [1,h,w]) -> 100 * mean(pred == target) per sample, [B,1] fp32"""
+    L.require_cuda(pred_masks, "pred_masks")
+    a, b = pred_masks.to(torch.int32).contiguous(), target_masks.to(torch.int32).contiguous()
+    B = a.shape[0]
+    if b.shape[0] not in (B, 1) or b.shape[1:] != a.shape[1:]:
+        raise ValueError(f"mask shapes {tuple(a.shape)} vs {tuple(b.shape)}")
+    n = a[0].numel() if B else 0
+    out = torch.empty(B, 1, dtype=torch.float32, device=a.device)
+    if B:
+        L.check(L.lib().cs_seg_agreement(L.ptr(a), L.ptr(b), n if (b.shape[0] == B and B > 1) else 0, B, n, L.ptr(out), L.stream_ptr(a.device)))
+    return out
+
+
 def load_dino_reward(device="cuda:0", config=None):
     """edit_ppo/reward_model.py:59-64 without the hub: the dinov2-base shapes and processor constants; the caller loads the weights."""
     processor = DinoImageProcessor()
@@ -355,9 +477,18 @@ def load_depth_reward(device="cuda:0", config=None):
     return HipDepthAnythingModel(cfg, device=device, processor=processor), processor
 
 
+def load_segmentation_reward(device="cuda:0", config=None):
+    """edit_ppo/reward_model.py:110-117 without the hub: the segformer-b4-finetuned-ade-512-512 shapes and processor constants; the caller loads the weights."""
+    cfg = dict(SEGFORMER_B4_ADE_CONFIG)
+    cfg.update(config or {})
+    processor = SegImageProcessor({"height": cfg["image_size"], "width": cfg["image_size"]})
+    return HipSegformerModel(cfg, device=device, processor=processor), processor
+
+
 def load_reward_model(reward_type, device="cuda:0", config=None):
-    """edit_ppo/reward_model.py:25-57.  ``image_psnr`` needs no model; ``dino`` and ``clip`` are built here; ``depth`` is built but loaded through
-    ``load_depth_reward`` (this dispatcher's answer for it is pinned by the existing tests); the other backbones are not implemented."""
+    """edit_ppo/reward_model.py:25-57.  ``image_psnr`` needs no model; ``dino`` and ``clip`` are built here; ``depth`` and ``segmentation`` are built but
+    loaded through ``load_depth_reward`` / ``load_segmentation_reward`` (this dispatcher's answers for them are pinned by the existing tests); the other
+    backbones are not implemented."""
     if reward_type == "image_psnr":
         return None, None
     if reward_type == "dino":
@@ -366,7 +497,9 @@ def load_reward_model(reward_type, device="cuda:0", config=None):
         return load_clip_reward(device, config)
     if reward_type == "depth":
         raise NotImplementedError("reward_type 'depth' is not loaded through this dispatcher yet: use load_depth_reward(device, config)")
-    if reward_type in ("inception", "segmentation", "llava", "qwen_vl"):
+    if reward_type == "segmentation":
+        raise NotImplementedError("reward_type 'segmentation' is not loaded through this dispatcher yet: use load_segmentation_reward(device, config)")
+    if reward_type in ("inception", "llava", "qwen_vl"):
         raise NotImplementedError(f"reward_type '{reward_type}' needs a third-party backbone network that is not implemented")
     raise ValueError(f"Unknown reward_type: {reward_type}")
 
@@ -435,3 +568,13 @@ def calculate_depth_reward(reward_model, reward_model_processor, model_pred, tar
         target_maps = target_maps.expand(pred_maps.shape[0], -1, -1)
     from .ppo import depth_psnr_tail
     return depth_psnr_tail(pred_maps, target_maps)
+
+
+def calculate_segmentation_reward(reward_model, reward_model_processor, model_pred, target, device=None):
+    """edit_ppo/reward_model.py:425-481 for the whole batch on the GPU, with the argument forms of ``calculate_dino_reward``: the share of pixels, times
+    100, on which the SegFormer class masks (argmax of the logits at a quarter of the processor's size) of pred and target agree -> rewards [B,1] fp32 in
+    [0, 100].  Any other ``reward_model`` (``None``, a transformers model) raises ``NotImplementedError``: the eager transformers path is not implemented."""
+    if not isinstance(reward_model, HipSegformerModel):
+        raise NotImplementedError("reward_type 'segmentation' needs a HipSegformerModel (load_segmentation_reward(device, config)); the eager transformers "
+                                  "path is not implemented")
+    return mask_agreement(*_paired_image_pass(reward_model, reward_model_processor, model_pred, target, reward_model.masks))

@@ -567,6 +567,62 @@ int cs_depth_forward(CsDepth* d, const void* patches, int batch, float* predicte
  * height x width -> per map (d - min) / (max - min + 1e-8): maps [batch, height, width] fp32 */
 int cs_depth_normalized_maps(CsDepth* d, const float* predicted_depth, int batch, int height, int width, float* maps, void* stream);
 
+/* ------------------------------------------------------------------------
+ * SegFormer mask-agreement reward (reward_type "segmentation": edit_ppo/reward_model.py:110-117, 425-481;
+ * third-party transformers SegformerForSemanticSegmentation + the nvidia/segformer-b4-finetuned-ade-512-512 Segformer image processor).
+ * Every LayerNorm of the model and its BatchNorm use eps = 1e-5 (the torch defaults; config.layer_norm_eps is not read by them).
+ * ---------------------------------------------------------------------- */
+typedef struct CsSegConfig {
+    /* MiT encoder, four stages */
+    int hidden_sizes[4];           /* 64, 128, 320, 512: each 64 or a multiple of 128 or 160 */
+    int depths[4];                 /* 3, 8, 27, 3 */
+    int num_attention_heads[4];    /* 1, 2, 5, 8 (head dim 64 in every stage) */
+    int sr_ratios[4];              /* 8, 4, 2, 1: kernel = stride of the sequence reduction in front of keys / values (1: none) */
+    int mlp_ratio;                 /* 4 */
+    /* all-MLP head */
+    int decoder_hidden_size;       /* 768 */
+    int num_labels;                /* 150 */
+    /* the processor's constants */
+    int size;                      /* 512: PIL BILINEAR resize to size x size (square inputs only), a multiple of 32 */
+    float image_mean[3];           /* 0.485, 0.456, 0.406 */
+    float image_std[3];            /* 0.229, 0.224, 0.225 */
+    double rescale_factor;         /* 1 / 255 */
+} CsSegConfig;
+
+typedef struct CsSeg CsSeg;
+
+/* host only: builds the weight manifest, touches no GPU */
+int cs_seg_create(const CsSegConfig* cfg, CsSeg** out);
+void cs_seg_destroy(CsSeg* g);
+/* tensors by their transformers SegformerForSemanticSegmentation state-dict names ("segformer.stages.0.patch_embeddings.proj.weight", ...,
+ * "decode_head.classifier.bias"); fp32 host memory.  "decode_head.batch_norm.num_batches_tracked" (0-d: ndim 0) is accepted and ignored */
+int cs_seg_set_weight(CsSeg* g, const char* name, const float* data_host, const int64_t* shape, int ndim);
+int cs_seg_num_weights(const CsSeg* g);
+const char* cs_seg_weight_name(const CsSeg* g, int i, int64_t* shape4, int* ndim);
+int cs_seg_finalize(CsSeg* g);
+size_t cs_seg_workspace_bytes(const CsSeg* g, int batch);
+double cs_seg_flops(const CsSeg* g, int batch);
+/* row length of the front end's output (one pixel per row: 3 channels zero-padded to 8 halfs) and stage-1 tokens per image ((size / 4)^2) */
+int cs_seg_patch_cols(const CsSeg* g);
+int cs_seg_num_tokens(const CsSeg* g);
+size_t cs_seg_preprocess_workspace_bytes(const CsSeg* g, int batch, int height, int width);
+/* the image front end of cs_vit_preprocess with the Segformer processor's rule: the whole image resized to size x size with PIL BILINEAR, no crop; `patches`
+ * is the normalised image [batch * size * size][8] fp16 (NHWC, channels 3 .. 7 zero).  height != width: CS_E_UNSUPPORTED.  crop_u8 (may be NULL): the resized
+ * uint8 image [batch, 3, size, size] (an input of the processor's own size comes out byte-identical) */
+int cs_seg_preprocess(CsSeg* g, const void* images, int dtype, int batch, int height, int width, void* patches,
+                      unsigned char* crop_u8, void* workspace, size_t workspace_bytes, void* stream);
+/* patches from cs_seg_preprocess -> logits [batch, num_labels, size / 4, size / 4] fp32 (NULL: not written; the fp16 logits stay in the workspace for cs_seg_masks) */
+int cs_seg_forward(CsSeg* g, const void* patches, int batch, float* logits, void* workspace, size_t workspace_bytes,
+                   void* stream);
+/* timing tools: cs_seg_forward returns after `parts` of (stage 1, 2, 3, 4, head); 5 (the default) runs everything, less leaves logits and masks undefined */
+int cs_seg_set_stage_limit(CsSeg* g, int parts);
+/* argmax over the classes of the logits the last cs_seg_forward of this batch size left in `workspace` (a tie goes to the lowest class): masks
+ * [batch, size / 4, size / 4] int32 */
+int cs_seg_masks(CsSeg* g, int batch, const void* workspace, size_t workspace_bytes, int* masks, void* stream);
+/* the reward's tail: out[b] = 100 * mean(pred[b] == target[b]) fp32 over n pixels; int32 device masks, target rows target_stride ints apart (0: one target
+ * shared by the batch) */
+int cs_seg_agreement(const int* pred, const int* target, int64_t target_stride, int batch, int64_t n, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -312,6 +312,22 @@ int cs_op_dpt_bicubic(const float* x, int B, int Hi, int Wi, int Ho, int Wo, flo
 /* x [B][n] fp32 <- (x - min) / (max - min + 1e-8) per map, in place */
 int cs_op_dpt_minmax_normalize(float* x, int B, int64_t n, void* stream);
 
+/* the kernels of the SegFormer segmentation reward (csrc/seg_ops.hip), NHWC fp16 device pointers unless noted; fp32 arithmetic, one rounding:
+ * out [B][H][W][C] = gelu_erf(depthwise 3x3 conv (pad 1) of x + bias): w [9][C] (tap ky * 3 + kx major), bias [C] or NULL; C a multiple of 64 up to 2048 */
+int cs_op_seg_dwconv_gelu(const void* x, int B, int H, int W, int C, const void* w, const void* bias, void* out, void* stream);
+/* rows of a k x k conv (stride, pad) over the first C channels of x [B][H][W][Cs] in F.unfold order: out [B * Ho * Wo][Kp], column c k k + ky k + kx, zero padded */
+int cs_op_seg_im2col(const void* x, int B, int H, int W, int Cs, int C, int k, int stride, int pad, int Kp, void* out, void* stream);
+/* rows of a kernel = stride = sr conv: out [B * (H / sr) * (W / sr)][sr * sr * C], column (ky * sr + kx) * C + c; C % 8 == 0 */
+int cs_op_seg_patchify(const void* x, int B, int H, int W, int C, int sr, void* out, void* stream);
+/* bilinear, align_corners = False: x [B][Hi][Wi][C] into the columns col .. col + C of out [B * Ho * Wo][ld]; C, col, ld multiples of 8 */
+int cs_op_seg_bilinear(const void* x, int B, int Hi, int Wi, int C, int Ho, int Wo, void* out, int64_t ld, int col, void* stream);
+/* out [M] int32 = argmax over the first n columns of x [M][ld]; a tie goes to the lowest index */
+int cs_op_seg_argmax(const void* x, int64_t M, int64_t ld, int n, int* out, void* stream);
+/* x [B * HW][ld] -> out [B][n][HW] fp32 (the first n columns) */
+int cs_op_seg_logits(const void* x, int B, int64_t HW, int64_t ld, int n, float* out, void* stream);
+/* x [n] <- max(x, 0) in place; n % 8 == 0 */
+int cs_op_seg_relu(void* x, int64_t n, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -4,6 +4,7 @@ medians of ``--reps`` runs after ``--warmup``; one JSON line at the end.
     python tools/bench_reward.py --reward dino  [--batch 80] [--reps 7] [--no-vae] [--out profiles/dino_reward_bench.txt]
     python tools/bench_reward.py --reward clip  [--batch 16] [--reps 7] [--out profiles/clip_reward_bench.txt]
     python tools/bench_reward.py --reward depth [--batch 8]  [--reps 7] [--out profiles/depth_reward_bench.txt]
+    python tools/bench_reward.py --reward segmentation [--batch 4] [--reps 7] [--out profiles/segmentation_reward_bench.txt]
 
 * ``dino`` (config 5's batch, 80 + 80 images): front end (quantise + PIL-exact resize + crop + normalise + patch rows), encoder (12 layers, 257 tokens per
   image), tail (normalise, cosine, scale) and, in the same process, the VAE decode of those 160 images for scale.
@@ -11,6 +12,9 @@ medians of ``--reps`` runs after ``--warmup``; one JSON line at the end.
   fraction of the fp16 MFMA peak from ``flops()``, the tail.
 * ``depth``: front end (resize to 518 x 518), model (DINOv2-small backbone at 1370 tokens tapped four times, DPT neck and head), post-processing (bicubic to
   512 x 512, min / max normalisation), tail (PSNR) and the whole ``calculate_depth_reward`` call.
+* ``segmentation``: front end (bilinear resize to 512 x 512: the identity at this size), the MiT-B4 encoder stage by stage (the forward stopped after 1 .. 4
+  stages, differenced), the head, argmax + agreement, the whole ``calculate_segmentation_reward`` call; and the depthwise 3x3 + GELU kernel alone at the
+  stage-1 shape with the bytes it must move (input + output once) over its time, next to the HBM copy rate of the micro-architecture guide.
 """
 import argparse
 import json
@@ -22,11 +26,14 @@ import torch
 
 from consolver_amd import synth
 from consolver_amd.ppo import depth_psnr_tail
-from consolver_amd.reward_model import calculate_depth_reward, cosine_reward, load_depth_reward, load_reward_model
+from consolver_amd import _lib as L
+from consolver_amd.reward_model import (calculate_depth_reward, calculate_segmentation_reward, cosine_reward, load_depth_reward, load_reward_model,
+                                        load_segmentation_reward, mask_agreement)
 
 DEV = "cuda:0"
 PEAK_F16_TFLOPS = 2500.0
-DEFAULT_BATCH = {"dino": 80, "clip": 16, "depth": 8}
+HBM_COPY_TBS = 6.29                # measured float4 copy rate of the MI355X (8.0 TB/s spec)
+DEFAULT_BATCH = {"dino": 80, "clip": 16, "depth": 8, "segmentation": 4}
 
 
 def timed(fn, warmup, reps):
@@ -102,10 +109,54 @@ def bench_depth(a, res, B, n):
             f"  calculate_depth_reward, whole call {res['reward_call_ms']:9.3f} ms"]
 
 
+def bench_segmentation(a, res, B, n):
+    model, proc = load_segmentation_reward(device=DEV)
+    model.load_state_dict(synth.synthetic_segformer_state_dict(model.manifest()))
+    images = random_images(a, n)
+    patches = model.preprocess(images)
+    _, masks = model._run(patches, False, True)
+    lib = L.lib()
+    res["max_batch"] = model.max_batch
+    res["front_end_ms"] = timed(lambda: model.preprocess(images), a.warmup, a.reps)
+    upto = []
+    try:
+        for parts in range(1, 6):                      # the forward stopped after stage 1 .. 4, then with the head
+            L.check(lib.cs_seg_set_stage_limit(model._h, parts))
+            upto.append(timed(lambda: model._run(patches, False, False), a.warmup, a.reps))
+    finally:
+        L.check(lib.cs_seg_set_stage_limit(model._h, 5))
+    for i in range(4):
+        res[f"stage{i + 1}_ms"] = upto[i] - (upto[i - 1] if i else 0.0)
+    res["head_ms"] = upto[4] - upto[3]
+    res["model_ms"] = upto[4]
+    res["argmax_agreement_ms"] = timed(lambda: (model._run(patches, False, True), mask_agreement(masks[:B], masks[B:])), a.warmup, a.reps) - upto[4]
+    res["reward_call_ms"] = timed(lambda: calculate_segmentation_reward(model, proc, images[:B], images[B:], DEV), a.warmup, a.reps)
+    res["model_tflop"] = model.flops(n) / 1e12
+    res["model_tflops"] = model.flops(n) / res["model_ms"] / 1e9
+    res["workspace_mb_per_image"] = int(model._fn("workspace_bytes")(model._h, 1)) / 1e6
+    # the depthwise 3x3 + GELU kernel alone at the stage-1 shape: [n][size / 4][size / 4][4 * 64] halfs in, the same out
+    g, C = a.size // 4, 4 * model.config["hidden_sizes"][0]
+    x = torch.randn(n, g, g, C, device=DEV, dtype=torch.float16)
+    w, bias, out = torch.randn(9, C, device=DEV, dtype=torch.float16) / 3, torch.randn(C, device=DEV, dtype=torch.float16), torch.empty_like(x)
+    st = L.stream_ptr(DEV)
+    res["dwconv_stage1_ms"] = timed(lambda: L.check(lib.cs_op_seg_dwconv_gelu(L.ptr(x), n, g, g, C, L.ptr(w), L.ptr(bias), L.ptr(out), st)), a.warmup, a.reps)
+    res["dwconv_stage1_mbytes"] = 2 * x.numel() * 2 / 1e6
+    res["dwconv_stage1_tbs"] = res["dwconv_stage1_mbytes"] / res["dwconv_stage1_ms"] / 1e3
+    res["hbm_copy_tbs"] = HBM_COPY_TBS
+    return [f"  front end     {res['front_end_ms']:9.3f} ms"] + [f"  stage {i + 1}       {res[f'stage{i + 1}_ms']:9.3f} ms" for i in range(4)] + [
+        f"  head          {res['head_ms']:9.3f} ms",
+        f"  model         {res['model_ms']:9.3f} ms  ({res['model_tflop']:.2f} TFLOP, {res['model_tflops']:.0f} TFLOP/s)",
+        f"  argmax + agreement {res['argmax_agreement_ms']:9.3f} ms",
+        f"  calculate_segmentation_reward, whole call {res['reward_call_ms']:9.3f} ms",
+        f"  depthwise 3x3 + GELU alone, [{n}][{g}][{g}][{C}]: {res['dwconv_stage1_ms']:.4f} ms for {res['dwconv_stage1_mbytes']:.1f} MB in + out = "
+        f"{res['dwconv_stage1_tbs']:.2f} TB/s (HBM copy rate of the micro-architecture guide: {HBM_COPY_TBS} TB/s measured, 8.0 spec; a tensor of this size can "
+        f"stay in the 256 MB Infinity Cache between two calls)"]
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reward", choices=sorted(DEFAULT_BATCH), required=True)
-    ap.add_argument("--batch", type=int, default=None, help="pred / target pairs (default: 80 dino, 16 clip, 8 depth)")
+    ap.add_argument("--batch", type=int, default=None, help="pred / target pairs (default: 80 dino, 16 clip, 8 depth, 4 segmentation)")
     ap.add_argument("--size", type=int, default=512)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--reps", type=int, default=7)
@@ -115,8 +166,8 @@ def main():
     B = a.batch if a.batch is not None else DEFAULT_BATCH[a.reward]
     n = 2 * B
     res = {"batch_pairs": B, "images": n, "size": a.size}
-    stages = (bench_depth if a.reward == "depth" else bench_features)(a, res, B, n)
-    model_name = ", ViT-L/14" if a.reward == "clip" else ""
+    stages = {"depth": bench_depth, "segmentation": bench_segmentation}.get(a.reward, bench_features)(a, res, B, n)
+    model_name = {"clip": ", ViT-L/14", "segmentation": ", SegFormer-B4"}.get(a.reward, "")
     lines = [f"{a.reward} reward, {n} images ({B} pred + {B} target) at {a.size}^2 fp16{model_name}, synthetic weights, medians of {a.reps}"] + stages
     lines.append(json.dumps(res))
     text = "\n".join(lines)
