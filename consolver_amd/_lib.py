@@ -82,6 +82,10 @@ class CsSegConfig(C.Structure):
                 ("rescale_factor", C.c_double)]
 
 
+class CsIncepConfig(C.Structure):
+    _fields_ = [("image_size", C.c_int), ("num_classes", C.c_int), ("image_mean", C.c_float * 3), ("image_std", C.c_float * 3), ("rescale_factor", C.c_double)]
+
+
 class CsGemm2Problem(C.Structure):
     _fields_ = [("x", C.c_void_p), ("M", C.c_int), ("K", C.c_int), ("w", C.c_void_p), ("bias", C.c_void_p), ("N", C.c_int),
                 ("res", C.c_void_p), ("gate", C.c_void_p), ("gate_stride", C.c_long), ("rows_per_sample", C.c_int), ("act", C.c_int),
@@ -281,10 +285,16 @@ SYMBOLS = {
     "cs_op_seg_argmax": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_void_p, C.c_void_p]),
     "cs_op_seg_logits": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_void_p, C.c_void_p]),
     "cs_op_seg_relu": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p]),
+    "cs_incep_set_stage_limit": (C.c_int, [C.c_void_p, C.c_int]),
+    "cs_op_incep_conv": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                   C.c_void_p, C.c_int64, C.c_int, C.c_void_p]),
+    "cs_op_incep_maxpool": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_void_p]),
+    "cs_op_incep_avgpool": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "cs_op_incep_head": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 # the image-tower handle families (csrc/image_tower.h) declare the same 13 entry points, each over its own config struct
-for _prefix, _config in (("vit", CsVitConfig), ("clipv", CsClipVisionConfig), ("depth", CsDepthConfig), ("seg", CsSegConfig)):
+for _prefix, _config in (("vit", CsVitConfig), ("clipv", CsClipVisionConfig), ("depth", CsDepthConfig), ("seg", CsSegConfig), ("incep", CsIncepConfig)):
     SYMBOLS.update({
         f"cs_{_prefix}_create": (C.c_int, [C.POINTER(_config), C.POINTER(C.c_void_p)]),
         f"cs_{_prefix}_destroy": (None, [C.c_void_p]),

@@ -36,6 +36,8 @@ SOURCES = {
     "depth.cpp": [],
     "seg_ops.hip": [],
     "segformer.cpp": [],
+    "incep_ops.hip": [],
+    "inception.cpp": [],
     "ppo.hip": [],
     "ops_api.cpp": [],
 }

@@ -15,6 +15,13 @@ namespace image_front_end {
 // one pass of PIL's ImagingResample (BICUBIC: Keys cubic a = -0.5, support 2 * max(scale, 1); BILINEAR: the triangle filter, support max(scale, 1)) for output
 // indices win0 .. win0 + win: taps normalised in double, converted as int(+-0.5 + k 2^22)
 enum Filter { PIL_BILINEAR = 2, PIL_BICUBIC = 3 };          // PIL.Image.Resampling values
+// where the center crop's window starts in a resized side of n: transformers' (n - C) / 2, or torchvision's int(round((n - C) / 2.0)) with Python's
+// round-half-to-even (they differ when n - C = 3 (mod 4): 39 -> 19 | 20)
+enum CropRule { CROP_FLOOR = 0, CROP_ROUND_HALF_EVEN = 1 };
+inline int crop_offset(int n, int C, CropRule rule) {
+    const int d = n - C, k = d / 2;
+    return (rule == CROP_ROUND_HALF_EVEN && (d & 1) && (k & 1)) ? k + 1 : k;
+}
 struct Taps { std::vector<int> lo, cnt, kk; int ksize; };
 inline double pil_cubic(double x) {
     const double a = -0.5;
@@ -59,6 +66,7 @@ struct Plan { VitResizePlan dev; };
 struct PlanCache {
     static constexpr size_t MAX_PLANS = 16;
     Filter filter = PIL_BICUBIC;                            // the processor's resample (set once, before the first plan)
+    CropRule crop_rule = CROP_FLOOR;                        // the processor's center-crop offset (set once, next to filter)
     std::map<std::pair<int, int>, Plan> plans;
     std::vector<void*> plan_allocs;
 
@@ -71,7 +79,7 @@ struct PlanCache {
         const int shrt = std::min(H, W), lng = std::max(H, W), nl = (int)((double)((int64_t)edge * lng) / shrt);
         const int nh = H <= W ? edge : nl, nw = H <= W ? nl : edge;
         if (nh < C || nw < C) CS_FAIL(CS_E_UNSUPPORTED, "%s: resized image %d x %d is smaller than the %d crop (the processor would pad)", who, nh, nw, C);
-        const Taps th = pil_taps(W, nw, (nw - C) / 2, C, filter), tv = pil_taps(H, nh, (nh - C) / 2, C, filter);
+        const Taps th = pil_taps(W, nw, crop_offset(nw, C, crop_rule), C, filter), tv = pil_taps(H, nh, crop_offset(nh, C, crop_rule), C, filter);
         Plan p{};
         int row0 = H, row1 = 0, col0 = W, col1 = 0;
         for (int i = 0; i < C; ++i) {

@@ -330,3 +330,21 @@ int launch_seg_argmax(const f16* x, long M, long ld, int n, int* out, hipStream_
 int launch_seg_logits(const f16* x, int B, long HW, long ld, int n, float* out, hipStream_t s);
 // out[b] = 100 * mean(pred[b][i] == target[b * target_stride + i], i < n) in fp32; target_stride 0 shares one target
 int launch_seg_agreement(const int* pred, const int* target, long target_stride, int B, long n, float* out, hipStream_t s);
+
+// ---- Inception-v3 reward (incep_ops.hip / inception.cpp): the general convolution, the pools and the head -------------------------------------------------
+// implicit-GEMM convolution on the matrix cores: NHWC fp16 x [B][H][W][Cin] (Cin % 8 == 0; channels creal .. Cin of a pixel are never used: the front end's
+// 8-channel rows carry 3), w [Cout][kh * kw][Cin] with zeros in those channels, Cout % 16 == 0, stride 1 | 2, any pads, any H x W that holds one window.
+// out[m][col + n] = relu(conv + bias[n]) in fp32, one rounding; rows of ld halfs, only the columns col .. col + Cout are written (the concat slice).
+struct IncepConvArgs {
+    const f16* x; int B, H, W, Cin, creal;
+    const f16* w; const float* bias; int Cout, kh, kw, stride, pad_h, pad_w;
+    f16* out; long ld; int col;
+};
+int launch_incep_conv(const IncepConvArgs& a, hipStream_t s);
+inline int incep_out_size(int n, int k, int stride, int pad) { return (n + 2 * pad - k) / stride + 1; }
+// max pool 3x3 stride 2 pad 0 of x [B][H][W][C] into the columns col .. col + C of out [B * Ho * Wo][ld]; C, col, ld multiples of 8
+int launch_incep_maxpool(const f16* x, int B, int H, int W, int C, f16* out, long ld, int col, hipStream_t s);
+// average pool 3x3 stride 1 pad 1 that divides by 9 everywhere (count_include_pad): the sum in fp32, one rounding; C % 8 == 0; out must not alias x
+int launch_incep_avgpool(const f16* x, int B, int H, int W, int C, f16* out, hipStream_t s);
+// mean [B][C] fp32 over the HW positions of x [B][HW][C], then logits [B][N] = mean w^T + bias (w fp16 [N][C], bias fp32 [N]): the mean is never rounded to fp16
+int launch_incep_head(const f16* x, int B, long HW, int C, const f16* w, const float* bias, int N, float* mean, float* logits, hipStream_t s);

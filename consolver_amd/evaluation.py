@@ -5,8 +5,8 @@ Mirrors, by name and output schema:
 * compute_reward.py:52-78 ``find_image_pairs``, :81-95 ``load_image_tensor``, :332-365 ``calculate_statistics``,
   :447-462 the results JSON (``statistics`` / ``raw_scores`` / ``config``).
 Scored on the GPU: the arithmetic-only reward (``image_psnr``, edit_ppo/reward_model.py:484-509; cs_image_psnr) and, given a model,
-the DINOv2 and CLIP image-similarity rewards (``dino``, :217-257; ``clip``, :512-552), the depth-map PSNR (``depth``, :359-422) and the SegFormer mask
-agreement (``segmentation``, :425-481; all in consolver_amd/reward_model.py).  The other backbone rewards are third-party networks that are not implemented.  PNG encode/decode is PIL (host I/O).
+the DINOv2 and CLIP image-similarity rewards (``dino``, :217-257; ``clip``, :512-552), the depth-map PSNR (``depth``, :359-422), the SegFormer mask
+agreement (``segmentation``, :425-481) and the Inception-v3 logit cosine (``inception``, :319-356; all in consolver_amd/reward_model.py).  The chat-model rewards (llava, qwen_vl) are not implemented.  PNG encode/decode is PIL (host I/O).
 """
 import json
 import os
@@ -74,8 +74,8 @@ def calculate_statistics(results):
 
 def score_image_pairs(image_pairs, reward_types=("image_psnr",), batch_size=16, device="cuda:0", reward_models=None):
     """-> {reward_type: [score per pair]} (compute_reward.py:98-330).  ``reward_models``: {reward_type: (model, processor)} as returned by
-    ``reward_model.load_reward_model`` / ``load_depth_reward`` / ``load_segmentation_reward`` for the rewards that need a network ("dino", "clip", "depth",
-    "segmentation")."""
+    ``reward_model.load_reward_model`` / ``load_depth_reward`` / ``load_segmentation_reward`` / ``load_inception_reward`` for the rewards that need a network ("dino", "clip", "depth",
+    "segmentation", "inception")."""
     results = {}
     reward_models = reward_models or {}
     for rt in reward_types:

@@ -8,13 +8,14 @@ step, with the reference's names:
   image-similarity reward the reference's run scripts train with) and ``"clip"`` (:512-552, CLIP ViT-L/14 image features;
   both in consolver_amd/reward_model.py) and ``"depth"`` (:359-422, the Depth Anything depth-map PSNR the reference's config defaults to; given a
   ``HipDepthAnythingModel`` from ``reward_model.load_depth_reward``) and ``"segmentation"`` (:425-481, SegFormer-B4 mask agreement; given a
-  ``HipSegformerModel`` from ``reward_model.load_segmentation_reward``).  The other backbone rewards (inception / llava / qwen_vl) are
-  third-party networks that are not implemented; they raise.
+  ``HipSegformerModel`` from ``reward_model.load_segmentation_reward``) and ``"inception"`` (:319-356, Inception-v3 logit cosine; given a
+  ``HipInceptionV3`` from ``reward_model.load_inception_reward``).  The other backbone rewards (llava / qwen_vl) are
+  third-party chat models that are not implemented; they raise.
 * ``compute_advantages`` = train_ppo.py:376-390, ``ppo_loss`` = :408-421 (value), ``PolicyTrainer`` = the
   optimisation step :404-437 (gradients, clip_grad_norm_, AdamW) and the checkpoint format.
 * ``collect_rollout`` = :352-403 for one batch of teacher pairs.
 
-Everything runs in the HIP library (cs_image_psnr / cs_vit_* / cs_clipv_* / cs_depth_* / cs_seg_* / cs_ppo_advantages / cs_ppo_loss); there is no
+Everything runs in the HIP library (cs_image_psnr / cs_vit_* / cs_clipv_* / cs_depth_* / cs_seg_* / cs_incep_* / cs_ppo_advantages / cs_ppo_loss); there is no
 CPU fallback.
 """
 import ctypes as C
@@ -63,7 +64,7 @@ def depth_psnr_tail(pred_depth, target_depth):
 
 # reward types computed by a model of reward_model.py -> its function there
 _MODEL_REWARDS = {"dino": "calculate_dino_reward", "clip": "calculate_clip_reward", "depth": "calculate_depth_reward",
-                  "segmentation": "calculate_segmentation_reward"}
+                  "segmentation": "calculate_segmentation_reward", "inception": "calculate_inception_reward"}
 
 
 def calculate_reward(reward_type, reward_model, reward_model_processor, model_pred, target, device=None):

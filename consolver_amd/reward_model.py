@@ -31,6 +31,12 @@ and a ``SegImageProcessor``; ``calculate_segmentation_reward`` runs the front en
 uint8 image), the MiT-B4 encoder and the all-MLP head (cs_seg_forward), the class argmax at a quarter of the processor's size (cs_seg_masks) and the
 agreement tail 100 * mean(mask_pred == mask_target) (cs_seg_agreement).  Weights load under their ``transformers.SegformerForSemanticSegmentation`` names.
 The fp32 restatement lives in tests/segformer_oracle.py.
+
+``inception`` (:98-108, :319-356): ``load_inception_reward()`` -> a ``HipInceptionV3`` (torchvision ``inception_v3`` in eval mode; AuxLogits is never
+evaluated) and an ``InceptionImageProcessor``; ``calculate_inception_reward`` runs the front end (torchvision's ``Resize(299, BICUBIC)`` +
+``CenterCrop(299)`` with its round-half-even offset, any aspect ratio, bit-identical on the uint8 image), the 94 BatchNorm-folded convolutions on one
+implicit-GEMM MFMA kernel with the pools and the fp32 head (cs_incep_forward) and the cosine tail on the [B,1000] logits of ``fc``.  Weights load under
+their torchvision names.  The fp32 restatement lives in tests/inception_oracle.py.
 """
 import ctypes as C
 
@@ -50,6 +56,8 @@ DEPTH_ANYTHING_V2_SMALL_CONFIG = dict(hidden_size=384, num_hidden_layers=12, num
 # nvidia/segformer-b4-finetuned-ade-512-512 (its config.json, from memory: no hub access here): MiT-B4 + the all-MLP head over the 150 ADE20K classes
 SEGFORMER_B4_ADE_CONFIG = dict(hidden_sizes=(64, 128, 320, 512), depths=(3, 8, 27, 3), num_attention_heads=(1, 2, 5, 8), sr_ratios=(8, 4, 2, 1), mlp_ratio=4,
                                decoder_hidden_size=768, num_labels=150, image_size=512)
+# torchvision inception_v3 (the widths are the architecture's); image_size is the reference's Resize / CenterCrop edge
+INCEPTION_V3_CONFIG = dict(image_size=299, num_classes=1000)
 _DT = {torch.float32: L.CS_F32, torch.float16: L.CS_F16}
 
 
@@ -443,6 +451,55 @@ class HipSegformerModel(_HipImageModel):
         return self._run(self.preprocess(images), False, True)[1]
 
 
+class InceptionImageProcessor:
+    """The reference's torchvision transform for the inception reward (edit_ppo/reward_model.py:98-108): ``Resize(size, BICUBIC)`` (shortest edge),
+    ``CenterCrop(size)`` (window at ``int(round((n - size) / 2.0))``, round half to even), ``ToTensor``, ``Normalize`` with the ImageNet mean / std.  A plain
+    holder: the arithmetic runs in ``HipInceptionV3.preprocess`` (any aspect ratio)."""
+    do_resize = do_center_crop = do_rescale = do_normalize = True
+    resample = 3                                   # PIL.Image.BICUBIC
+
+    def __init__(self, size=299, rescale_factor=1 / 255, image_mean=(0.485, 0.456, 0.406), image_std=(0.229, 0.224, 0.225)):
+        self.size = int(size)
+        if not 75 <= self.size <= 2048:
+            raise ValueError("Inception-v3 needs an image edge of 75 .. 2048")
+        self.rescale_factor, self.image_mean, self.image_std = float(rescale_factor), tuple(image_mean), tuple(image_std)
+
+    def constants(self):
+        return (self.size, self.size, self.rescale_factor, self.image_mean, self.image_std)
+
+
+class HipInceptionV3(_HipImageEncoder):
+    """torchvision ``inception_v3(aux_logits=True, transform_input=False).eval()``.  ``model(pixel_values)`` -> the logits of ``fc`` [B, num_classes] fp32 is
+    the call the reference makes (its comment says features; the tensor is the logits); ``image_features(images)`` runs the transform on the GPU as well.
+    ``AuxLogits.*`` tensors of a checkpoint are ignored by ``load_state_dict``."""
+    workspace_budget = 1024 << 20         # bytes of workspace one call may take: max_batch is sized from it (299: 5.4 MB per image)
+    _prefix = "incep"
+
+    def __init__(self, config=None, device="cuda:0", processor=None):
+        cfg = dict(INCEPTION_V3_CONFIG)
+        cfg.update(config or {})
+        self.config = cfg
+        self.device = torch.device(device)
+        self.processor = processor or InceptionImageProcessor(cfg["image_size"])
+        size, _, rescale, mean, std = self.processor.constants()
+        if size != cfg["image_size"]:
+            raise ValueError(f"the processor resizes to {size}, the model was configured for {cfg['image_size']}")
+        c = L.CsIncepConfig(size, cfg["num_classes"], (C.c_float * 3)(*mean), (C.c_float * 3)(*std), rescale)
+        h = C.c_void_p()
+        L.check(L.lib().cs_incep_create(C.byref(c), C.byref(h)))
+        self._init_handle(h, size, 1)
+        self._feature_dim = cfg["num_classes"]
+        self.max_batch = max(1, min(_HipImageModel.max_batch, self.workspace_budget // int(self._fn("workspace_bytes")(h, 1))))
+
+    @torch.no_grad()
+    def __call__(self, pixel_values=None, **_ignored):
+        """``reward_model(img_tensor)`` with the transform's output [B,3,size,size] -> logits [B, num_classes] fp32"""
+        if pixel_values is None:
+            raise ValueError("You have to specify pixel_values")
+        L.require_cuda(pixel_values, "pixel_values")
+        return self.encode_patches(self.pixel_values_to_patches(pixel_values))
+
+
 def mask_agreement(pred_masks, target_masks):
     """int32 masks [B,h,w] x ([B,h,w] or [1,h,w]) -> 100 * mean(pred == target) per sample, [B,1] fp32"""
     L.require_cuda(pred_masks, "pred_masks")
@@ -485,10 +542,18 @@ def load_segmentation_reward(device="cuda:0", config=None):
     return HipSegformerModel(cfg, device=device, processor=processor), processor
 
 
+def load_inception_reward(device="cuda:0", config=None):
+    """edit_ppo/reward_model.py:98-108 without the hub: torchvision's Inception-v3 shapes and the reference's transform constants; the caller loads the weights."""
+    cfg = dict(INCEPTION_V3_CONFIG)
+    cfg.update(config or {})
+    processor = InceptionImageProcessor(cfg["image_size"])
+    return HipInceptionV3(cfg, device=device, processor=processor), processor
+
+
 def load_reward_model(reward_type, device="cuda:0", config=None):
-    """edit_ppo/reward_model.py:25-57.  ``image_psnr`` needs no model; ``dino`` and ``clip`` are built here; ``depth`` and ``segmentation`` are built but
-    loaded through ``load_depth_reward`` / ``load_segmentation_reward`` (this dispatcher's answers for them are pinned by the existing tests); the other
-    backbones are not implemented."""
+    """edit_ppo/reward_model.py:25-57.  ``image_psnr`` needs no model; ``dino`` and ``clip`` are built here; ``depth``, ``segmentation`` and ``inception`` are
+    built but loaded through ``load_depth_reward`` / ``load_segmentation_reward`` / ``load_inception_reward`` (this dispatcher's answers for them are pinned
+    by the existing tests); the other backbones are not implemented."""
     if reward_type == "image_psnr":
         return None, None
     if reward_type == "dino":
@@ -499,13 +564,17 @@ def load_reward_model(reward_type, device="cuda:0", config=None):
         raise NotImplementedError("reward_type 'depth' is not loaded through this dispatcher yet: use load_depth_reward(device, config)")
     if reward_type == "segmentation":
         raise NotImplementedError("reward_type 'segmentation' is not loaded through this dispatcher yet: use load_segmentation_reward(device, config)")
-    if reward_type in ("inception", "llava", "qwen_vl"):
+    if reward_type == "inception":
+        raise NotImplementedError("reward_type 'inception' is not loaded through this dispatcher yet: use load_inception_reward(device, config)")
+    if reward_type in ("llava", "qwen_vl"):
         raise NotImplementedError(f"reward_type '{reward_type}' needs a third-party backbone network that is not implemented")
     raise ValueError(f"Unknown reward_type: {reward_type}")
 
 
 def cosine_reward(pred_features, target_features):
-    """[B,D] fp32 x ([B,D] or [1,D]) -> (cosine_similarity(normalize(a), normalize(b)) + 1) * 50, [B,1] fp32"""
+    """[B,D] fp32 x ([B,D] or [1,D]) -> (cosine_similarity(normalize(a), normalize(b)) + 1) * 50, [B,1] fp32.  cs_cosine_reward normalises and then takes
+    the cosine (the dino / clip form); that equals a plain ``F.cosine_similarity`` of the raw vectors (the inception form) to fp32 rounding unless a
+    vector's norm is under 1e-8 (where both clamp, differently)."""
     L.require_cuda(pred_features, "pred_features")
     a, b = pred_features.to(torch.float32).contiguous(), target_features.to(torch.float32).contiguous()
     B, D = a.shape
@@ -578,3 +647,14 @@ def calculate_segmentation_reward(reward_model, reward_model_processor, model_pr
         raise NotImplementedError("reward_type 'segmentation' needs a HipSegformerModel (load_segmentation_reward(device, config)); the eager transformers "
                                   "path is not implemented")
     return mask_agreement(*_paired_image_pass(reward_model, reward_model_processor, model_pred, target, reward_model.masks))
+
+
+def calculate_inception_reward(reward_model, reward_model_processor, model_pred, target, device=None):
+    """edit_ppo/reward_model.py:319-356 for the whole batch in one pass, with the argument forms of ``calculate_dino_reward`` and images of any aspect ratio:
+    (cosine_similarity of the Inception-v3 logits of pred and target + 1) * 50 -> rewards [B,1] fp32 in [0, 100].  The tail normalises each logit vector and
+    then takes the cosine (``cosine_reward``): equal to ``F.cosine_similarity`` of the raw logits to fp32 rounding unless a logit vector's norm is under
+    1e-8.  Any other ``reward_model`` (``None``, a torchvision module) raises ``NotImplementedError``: the eager torchvision path is not implemented."""
+    if not isinstance(reward_model, HipInceptionV3):
+        raise NotImplementedError("reward_type 'inception' needs a HipInceptionV3 (load_inception_reward(device, config)); the eager torchvision path is "
+                                  "not implemented")
+    return _feature_cosine_reward(reward_model, reward_model_processor, model_pred, target)

@@ -117,6 +117,33 @@ def synthetic_segformer_state_dict(manifest, seed=20260101):
     return sd
 
 
+def synthetic_inception_state_dict(manifest, seed=20260102):
+    """Inception-v3 (``HipInceptionV3.manifest()``), the SegFormer recipe: conv filters and ``fc.weight`` ~ N(0, 1/fan_in), BatchNorm gains 1 + 0.1 N, biases
+    0.05 N, running_mean 0.1 N, running_var uniform in [0.5, 1.5], ``num_batches_tracked`` an int64 zero.  With these running statistics 94 ReLU layers
+    build up a constant component and the logits hardly depend on the image: tests calibrate the statistics on a batch first
+    (tests/inception_oracle.py ``calibrate_batch_norm``)."""
+    g = torch.Generator().manual_seed(seed)
+    sd = {}
+    for name, shape in manifest:
+        if name.endswith("num_batches_tracked"):
+            w = torch.zeros(shape, dtype=torch.int64)
+        elif name.endswith("running_var"):
+            w = 0.5 + torch.rand(shape, generator=g)
+        elif name.endswith("running_mean"):
+            w = 0.1 * torch.randn(shape, generator=g)
+        elif name.endswith(".weight") and len(shape) >= 2:
+            fan_in = 1
+            for s in shape[1:]:
+                fan_in *= s
+            w = torch.randn(shape, generator=g) * (1.0 / fan_in) ** 0.5
+        elif ".bn." in name and name.endswith(".weight"):
+            w = 1.0 + 0.1 * torch.randn(shape, generator=g)
+        else:
+            w = 0.05 * torch.randn(shape, generator=g)
+        sd[name] = w
+    return sd
+
+
 def synthetic_clip_vision_state_dict(manifest, seed=20251230):
     """CLIP vision tower + projection: matrices (the patch projection included) ~ N(0, 1/fan_in), class and position embeddings 0.5 N, norm gains
     1 + 0.1 N (``pre_layrnorm`` / ``post_layernorm`` / ``layer_norm1|2``), biases 0.05 N."""

@@ -623,6 +623,47 @@ int cs_seg_masks(CsSeg* g, int batch, const void* workspace, size_t workspace_by
  * shared by the batch) */
 int cs_seg_agreement(const int* pred, const int* target, int64_t target_stride, int batch, int64_t n, float* out, void* stream);
 
+/* ------------------------------------------------------------------------
+ * Inception-v3 logit-cosine reward (reward_type "inception": edit_ppo/reward_model.py:98-108, 319-356; third-party torchvision
+ * inception_v3(aux_logits=True, transform_input=False) in eval mode behind Resize(size, BICUBIC) + CenterCrop(size) + ToTensor + Normalize).
+ * The widths are the architecture's; every BatchNorm has eps = 1e-3 and is folded into its convolution at finalize.  AuxLogits is never evaluated.
+ * ---------------------------------------------------------------------- */
+typedef struct CsIncepConfig {
+    int image_size;                /* 299: the resize's shortest edge and the center crop (75 .. 2048) */
+    int num_classes;               /* 1000 */
+    float image_mean[3];           /* 0.485, 0.456, 0.406 */
+    float image_std[3];            /* 0.229, 0.224, 0.225 */
+    double rescale_factor;         /* 1 / 255 */
+} CsIncepConfig;
+
+typedef struct CsIncep CsIncep;
+
+/* host only: builds the weight manifest, touches no GPU */
+int cs_incep_create(const CsIncepConfig* cfg, CsIncep** out);
+void cs_incep_destroy(CsIncep* g);
+/* tensors by their torchvision Inception3 state-dict names ("Conv2d_1a_3x3.conv.weight", "Conv2d_1a_3x3.bn.running_var", ..., "fc.bias"); fp32 host memory.
+ * "....bn.num_batches_tracked" (0-d: ndim 0) and every "AuxLogits.*" tensor of a real checkpoint are accepted and ignored */
+int cs_incep_set_weight(CsIncep* g, const char* name, const float* data_host, const int64_t* shape, int ndim);
+int cs_incep_num_weights(const CsIncep* g);
+const char* cs_incep_weight_name(const CsIncep* g, int i, int64_t* shape4, int* ndim);
+int cs_incep_finalize(CsIncep* g);
+size_t cs_incep_workspace_bytes(const CsIncep* g, int batch);
+double cs_incep_flops(const CsIncep* g, int batch);
+/* row length of the front end's output (one pixel per row: 3 channels zero-padded to 8 halfs) and positions of the last grid per image */
+int cs_incep_patch_cols(const CsIncep* g);
+int cs_incep_num_tokens(const CsIncep* g);
+size_t cs_incep_preprocess_workspace_bytes(const CsIncep* g, int batch, int height, int width);
+/* the image front end of cs_vit_preprocess with torchvision's rules: PIL BICUBIC resize of the shortest edge to image_size, center crop at
+ * int(round((n - image_size) / 2.0)) (round half to even), any height x width whose resized sides reach image_size; `patches` is the normalised image
+ * [batch * image_size * image_size][8] fp16 (NHWC, channels 3 .. 7 zero).  crop_u8 (may be NULL): the cropped uint8 image [batch, 3, image_size, image_size] */
+int cs_incep_preprocess(CsIncep* g, const void* images, int dtype, int batch, int height, int width, void* patches,
+                        unsigned char* crop_u8, void* workspace, size_t workspace_bytes, void* stream);
+/* patches from cs_incep_preprocess -> the logits of fc [batch, num_classes] fp32 */
+int cs_incep_forward(CsIncep* g, const void* patches, int batch, float* logits, void* workspace, size_t workspace_bytes,
+                     void* stream);
+/* timing tools: cs_incep_forward returns after `parts` of (stem, Mixed_5, Mixed_6, Mixed_7, head); 5 (the default) runs everything, less leaves logits undefined */
+int cs_incep_set_stage_limit(CsIncep* g, int parts);
+
 #ifdef __cplusplus
 }
 #endif

@@ -328,6 +328,19 @@ int cs_op_seg_logits(const void* x, int B, int64_t HW, int64_t ld, int n, float*
 /* x [n] <- max(x, 0) in place; n % 8 == 0 */
 int cs_op_seg_relu(void* x, int64_t n, void* stream);
 
+/* the kernels of the Inception-v3 reward (csrc/incep_ops.hip), NHWC fp16 device pointers unless noted; fp32 arithmetic, one rounding:
+ * general implicit-GEMM convolution on the matrix cores: x [B][H][W][Cin] (Cin % 8 == 0; only the first Creal channels of a pixel are used, the others may
+ * hold anything), w [Cout][KH * KW][Cin] (zero in the channels Creal .. Cin), bias fp32 [Cout] or NULL, Cout % 16 == 0; stride 1 | 2; pad_h, pad_w >= 0.
+ * relu(conv + bias) goes to the columns col .. col + Cout of out [B * Ho * Wo][ld] (col, ld multiples of 16); nothing else of out is written */
+int cs_op_incep_conv(const void* x, int B, int H, int W, int Cin, int Creal, const void* w, const float* bias, int Cout, int KH, int KW, int stride,
+                     int pad_h, int pad_w, void* out, int64_t ld, int col, void* stream);
+/* max pool 3x3, stride 2, no padding: x [B][H][W][C] into the columns col .. col + C of out [B * Ho * Wo][ld]; C, col, ld multiples of 8 */
+int cs_op_incep_maxpool(const void* x, int B, int H, int W, int C, void* out, int64_t ld, int col, void* stream);
+/* average pool 3x3, stride 1, pad 1, count_include_pad (always / 9): x [B][H][W][C] -> out [B][H][W][C]; C % 8 == 0 */
+int cs_op_incep_avgpool(const void* x, int B, int H, int W, int C, void* out, void* stream);
+/* head: mean [B][C] fp32 (scratch) = mean over the HW positions of x [B][HW][C]; logits [B][N] fp32 = mean w^T + bias; w fp16 [N][C], bias fp32 [N]; C % 8 == 0 */
+int cs_op_incep_head(const void* x, int B, int64_t HW, int C, const void* w, const float* bias, int N, float* mean, float* logits, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

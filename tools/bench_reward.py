@@ -5,6 +5,7 @@ medians of ``--reps`` runs after ``--warmup``; one JSON line at the end.
     python tools/bench_reward.py --reward clip  [--batch 16] [--reps 7] [--out profiles/clip_reward_bench.txt]
     python tools/bench_reward.py --reward depth [--batch 8]  [--reps 7] [--out profiles/depth_reward_bench.txt]
     python tools/bench_reward.py --reward segmentation [--batch 4] [--reps 7] [--out profiles/segmentation_reward_bench.txt]
+    python tools/bench_reward.py --reward inception [--batch 4] [--reps 7] [--out profiles/inception_reward_bench.txt]
 
 * ``dino`` (config 5's batch, 80 + 80 images): front end (quantise + PIL-exact resize + crop + normalise + patch rows), encoder (12 layers, 257 tokens per
   image), tail (normalise, cosine, scale) and, in the same process, the VAE decode of those 160 images for scale.
@@ -15,6 +16,8 @@ medians of ``--reps`` runs after ``--warmup``; one JSON line at the end.
 * ``segmentation``: front end (bilinear resize to 512 x 512: the identity at this size), the MiT-B4 encoder stage by stage (the forward stopped after 1 .. 4
   stages, differenced), the head, argmax + agreement, the whole ``calculate_segmentation_reward`` call; and the depthwise 3x3 + GELU kernel alone at the
   stage-1 shape with the bytes it must move (input + output once) over its time, next to the HBM copy rate of the micro-architecture guide.
+* ``inception``: front end (bicubic resize to 299 + crop), Inception-v3 part by part (the forward stopped after the stem, Mixed_5, Mixed_6, Mixed_7,
+  differenced), the head, the whole ``calculate_inception_reward`` call; and the convolution kernel alone at three of the network's shapes with its rate.
 """
 import argparse
 import json
@@ -27,13 +30,13 @@ import torch
 from consolver_amd import synth
 from consolver_amd.ppo import depth_psnr_tail
 from consolver_amd import _lib as L
-from consolver_amd.reward_model import (calculate_depth_reward, calculate_segmentation_reward, cosine_reward, load_depth_reward, load_reward_model,
-                                        load_segmentation_reward, mask_agreement)
+from consolver_amd.reward_model import (calculate_depth_reward, calculate_inception_reward, calculate_segmentation_reward, cosine_reward, load_depth_reward,
+                                        load_inception_reward, load_reward_model, load_segmentation_reward, mask_agreement)
 
 DEV = "cuda:0"
 PEAK_F16_TFLOPS = 2500.0
 HBM_COPY_TBS = 6.29                # measured float4 copy rate of the MI355X (8.0 TB/s spec)
-DEFAULT_BATCH = {"dino": 80, "clip": 16, "depth": 8, "segmentation": 4}
+DEFAULT_BATCH = {"dino": 80, "clip": 16, "depth": 8, "segmentation": 4, "inception": 4}
 
 
 def timed(fn, warmup, reps):
@@ -153,10 +156,55 @@ def bench_segmentation(a, res, B, n):
         f"stay in the 256 MB Infinity Cache between two calls)"]
 
 
+def bench_inception(a, res, B, n):
+    model, proc = load_inception_reward(device=DEV)
+    model.load_state_dict(synth.synthetic_inception_state_dict(model.manifest()))
+    images = random_images(a, n)
+    patches = model.preprocess(images)
+    feats = model.encode_patches(patches)
+    lib = L.lib()
+    res["max_batch"] = model.max_batch
+    res["front_end_ms"] = timed(lambda: model.preprocess(images), a.warmup, a.reps)
+    upto, names = [], ("stem", "mixed_5", "mixed_6", "mixed_7", "head")
+    try:
+        for parts in range(1, 6):                      # the forward stopped after the stem, Mixed_5, Mixed_6, Mixed_7, then with the head
+            L.check(lib.cs_incep_set_stage_limit(model._h, parts))
+            upto.append(timed(lambda: model.encode_patches(patches), a.warmup, a.reps))
+    finally:
+        L.check(lib.cs_incep_set_stage_limit(model._h, 5))
+    for i, k in enumerate(names):
+        res[k + "_ms"] = upto[i] - (upto[i - 1] if i else 0.0)
+    res["model_ms"] = upto[4]
+    res["tail_ms"] = timed(lambda: cosine_reward(feats[:B], feats[B:]), a.warmup, a.reps)
+    res["reward_call_ms"] = timed(lambda: calculate_inception_reward(model, proc, images[:B], images[B:], DEV), a.warmup, a.reps)
+    res["model_tflop"] = model.flops(n) / 1e12
+    res["model_tflops"] = model.flops(n) / res["model_ms"] / 1e9
+    res["workspace_mb_per_image"] = int(model._fn("workspace_bytes")(model._h, 1)) / 1e6
+    lines = [f"  front end     {res['front_end_ms']:9.3f} ms"] + [f"  {k:<12s}  {res[k + '_ms']:9.3f} ms" for k in names] + [
+        f"  model         {res['model_ms']:9.3f} ms  ({res['model_tflop']:.3f} TFLOP, {res['model_tflops']:.1f} TFLOP/s)",
+        f"  tail          {res['tail_ms']:9.3f} ms",
+        f"  calculate_inception_reward, whole call {res['reward_call_ms']:9.3f} ms"]
+    # the convolution kernel alone at three shapes of the network: (grid, Cin, Cout, kh, kw, stride, pad_h, pad_w)
+    st = L.stream_ptr(DEV)
+    for name, (g, ci, co, kh, kw, stride, ph, pw) in (("conv2b_3x3_147", (147, 32, 64, 3, 3, 1, 1, 1)), ("mixed5_3x3_35", (35, 96, 96, 3, 3, 1, 1, 1)),
+                                                      ("mixed6_1x7_17", (17, 192, 192, 1, 7, 1, 0, 3)), ("mixed7_1x1_8", (8, 2048, 448, 1, 1, 1, 0, 0))):
+        x = torch.randn(n, g, g, ci, device=DEV, dtype=torch.float16)
+        w = torch.randn(co, kh * kw, ci, device=DEV, dtype=torch.float16) / (kh * kw * ci) ** 0.5
+        bias = torch.randn(co, device=DEV)
+        go = (g + 2 * ph - kh) // stride + 1
+        out = torch.empty(n * go * go, co, device=DEV, dtype=torch.float16)
+        ms = timed(lambda: L.check(lib.cs_op_incep_conv(L.ptr(x), n, g, g, ci, ci, L.ptr(w), L.ptr(bias), co, kh, kw, stride, ph, pw, L.ptr(out), co, 0, st)),
+                   a.warmup, a.reps)
+        res[f"conv_{name}_ms"] = ms
+        res[f"conv_{name}_tflops"] = 2.0 * n * go * go * co * ci * kh * kw / ms / 1e9
+        lines.append(f"  conv kernel alone, {name}: [{n}][{g}][{g}][{ci}] -> {co}, {kh} x {kw}: {ms:.4f} ms = {res[f'conv_{name}_tflops']:.1f} TFLOP/s")
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reward", choices=sorted(DEFAULT_BATCH), required=True)
-    ap.add_argument("--batch", type=int, default=None, help="pred / target pairs (default: 80 dino, 16 clip, 8 depth, 4 segmentation)")
+    ap.add_argument("--batch", type=int, default=None, help="pred / target pairs (default: 80 dino, 16 clip, 8 depth, 4 segmentation, 4 inception)")
     ap.add_argument("--size", type=int, default=512)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--reps", type=int, default=7)
@@ -166,8 +214,8 @@ def main():
     B = a.batch if a.batch is not None else DEFAULT_BATCH[a.reward]
     n = 2 * B
     res = {"batch_pairs": B, "images": n, "size": a.size}
-    stages = {"depth": bench_depth, "segmentation": bench_segmentation}.get(a.reward, bench_features)(a, res, B, n)
-    model_name = {"clip": ", ViT-L/14", "segmentation": ", SegFormer-B4"}.get(a.reward, "")
+    stages = {"depth": bench_depth, "segmentation": bench_segmentation, "inception": bench_inception}.get(a.reward, bench_features)(a, res, B, n)
+    model_name = {"clip": ", ViT-L/14", "segmentation": ", SegFormer-B4", "inception": ", Inception-v3 at 299"}.get(a.reward, "")
     lines = [f"{a.reward} reward, {n} images ({B} pred + {B} target) at {a.size}^2 fp16{model_name}, synthetic weights, medians of {a.reps}"] + stages
     lines.append(json.dumps(res))
     text = "\n".join(lines)
