@@ -32,6 +32,13 @@ class CsStepArgs(C.Structure):
                 ("v_prediction", C.c_int), ("dt", C.c_float), ("x_is_f32", C.c_int), ("x_out_lp", C.c_void_p), ("lp_dtype", C.c_int)]
 
 
+class CsDpmStepArgs(C.Structure):
+    _fields_ = [("x", C.c_void_p), ("eps_text", C.c_void_p), ("eps_uncond", C.c_void_p), ("guidance", C.c_float), ("m_prev", C.c_void_p),
+                ("B", C.c_int), ("elems", C.c_int64), ("io_dtype", C.c_int), ("out_dtype", C.c_int), ("x_is_f32", C.c_int),
+                ("x_out", C.c_void_p), ("m_out", C.c_void_p), ("x_out_lp", C.c_void_p), ("lp_dtype", C.c_int),
+                ("conv_x", C.c_float), ("conv_e", C.c_float), ("cx", C.c_float), ("c0", C.c_float), ("c1", C.c_float)]
+
+
 class CsFluxConfig(C.Structure):
     _fields_ = [("in_channels", C.c_int), ("num_layers", C.c_int), ("num_single_layers", C.c_int), ("num_heads", C.c_int),
                 ("head_dim", C.c_int), ("joint_attention_dim", C.c_int), ("pooled_projection_dim", C.c_int),
@@ -114,6 +121,7 @@ SYMBOLS = {
     "cs_stack_history": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_void_p]),
     "cs_lms_ddim_step": (C.c_int, [C.POINTER(CsStepArgs), C.c_void_p]),
     "cs_lms_euler_step": (C.c_int, [C.POINTER(CsStepArgs), C.c_void_p]),
+    "cs_dpm_multistep_step": (C.c_int, [C.POINTER(CsDpmStepArgs), C.c_void_p]),
     "cs_psnr_workspace_bytes": (C.c_size_t, [C.c_int]),
     "cs_image_psnr": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_size_t,
                                 C.c_void_p]),

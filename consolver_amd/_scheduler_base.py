@@ -202,5 +202,8 @@ if not HAVE_DIFFUSERS:
         @classmethod
         def _get_compatibles(cls):
             import consolver_amd
+            # this package's classes that name each other: a learned solver lists the Karras family (its config loads into any of them), but
+            # the package's own DPMSolverMultistepScheduler does not list the learned solvers (their policy has no counterpart in it)
             names = list(set([cls.__name__] + list(cls._compatibles)))
-            return [getattr(consolver_amd, n) for n in names if hasattr(consolver_amd, n)]
+            found = [getattr(consolver_amd, n) for n in names if hasattr(consolver_amd, n)]
+            return [c for c in found if c is cls or cls.__name__ in getattr(c, "_compatibles", ())]

@@ -4,6 +4,7 @@
 //                       (scheduler_ppo.py:165-175,253-283,306-332; denoise_ppo.py:96-100)
 //   cs_lms_euler_step : same with the flow-matching Euler epilogue
 //                       (edit_ppo/scheduler_fmppo.py:400-436)
+//   cs_dpm_multistep_step : CFG combine + model-output conversion + Multistep DPM-Solver update (orders 1, 2)
 //   cs_factor_probs   : FactorNetPPO.forward_ (factor_net_ppo.py:137-157)
 //   cs_cosine_features: compute_cosine_similarity (factor_net_ppo.py:108-130)
 //   cs_sample_actions / cs_gather_actions / cs_action_probs / cs_step_masks / cs_stack_history
@@ -251,6 +252,125 @@ int launch_step(const CsStepArgs* a, void* stream) {
     return CS_OK;
 }
 
+// ---------------------------------------------------------------- Multistep DPM-Solver
+// Every variant (dpmsolver / dpmsolver++, epsilon / v prediction, first / second order, midpoint / heun) is the same linear update per
+// element; the variant lives in five host scalars (scheduling_dpm.py).  m0 is the "converted model output" of this step (the history entry
+// of the next one), rounded to the model dtype like the combined eps; m1 is the previous step's m0 (NULL at first order).
+struct DpmParams {
+    const void* x; const void* ec; const void* eu; float g;
+    const void* m1;
+    int64_t elems;
+    void* x_out; void* m_out;
+    float conv_x, conv_e, cx, c0, c1;
+    int x_f32;   // as StepParams::x_f32
+    void* x_lp;  // as StepParams::x_lp
+    int lp_bf16;
+};
+
+__device__ __forceinline__ float dpm_one(const DpmParams& p, float x, float m0, float m1) {
+    float r = p.cx * x + p.c0 * m0;
+    if (p.m1) r = r + p.c1 * m1;
+    return r;
+}
+
+template <typename TI, typename TO>
+__global__ __launch_bounds__(256) void dpm_step_kernel(DpmParams p) {
+    constexpr int V = Io<TI>::VEC;
+    const int b = blockIdx.y;
+    const int64_t base = (int64_t)b * p.elems;
+    const int64_t nvec = p.elems / V;
+    for (int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; v < nvec; v += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t i = base + v * V;
+        float x[V], e[V], u[V], h[V], o[V];
+        if (p.x_f32) {   // block-uniform
+#pragma unroll
+            for (int j = 0; j < V; ++j) x[j] = reinterpret_cast<const float*>(p.x)[i + j];
+        } else {
+            Io<TI>::load(p.x, i, x);
+        }
+        Io<TI>::load(p.ec, i, e);
+        if (p.eu) {
+            Io<TI>::load(p.eu, i, u);
+#pragma unroll
+            for (int j = 0; j < V; ++j) e[j] = Io<TI>::round(u[j] + p.g * (e[j] - u[j]));
+        }
+#pragma unroll
+        for (int j = 0; j < V; ++j) e[j] = Io<TI>::round(p.conv_x * x[j] + p.conv_e * e[j]);
+        if (p.m1) {
+            Io<TI>::load(p.m1, i, h);
+        } else {
+#pragma unroll
+            for (int j = 0; j < V; ++j) h[j] = 0.f;
+        }
+        if (p.m_out) Io<TI>::store(p.m_out, i, e);
+#pragma unroll
+        for (int j = 0; j < V; ++j) o[j] = dpm_one(p, x[j], e[j], h[j]);
+        if constexpr (Io<TO>::VEC == V) {
+            Io<TO>::store(p.x_out, i, o);
+        } else {
+#pragma unroll
+            for (int j = 0; j < V; ++j) Io<TO>::store1(p.x_out, i + j, o[j]);
+        }
+        if (p.x_lp) store_lp<V>(p.x_lp, i, o, p.lp_bf16);
+    }
+    // scalar tail (elems % V != 0): handled by the first block of each sample
+    if (blockIdx.x == 0) {
+        for (int64_t t = nvec * V + threadIdx.x; t < p.elems; t += blockDim.x) {
+            const int64_t i = base + t;
+            const float x = p.x_f32 ? reinterpret_cast<const float*>(p.x)[i] : Io<TI>::load1(p.x, i);
+            float e = Io<TI>::load1(p.ec, i);
+            if (p.eu) { float u = Io<TI>::load1(p.eu, i); e = Io<TI>::round(u + p.g * (e - u)); }
+            e = Io<TI>::round(p.conv_x * x + p.conv_e * e);
+            const float h = p.m1 ? Io<TI>::load1(p.m1, i) : 0.f;
+            if (p.m_out) Io<TI>::store1(p.m_out, i, e);
+            const float r = dpm_one(p, x, e, h);
+            Io<TO>::store1(p.x_out, i, r);
+            if (p.x_lp) store_lp1(p.x_lp, i, r, p.lp_bf16);
+        }
+    }
+}
+
+int launch_dpm_step(const CsDpmStepArgs* a, void* stream) {
+    if (!a) CS_FAIL(CS_E_ARG, "args is NULL");
+    if (a->B < 0 || a->elems < 0) CS_FAIL(CS_E_SHAPE, "negative shape");
+    const bool empty = (a->B == 0 || a->elems == 0);
+    if (!empty && (!a->x || !a->eps_text || !a->x_out)) CS_FAIL(CS_E_ARG, "x, eps_text and x_out are required");
+    if (a->x_out_lp && (a->out_dtype != CS_F32 || (a->lp_dtype != CS_F16 && a->lp_dtype != CS_BF16)))
+        CS_FAIL(CS_E_ARG, "x_out_lp is the 16-bit copy (lp_dtype CS_F16 or CS_BF16) of an fp32 result (out_dtype CS_F32)");
+    const int io = a->io_dtype, od = a->out_dtype;
+    const bool pair_ok = (io == CS_F32 && od == CS_F32) || (io == CS_F16 && (od == CS_F16 || od == CS_F32)) || (io == CS_BF16 && (od == CS_BF16 || od == CS_F32));
+    if (!pair_ok) CS_FAIL(CS_E_DTYPE, "unsupported io/out dtype pair (%d,%d)", io, od);
+    if (a->x_is_f32 && io != CS_F32 && od != CS_F32) CS_FAIL(CS_E_DTYPE, "an fp32 sample gives an fp32 result (out_dtype %d)", od);
+    if (empty) return CS_OK;
+    const bool identity = (a->conv_x == 0.f && a->conv_e == 1.f);
+    if ((a->eps_uncond || !identity) && !a->m_out)
+        CS_FAIL(CS_E_ARG, "m_out is required with CFG or a model-output conversion (the converted output is the history entry)");
+    DpmParams p;
+    p.x = a->x; p.ec = a->eps_text; p.eu = a->eps_uncond; p.g = a->guidance;
+    p.m1 = a->m_prev; p.elems = a->elems;
+    p.x_out = a->x_out; p.m_out = a->m_out;
+    p.conv_x = a->conv_x; p.conv_e = a->conv_e; p.cx = a->cx; p.c0 = a->c0; p.c1 = a->c1;
+    p.x_f32 = (a->x_is_f32 != 0 && io != CS_F32);
+    p.x_lp = a->x_out_lp; p.lp_bf16 = a->lp_dtype == CS_BF16;
+    const int vec = (io == CS_F32) ? 4 : 8;
+    int64_t nvec = a->elems / vec;
+    int gx = (int)((nvec + 255) / 256);
+    // the same capped grid as launch_step: ~8 blocks per CU overall, grid-stride the rest
+    int cap = (2048 + a->B - 1) / a->B; if (cap < 1) cap = 1;
+    if (gx > cap) gx = cap; if (gx < 1) gx = 1;
+    dim3 grid(gx, a->B), block(256);
+    hipStream_t s = (hipStream_t)stream;
+#define LAUNCH(TI, TO) hipLaunchKernelGGL((dpm_step_kernel<TI, TO>), grid, block, 0, s, p)
+    if (io == CS_F32) LAUNCH(float, float);
+    else if (io == CS_F16 && od == CS_F16) LAUNCH(f16, f16);
+    else if (io == CS_F16) LAUNCH(f16, float);
+    else if (od == CS_BF16) LAUNCH(bf16_tag, bf16_tag);
+    else LAUNCH(bf16_tag, float);
+#undef LAUNCH
+    CS_CHECK_LAUNCH();
+    return CS_OK;
+}
+
 // ---------------------------------------------------------------- policy MLP
 // one workgroup per DISTINCT conditioning row; weights (<= ~1 MB) stay in L2.  When one row is
 // broadcast to all B samples (x_row_stride == 0, no cosine features: every sampling step), a single
@@ -471,6 +591,7 @@ extern "C" {
 
 int cs_lms_ddim_step(const CsStepArgs* args, void* stream) { return launch_step<false>(args, stream); }
 int cs_lms_euler_step(const CsStepArgs* args, void* stream) { return launch_step<true>(args, stream); }
+int cs_dpm_multistep_step(const CsDpmStepArgs* args, void* stream) { return launch_dpm_step(args, stream); }
 
 int cs_factor_probs(const CsFactorNet* n, const float* x, int x_row_stride, const float* cos_feat, int B, float* probs, void* stream) {
     if (!n) CS_FAIL(CS_E_ARG, "net is NULL");

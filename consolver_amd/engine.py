@@ -64,11 +64,13 @@ class SDSamplingEngine:
         self._graph = None
         self._graph_key = None
         self.forward_events = None      # optional list collecting (start, stop) events around UNet forwards
+        self.last_latents = None        # final latents of the last generate() call (a view of an internal buffer)
 
     def _buffers(self, B, shape, device):
         key = (B, tuple(shape), str(device), self.latents_dtype, self.eps_dtype)
         if self._bufs is None or self._bufs["key"] != key:
-            order = self.scheduler.config.order_dim
+            cfg = self.scheduler.config
+            order = cfg.get("order_dim") or cfg["solver_order"]       # (DPMSolverMultistepScheduler keeps `solver_order` converted outputs)
             C, H, W = shape
             self._graph = self._graph_key = None      # a captured graph holds the OLD buffers' addresses (latents_dtype is a public attribute and part of the key)
             self._bufs = dict(
@@ -144,6 +146,7 @@ class SDSamplingEngine:
         if output_type == "pt" and self.vae is None:
             raise RuntimeError("output_type='pt' needs a HIP AutoencoderKL (SDSamplingEngine(..., vae=...))")
         lat = self._generate_latents(prompt_embeds, negative_prompt_embeds, latents, num_inference_steps, generator, use_graph)
+        self.last_latents = lat         # (the same view of the internal buffer: what output_type="pt" decoded, for callers that keep both)
         if output_type == "latent":
             return lat
         from .vae import decode_latents

@@ -63,8 +63,27 @@ def _load_sd(path):
     return torch.load(path, map_location="cpu")
 
 
-def main(argv=None):
+SOLVERS = ("consistencysolver", "multistep-dpmsolver", "ddim")
+
+
+def make_scheduler(solver, order_dim=4, scaler_dim=0, use_conv=False, num_actions=11):
+    """the in-tree equivalent of ``gen_ppo.load_pipeline(type=...)`` (gen_ppo.py:108-169) on SD1.5's schedule: the learned solver, the
+    Multistep-DPM-Solver baseline (:149-155) or eta = 0 DDIM on the learned solver's grid (baselines.py)."""
     import consolver_amd
+    sd15 = dict(beta_start=0.00085, beta_end=0.012, beta_schedule="scaled_linear")
+    if solver == "consistencysolver":
+        return consolver_amd.PPOScheduler(timestep_spacing="trailing", order_dim=order_dim, scaler_dim=scaler_dim, use_conv=use_conv,
+                                          factor_net_kwargs=dict(embedding_dim=32, hidden_dim=256, num_actions=num_actions), **sd15)
+    if solver == "multistep-dpmsolver":
+        return consolver_amd.DPMSolverMultistepScheduler(**consolver_amd.SD15_MULTISTEP_DPM_KWARGS)
+    if solver == "ddim":
+        from .baselines import DDIMBaselineScheduler
+        return DDIMBaselineScheduler(timestep_spacing="trailing", **sd15)
+    raise ValueError(f"unknown solver {solver!r}; expected one of {SOLVERS}")
+
+
+def main(argv=None, *, unet=None, vae=None):
+    """``unet`` / ``vae``: already loaded HIP handles to run on instead of building them from the arguments."""
     from .engine import SDSamplingEngine
     from .synth import synthetic_prompt_embeds, synthetic_unet_state_dict, synthetic_vae_state_dict
     from .text_encoder import load_prompt_cache
@@ -84,28 +103,35 @@ def main(argv=None):
     ap.add_argument("--num-actions", type=int, default=11)
     ap.add_argument("--use_conv", "--use-conv", dest="use_conv", action="store_true",
                     help="gen_ppo.py:399: the policy also sees the cosine-similarity features of the eps history (factor_net_ppo.py:72-73,146-149)")
+    ap.add_argument("--solver", default="consistencysolver", choices=SOLVERS,
+                    help="gen_ppo.load_pipeline(type=...): the learned solver (default), the Multistep-DPM-Solver baseline or DDIM; the baselines have no policy")
     ap.add_argument("--residual", default="f16x2", choices=["f16", "f16x2", "residual_fp32"],
                     help="residual-stream storage of the UNet executor (include/consolver_hip.h): f16x2 meets the 1e-3 latent gate, f16 is ~8 %% faster")
     args = ap.parse_args(argv)
+    if args.solver != "consistencysolver" and (args.policy or args.use_conv):
+        ap.error(f"--policy / --use_conv belong to the learned solver; --solver {args.solver} has no policy")
     rank, world, local, dist = launch.init_distributed()
     torch.cuda.set_device(local)
     dev = torch.device("cuda", local)
-    unet, vae = HipUNet2DConditionModel(device=dev, residual=args.residual), HipAutoencoderKL(device=dev)
+    given = unet is not None and vae is not None
+    if not given:
+        unet, vae = HipUNet2DConditionModel(device=dev, residual=args.residual), HipAutoencoderKL(device=dev)
     if args.synthetic:
-        unet.load_state_dict(synthetic_unet_state_dict(unet.manifest()))
-        vae.load_state_dict(synthetic_vae_state_dict(vae.manifest()))
+        if not given:
+            unet.load_state_dict(synthetic_unet_state_dict(unet.manifest()))
+            vae.load_state_dict(synthetic_vae_state_dict(vae.manifest()))
         prompts = [f"synthetic prompt {i}" for i in range(args.synthetic)]
         pe, ne = synthetic_prompt_embeds(args.synthetic, seed=1001).half(), synthetic_prompt_embeds(args.synthetic, seed=1002).half()
     else:
-        unet.load_state_dict(_load_sd(args.unet))
-        vae.load_state_dict(_load_sd(args.vae))
+        if not given:
+            unet.load_state_dict(_load_sd(args.unet))
+            vae.load_state_dict(_load_sd(args.vae))
         prompts, pe, ne = load_prompt_cache(args.prompt_cache)
-    sch = consolver_amd.PPOScheduler(beta_start=0.00085, beta_end=0.012, beta_schedule="scaled_linear", timestep_spacing="trailing",
-                                     order_dim=args.order_dim, scaler_dim=args.scaler_dim, use_conv=args.use_conv,
-                                     factor_net_kwargs=dict(embedding_dim=32, hidden_dim=256, num_actions=args.num_actions))
-    if args.policy:
-        sch.factor_net.load_state_dict(torch.load(args.policy, map_location="cpu"))
-    sch.factor_net.to(dev)
+    sch = make_scheduler(args.solver, args.order_dim, args.scaler_dim, args.use_conv, args.num_actions)
+    if sch.factor_net is not None:
+        if args.policy:
+            sch.factor_net.load_state_dict(torch.load(args.policy, map_location="cpu"))
+        sch.factor_net.to(dev)
     eng = SDSamplingEngine(unet, sch, guidance_scale=args.cfg, vae=vae)
     if dist is not None:
         dist.barrier()
@@ -119,7 +145,8 @@ def main(argv=None):
         print(f"{total} images in {secs:.2f} s = {total / secs:.2f} images/s on {world} GPU(s); per rank: {[c for c, _ in report]}")
     if dist is not None:
         dist.destroy_process_group()
-    return {"images": n, "use_conv": bool(sch.factor_net.use_conv), "residual": unet.residual, "seconds": secs}
+    return {"images": n, "use_conv": bool(sch.factor_net.use_conv) if sch.factor_net is not None else False, "residual": unet.residual, "seconds": secs,
+            "solver": args.solver}
 
 
 if __name__ == "__main__":

@@ -77,7 +77,8 @@ class ConsistencySolverPipeline:
                 raise ValueError(f"unknown output_type {output_type!r}")
         if not return_dict:
             return (out, None)
-        return types.SimpleNamespace(images=out, nsfw_content_detected=None)
+        # gen_pretrain/pipeline.py:1122: the initial noise and the final latents, on the CPU (what the teacher-pair generator stores)
+        return types.SimpleNamespace(images=out, nsfw_content_detected=None, init_latent=latents.cpu(), generate_latent=eng.last_latents.cpu())
 
 
 class FluxKontextEditPipeline:

@@ -150,6 +150,35 @@ int cs_lms_ddim_step(const CsStepArgs* args, void* stream);
 int cs_lms_euler_step(const CsStepArgs* args, void* stream);
 
 /* ------------------------------------------------------------------------
+ * Multistep DPM-Solver update (orders 1 and 2; consolver_amd/scheduling_dpm.py).
+ * Every variant is one linear update per element; the variant is in five host scalars:
+ *     eps = eps_uncond ? round_io(u + guidance * (c - u)) : c
+ *     m0  = round_io(conv_x * x + conv_e * eps)        the converted model output, written to m_out
+ *     x'  = cx * x + c0 * m0 + c1 * m_prev             (c1 * m_prev only when m_prev != NULL)
+ * Pointer and dtype fields mean what they mean in CsStepArgs.
+ * ---------------------------------------------------------------------- */
+typedef struct CsDpmStepArgs {
+    const void* x;            /* [B, elems] current sample (io_dtype, or fp32 when x_is_f32) */
+    const void* eps_text;     /* [B, elems] model output (conditional branch)       */
+    const void* eps_uncond;   /* [B, elems] unconditional branch, or NULL (no CFG)  */
+    float guidance;
+    const void* m_prev;       /* [B, elems] the previous step's m0, or NULL (first order) */
+    int B;
+    int64_t elems;            /* elements per sample                                */
+    int io_dtype;             /* dtype of eps_*, m_prev, m_out (and of x unless x_is_f32) */
+    int out_dtype;            /* dtype of x_out                                     */
+    int x_is_f32;
+    void* x_out;              /* [B, elems]                                         */
+    void* m_out;              /* [B, elems] m0; required when eps_uncond != NULL or
+                                 (conv_x, conv_e) != (0, 1), else optional           */
+    void* x_out_lp;           /* optional 16-bit copy of an fp32 result, as CsStepArgs::x_out_lp */
+    int lp_dtype;
+    float conv_x, conv_e, cx, c0, c1;
+} CsDpmStepArgs;
+
+int cs_dpm_multistep_step(const CsDpmStepArgs* args, void* stream);
+
+/* ------------------------------------------------------------------------
  * SD1.5 UNet2DConditionModel forward (denoiser).  See DESIGN.md for the
  * activation layout (NHWC fp16) and the kernels behind it.
  * ---------------------------------------------------------------------- */

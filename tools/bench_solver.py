@@ -1,6 +1,11 @@
 """K1 (fused CFG + LMS combine + DDIM/Euler) bandwidth: algorithmic bytes / kernel time vs HBM peak.
 
-Algorithmic bytes per step: passes = [x] + [eps_u, eps_c] + [hist m-1] + [x'] + [eps store]."""
+Algorithmic bytes per step: passes = [x] + [eps_u, eps_c] + [hist m-1] + [x'] + [eps store].
+
+``--dpm``: the Multistep DPM-Solver update (cs_dpm_multistep_step) in the engine's form -- fp32 state, fp16 model outputs, CFG, second order, the fp16
+copy of the result in the same pass -- next to cs_lms_ddim_step with a history of 2 on the same tensors (the same 18 bytes per element), and a 1 GiB
+device copy (read + write bytes, what bench.py --full reports as dtod_copy_1gib_tbps) as the rate both are a share of.  The two kernels are timed
+as hipGraph replays of 500 captured launches (a Python launch loop measures the host's enqueue rate at this size), alternating, median of 5."""
 import ctypes as C, json, os, sys
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -35,6 +40,69 @@ def run(B, elems, dtype, m, cfg=True, euler=False, iters=50):
     nbytes = passes * B * elems * x.element_size()
     return dict(B=B, elems=elems, dtype=str(dtype).split(".")[-1], m=m, cfg=cfg, euler=euler, us=round(us, 2),
                 MB=round(nbytes / 1e6, 2), GBps=round(nbytes / us / 1e3, 1), frac_of_8TBps=round(nbytes / us / 1e3 / 8000, 3))
+
+def time_us(fn, iters):
+    for _ in range(3): fn()
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(iters): fn()
+    e1.record(); torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / iters * 1e3
+
+
+def graph_us(fn, launches=500, replays=10):
+    """kernel time without the host's launch path: ``launches`` back-to-back launches captured into one hipGraph, replayed ``replays`` times"""
+    side = torch.cuda.Stream(device=dev)
+    side.wait_stream(torch.cuda.current_stream(dev))
+    with torch.cuda.stream(side):
+        for _ in range(3): fn()
+    torch.cuda.current_stream(dev).wait_stream(side)
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        for _ in range(launches): fn()
+    return time_us(g.replay, replays) / launches
+
+
+def run_dpm(B=32, elems=4 * 64 * 64):
+    h = lambda: torch.randn(B, elems, device=dev).half()
+    x, out = torch.randn(B, elems, device=dev), torch.empty(B, elems, device=dev)
+    eu, ec, m1, mo, lp = h(), h(), h(), h(), h()
+    d = L.CsDpmStepArgs()
+    d.x, d.eps_text, d.eps_uncond, d.guidance, d.m_prev = x.data_ptr(), ec.data_ptr(), eu.data_ptr(), 3.0, m1.data_ptr()
+    d.B, d.elems, d.io_dtype, d.out_dtype, d.x_is_f32 = B, elems, L.CS_F16, L.CS_F32, 1
+    d.x_out, d.m_out, d.x_out_lp, d.lp_dtype = out.data_ptr(), mo.data_ptr(), lp.data_ptr(), L.CS_F16
+    d.conv_x, d.conv_e, d.cx, d.c0, d.c1 = 0.0, 1.0, 1.02, -0.21, 0.07
+    actions = torch.rand(B, 3, device=dev)
+    a = L.CsStepArgs()
+    a.x, a.eps_text, a.eps_uncond, a.guidance = x.data_ptr(), ec.data_ptr(), eu.data_ptr(), 3.0
+    a.hist[0] = m1.data_ptr()
+    a.m, a.order_dim, a.scaler_dim = 2, 2, 0
+    a.actions, a.actions_stride, a.B, a.elems = actions.data_ptr(), 3, B, elems
+    a.io_dtype, a.out_dtype, a.x_is_f32 = L.CS_F16, L.CS_F32, 1
+    a.x_out, a.eps_out, a.x_out_lp, a.lp_dtype = out.data_ptr(), mo.data_ptr(), lp.data_ptr(), L.CS_F16
+    a.sqrt_at, a.sqrt_1mat, a.sqrt_ap, a.sqrt_1map = 0.3, 0.95, 0.5, 0.86
+    nbytes = (4 + 2 + 2 + 2 + 4 + 2 + 2) * B * elems          # x, eps_u, eps_c, m1 | x', m0, fp16 copy of x'
+    src = torch.randn(1 << 28, device=dev); dst = torch.empty_like(src)
+    copy_gbps = 2.0 * (1 << 30) / time_us(lambda: dst.copy_(src), 20) / 1e3
+    del src, dst
+    kernels = (("cs_dpm_multistep_step", lib.cs_dpm_multistep_step, d), ("cs_lms_ddim_step_m2", lib.cs_lms_ddim_step, a))
+    times = {name: [] for name, _, _ in kernels}
+    for _ in range(5):                                        # alternate the two kernels; report the median window
+        for name, fn, args in kernels:
+            times[name].append(graph_us(lambda: L.check(fn(C.byref(args), L.stream_ptr(dev)))))
+    rows = []
+    for name, _, _ in kernels:
+        us = sorted(times[name])[2]
+        rows.append(dict(kernel=name, B=B, elems=elems, state="float32", outputs="float16", cfg=True, order=2, us=round(us, 2),
+                         us_min_max=[round(min(times[name]), 2), round(max(times[name]), 2)], MB=round(nbytes / 1e6, 2),
+                         GBps=round(nbytes / us / 1e3, 1), copy_1gib_GBps=round(copy_gbps, 1), share_of_copy_rate=round(nbytes / us / 1e3 / copy_gbps, 3)))
+    return rows
+
+
+if "--dpm" in sys.argv:
+    for r in run_dpm(): print(json.dumps(r))
+    sys.exit(0)
 
 rows = [run(16, 16384, torch.float16, 4),            # configs[1]: batch 16, steady state step
         run(80, 16384, torch.float16, 4),            # configs[4]: PPO rollout batch
