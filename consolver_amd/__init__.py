@@ -11,5 +11,6 @@ from ._scheduler_base import HAVE_DIFFUSERS, SolverConfig  # noqa: F401
 from .scheduling_fmppo import FMPPOScheduler  # noqa: F401
 from .factor_net import FactorNetPPO, FluxFactorNetPPO  # noqa: F401
 from .scheduling_dpm import DPMSolverMultistepScheduler, SD15_MULTISTEP_DPM_KWARGS  # noqa: F401
+from .fid import FIDStatistics, HipFIDInception, compute_fid, frechet_distance, load_fid_inception  # noqa: F401
 
 __version__ = "0.1.0"

@@ -11,7 +11,7 @@ import torch
 PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CONSOLVER_HIP_LIB") or os.path.join(PKG, "libconsolver_hip.so")   # override: A/B builds in tools/
 
-CS_F32, CS_F16, CS_BF16 = 0, 1, 2
+CS_F32, CS_F16, CS_BF16, CS_U8 = 0, 1, 2, 3
 CS_MAX_ORDER = 8
 _DT = {torch.float32: CS_F32, torch.float16: CS_F16, torch.bfloat16: CS_BF16}
 
@@ -91,6 +91,10 @@ class CsSegConfig(C.Structure):
 
 class CsIncepConfig(C.Structure):
     _fields_ = [("image_size", C.c_int), ("num_classes", C.c_int), ("image_mean", C.c_float * 3), ("image_std", C.c_float * 3), ("rescale_factor", C.c_double)]
+
+
+class CsFidConfig(C.Structure):
+    _fields_ = [("image_mean", C.c_float * 3), ("image_std", C.c_float * 3)]
 
 
 class CsGemm2Problem(C.Structure):
@@ -299,10 +303,15 @@ SYMBOLS = {
     "cs_op_incep_maxpool": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_void_p]),
     "cs_op_incep_avgpool": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "cs_op_incep_head": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cs_op_fid_avgpool": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "cs_op_fid_maxpool": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "cs_fid_stats_accumulate": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cs_fid_stats_finalize": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 # the image-tower handle families (csrc/image_tower.h) declare the same 13 entry points, each over its own config struct
-for _prefix, _config in (("vit", CsVitConfig), ("clipv", CsClipVisionConfig), ("depth", CsDepthConfig), ("seg", CsSegConfig), ("incep", CsIncepConfig)):
+for _prefix, _config in (("vit", CsVitConfig), ("clipv", CsClipVisionConfig), ("depth", CsDepthConfig), ("seg", CsSegConfig), ("incep", CsIncepConfig),
+                         ("fid", CsFidConfig)):
     SYMBOLS.update({
         f"cs_{_prefix}_create": (C.c_int, [C.POINTER(_config), C.POINTER(C.c_void_p)]),
         f"cs_{_prefix}_destroy": (None, [C.c_void_p]),

@@ -38,6 +38,8 @@ SOURCES = {
     "segformer.cpp": [],
     "incep_ops.hip": [],
     "inception.cpp": [],
+    "fid_ops.hip": [],
+    "fid.cpp": [],
     "ppo.hip": [],
     "ops_api.cpp": [],
 }

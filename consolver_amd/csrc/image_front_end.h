@@ -23,6 +23,7 @@ inline int crop_offset(int n, int C, CropRule rule) {
     return (rule == CROP_ROUND_HALF_EVEN && (d & 1) && (k & 1)) ? k + 1 : k;
 }
 struct Taps { std::vector<int> lo, cnt, kk; int ksize; };
+struct TapsF64 { std::vector<int> lo, cnt; std::vector<double> kk; int ksize; };      // the taps as precompute_coeffs leaves them: normalised, in double
 inline double pil_cubic(double x) {
     const double a = -0.5;
     x = std::fabs(x);
@@ -34,11 +35,11 @@ inline double pil_triangle(double x) {
     x = std::fabs(x);
     return x < 1.0 ? 1.0 - x : 0.0;
 }
-inline Taps pil_taps(int in, int out, int win0, int win, Filter filter = PIL_BICUBIC) {
-    Taps t;
+inline TapsF64 pil_taps_f64(int in, int out, int win0, int win, Filter filter = PIL_BICUBIC) {
+    TapsF64 t;
     const double scale = (double)in / out, fs = std::max(scale, 1.0), support = (filter == PIL_BILINEAR ? 1.0 : 2.0) * fs, ww = 1.0 / fs;
     t.ksize = (int)std::ceil(support) * 2 + 1;
-    t.lo.resize(win); t.cnt.resize(win); t.kk.assign((size_t)win * t.ksize, 0);
+    t.lo.resize(win); t.cnt.resize(win); t.kk.assign((size_t)win * t.ksize, 0.0);
     std::vector<double> w(t.ksize);
     for (int i = 0; i < win; ++i) {
         const double center = (win0 + i + 0.5) * scale;
@@ -49,16 +50,33 @@ inline Taps pil_taps(int in, int out, int win0, int win, Filter filter = PIL_BIC
             w[x] = filter == PIL_BILINEAR ? pil_triangle(a) : pil_cubic(a);
             tot += w[x];
         }
-        for (int x = 0; x < n; ++x) {
-            const double k = tot != 0.0 ? w[x] / tot : w[x];
-            t.kk[(size_t)i * t.ksize + x] = k < 0 ? (int)(-0.5 + k * (1 << 22)) : (int)(0.5 + k * (1 << 22));
-        }
+        for (int x = 0; x < n; ++x) t.kk[(size_t)i * t.ksize + x] = tot != 0.0 ? w[x] / tot : w[x];
         t.lo[i] = xmin; t.cnt[i] = n;
     }
     return t;
 }
+// the 8-bit path: the same taps converted as int(+-0.5 + k 2^22)
+inline Taps pil_taps(int in, int out, int win0, int win, Filter filter = PIL_BICUBIC) {
+    TapsF64 f = pil_taps_f64(in, out, win0, win, filter);
+    Taps t;
+    t.ksize = f.ksize; t.lo = std::move(f.lo); t.cnt = std::move(f.cnt); t.kk.resize(f.kk.size());
+    for (size_t i = 0; i < f.kk.size(); ++i) {
+        const double k = f.kk[i];
+        t.kk[i] = k < 0 ? (int)(-0.5 + k * (1 << 22)) : (int)(0.5 + k * (1 << 22));
+    }
+    return t;
+}
+// one side of a mode-"F" resize to `out`: PIL runs no pass over a side that has the size already (the pixels are copied), stated as one tap of 1.0
+inline TapsF64 pil_float_side(int in, int out) {
+    if (in != out) return pil_taps_f64(in, out, 0, out, PIL_BICUBIC);
+    TapsF64 t;
+    t.ksize = 1; t.lo.resize(out); t.cnt.assign(out, 1); t.kk.assign(out, 1.0);
+    for (int i = 0; i < out; ++i) t.lo[i] = i;
+    return t;
+}
 
 struct Plan { VitResizePlan dev; };
+struct FloatPlan { FidResizePlan dev; };
 
 // resize tables per input (height, width), at most MAX_PLANS of them (a directory of many image sizes must not grow device memory without bound: when the
 // cache is full it is emptied -- hipFree waits for the kernels that still read a table).  Like every handle here the owner serves one thread at a time, and the
@@ -68,7 +86,16 @@ struct PlanCache {
     Filter filter = PIL_BICUBIC;                            // the processor's resample (set once, before the first plan)
     CropRule crop_rule = CROP_FLOOR;                        // the processor's center-crop offset (set once, next to filter)
     std::map<std::pair<int, int>, Plan> plans;
+    std::map<std::pair<int, int>, FloatPlan> float_plans;   // get_float_plan's; the bound and the allocations are shared with `plans`
     std::vector<void*> plan_allocs;
+
+    // a full cache is emptied before a new table is allocated
+    int make_room() {
+        if (plans.size() + float_plans.size() < MAX_PLANS) return CS_OK;
+        for (void* q : plan_allocs) CS_CHECK_HIP(hipFree(q));
+        plan_allocs.clear(); plans.clear(); float_plans.clear();
+        return CS_OK;
+    }
 
     // the plan of an H x W input for the processor (shortest edge `edge`, center crop C); `who` names the executor in error messages
     int get_plan(const char* who, int edge, int C, int H, int W, const Plan** out) {
@@ -89,10 +116,8 @@ struct PlanCache {
         std::vector<int> all;
         auto put = [&](const std::vector<int>& v) { const size_t o = all.size(); all.insert(all.end(), v.begin(), v.end()); return o; };
         const size_t o0 = put(th.lo), o1 = put(th.cnt), o2 = put(th.kk), o3 = put(tv.lo), o4 = put(tv.cnt), o5 = put(tv.kk);
-        if (plans.size() >= MAX_PLANS) {
-            for (void* q : plan_allocs) CS_CHECK_HIP(hipFree(q));
-            plan_allocs.clear(); plans.clear();
-        }
+        const int rc = make_room();
+        if (rc != CS_OK) return rc;
         int* d = nullptr;
         CS_CHECK_HIP(hipMalloc((void**)&d, all.size() * sizeof(int)));
         if (hipMemcpy(d, all.data(), all.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(d); CS_FAIL(CS_E_HIP, "%s: resize table upload failed", who); }
@@ -101,10 +126,37 @@ struct PlanCache {
         *out = &(plans[{H, W}] = p);
         return CS_OK;
     }
+    // the plan of an H x W mode-"F" image resized straight to out x out (clean-fid's resize): both axes independent, no crop window, double taps
+    int get_float_plan(const char* who, int out_size, int H, int W, const FloatPlan** out) {
+        auto it = float_plans.find({H, W});
+        if (it != float_plans.end()) { *out = &it->second; return CS_OK; }
+        if (H < 1 || W < 1 || out_size < 1) CS_FAIL(CS_E_SHAPE, "%s: bad image size %d x %d", who, H, W);
+        const TapsF64 th = pil_float_side(W, out_size), tv = pil_float_side(H, out_size);
+        // one allocation: the doubles first (8-byte aligned), then the ints
+        const size_t nd = th.kk.size() + tv.kk.size(), ni = 4 * (size_t)out_size;
+        std::vector<unsigned char> all(nd * sizeof(double) + ni * sizeof(int));
+        double* hd = (double*)all.data();
+        int* hi = (int*)(all.data() + nd * sizeof(double));
+        std::copy(th.kk.begin(), th.kk.end(), hd); std::copy(tv.kk.begin(), tv.kk.end(), hd + th.kk.size());
+        std::copy(th.lo.begin(), th.lo.end(), hi); std::copy(th.cnt.begin(), th.cnt.end(), hi + out_size);
+        std::copy(tv.lo.begin(), tv.lo.end(), hi + 2 * out_size); std::copy(tv.cnt.begin(), tv.cnt.end(), hi + 3 * out_size);
+        const int rc = make_room();
+        if (rc != CS_OK) return rc;
+        unsigned char* d = nullptr;
+        CS_CHECK_HIP(hipMalloc((void**)&d, all.size()));
+        if (hipMemcpy(d, all.data(), all.size(), hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(d); CS_FAIL(CS_E_HIP, "%s: resize table upload failed", who); }
+        plan_allocs.push_back(d);
+        const double* dd = (const double*)d;
+        const int* di = (const int*)(d + nd * sizeof(double));
+        FloatPlan p{};
+        p.dev = FidResizePlan{di, di + out_size, dd, th.ksize, di + 2 * out_size, di + 3 * out_size, dd + th.kk.size(), tv.ksize, out_size};
+        *out = &(float_plans[{H, W}] = p);
+        return CS_OK;
+    }
     // the owner's destroy: nothing reads a table any more
     void free_device() {
         for (void* p : plan_allocs) (void)hipFree(p);
-        plan_allocs.clear(); plans.clear();
+        plan_allocs.clear(); plans.clear(); float_plans.clear();
     }
 };
 

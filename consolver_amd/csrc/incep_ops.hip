@@ -293,14 +293,25 @@ int launch_incep_avgpool(const f16* x, int B, int H, int W, int C, f16* out, hip
     return CS_OK;
 }
 
+int launch_incep_mean(const f16* x, int B, long HW, int C, float* mean, hipStream_t s) {
+    if (!x || !mean) CS_FAIL(CS_E_ARG, "incep mean: null pointer");
+    if (B < 0 || HW < 1 || C < 8 || C % 8) CS_FAIL(CS_E_SHAPE, "incep mean: C %% 8 == 0 and positive sizes required");
+    if (B == 0) return CS_OK;
+    const long t1 = (long)B * (C / 8);
+    if (t1 > 0x7fffffffL * 256) CS_FAIL(CS_E_SHAPE, "incep mean: too large for one launch");
+    hipLaunchKernelGGL(incep_mean_kernel, dim3(blocks_for(t1)), dim3(256), 0, s, x, HW, C / 8, t1, mean);
+    CS_CHECK_LAUNCH();
+    return CS_OK;
+}
+
 int launch_incep_head(const f16* x, int B, long HW, int C, const f16* w, const float* bias, int N, float* mean, float* logits, hipStream_t s) {
     if (!x || !w || !mean || !logits) CS_FAIL(CS_E_ARG, "incep head: null pointer");
     if (B < 0 || HW < 1 || C < 8 || C % 8 || N < 1) CS_FAIL(CS_E_SHAPE, "incep head: C %% 8 == 0 and positive sizes required");
     if (B == 0) return CS_OK;
     const long t1 = (long)B * (C / 8), t2 = (long)B * N;
     if (t1 > 0x7fffffffL * 256 || (t2 + 3) / 4 > 0x7fffffffL) CS_FAIL(CS_E_SHAPE, "incep head: too large for one launch");
-    hipLaunchKernelGGL(incep_mean_kernel, dim3(blocks_for(t1)), dim3(256), 0, s, x, HW, C / 8, t1, mean);
-    CS_CHECK_LAUNCH();
+    const int rc = launch_incep_mean(x, B, HW, C, mean, s);
+    if (rc != CS_OK) return rc;
     hipLaunchKernelGGL(incep_fc_kernel, dim3((unsigned)((t2 + 3) / 4)), dim3(256), 0, s, mean, w, bias, C, N, t2, logits);
     CS_CHECK_LAUNCH();
     return CS_OK;

@@ -348,3 +348,25 @@ int launch_incep_maxpool(const f16* x, int B, int H, int W, int C, f16* out, lon
 int launch_incep_avgpool(const f16* x, int B, int H, int W, int C, f16* out, hipStream_t s);
 // mean [B][C] fp32 over the HW positions of x [B][HW][C], then logits [B][N] = mean w^T + bias (w fp16 [N][C], bias fp32 [N]): the mean is never rounded to fp16
 int launch_incep_head(const f16* x, int B, long HW, int C, const f16* w, const float* bias, int N, float* mean, float* logits, hipStream_t s);
+// the head's first half alone: mean [B][C] fp32 over the HW positions of x [B][HW][C] (the FID variant's pool3 features, fid.cpp)
+int launch_incep_mean(const f16* x, int B, long HW, int C, float* mean, hipStream_t s);
+
+// ---- FID (fid_ops.hip / fid.cpp): clean-fid's float resize, the 2015 graph's pools, fp64 feature statistics -----------------------------------------------
+// PIL's ImagingResample for mode-"F" images as device tables (image_front_end.h, PlanCache::get_float_plan): for every output column / row the first input
+// index, the tap count and the taps in double (normalised in double, never converted to fixed point); both axes independent, no crop window
+struct FidResizePlan {
+    const int *h_lo, *h_cnt; const double* h_kk; int h_ksize;
+    const int *v_lo, *v_cnt; const double* v_kk; int v_ksize;
+    int out;                                  // output side (299)
+};
+// images [B][3][H][W] (CS_U8, or CS_F16 / CS_F32 in [0, 1] quantised as round(clamp(x, 0, 1) * 255)) -> horizontal pass into tmp [B * 3][H][out] fp32, vertical
+// pass, clip to [0, 255] -> resized (optional) [B][3][out][out] fp32 and patches [B * out * out][8] fp16 = (v - mean[c]) / stdv[c], channels 3 .. 7 zero
+int launch_fid_front_end(const void* images, int dtype, int B, int H, int W, const FidResizePlan& pl, const float* mean, const float* stdv, float* tmp,
+                         f16* patches, float* resized, hipStream_t s);
+// 3x3 stride 1 pad 1 pools that leave the padding out: the average divides by the taps inside the image, the max is over them; C % 8 == 0; out must not alias x
+int launch_fid_avgpool(const f16* x, int B, int H, int W, int C, f16* out, hipStream_t s);
+int launch_fid_maxpool(const f16* x, int B, int H, int W, int C, f16* out, hipStream_t s);
+// sum[j] += sum_r f[r][j], outer[i][j] += sum_r f[r][i] f[r][j] in fp64 over f [n][d] fp32 (v_mfma_f64_16x16x4_f64); d % 16 == 0, 16 <= d <= 4096, n >= 1
+int launch_fid_stats_accumulate(const float* f, long n, int d, double* sum, double* outer, hipStream_t s);
+// mu = sum / N, sigma = (outer - N mu mu^T) / (N - 1); N >= 2
+int launch_fid_stats_finalize(const double* sum, const double* outer, long N, int d, double* mu, double* sigma, hipStream_t s);

@@ -189,3 +189,9 @@ def synthetic_flux_state_dict(manifest, seed=20251226, device="cpu", dtype=torch
                 w = w + 0.3
         sd[name] = w.to(dtype)
     return sd
+
+
+def synthetic_fid_inception_state_dict(manifest, seed=20260103):
+    """The FID Inception-v3 (``HipFIDInception.manifest()``: the inception manifest without ``fc``): the recipe of ``synthetic_inception_state_dict``; tests
+    calibrate the BatchNorm statistics on a batch first, as they do for the classifier."""
+    return synthetic_inception_state_dict(manifest, seed)

@@ -44,7 +44,7 @@ extern "C" {
 #define CS_MAX_ACTION_DIMS 16 /* order + scaler + mu - 1 */
 
 enum { CS_OK = 0, CS_E_ARG = -1, CS_E_SHAPE = -2, CS_E_DTYPE = -3, CS_E_HIP = -4, CS_E_STATE = -5, CS_E_UNSUPPORTED = -6 };
-enum { CS_F32 = 0, CS_F16 = 1, CS_BF16 = 2 };
+enum { CS_F32 = 0, CS_F16 = 1, CS_BF16 = 2, CS_U8 = 3 };   /* CS_U8: image input of cs_fid_preprocess only */
 
 int cs_abi_version(void);
 const char* cs_error_string(int code);
@@ -692,6 +692,50 @@ int cs_incep_forward(CsIncep* g, const void* patches, int batch, float* logits, 
                      void* stream);
 /* timing tools: cs_incep_forward returns after `parts` of (stem, Mixed_5, Mixed_6, Mixed_7, head); 5 (the default) runs everything, less leaves logits undefined */
 int cs_incep_set_stage_limit(CsIncep* g, int parts);
+
+/* ------------------------------------------------------------------------
+ * FID (the first column of the reference's results table; fid_test.py: cleanfid.fid.compute_fid(generated_dir, "coco/val2017")).
+ * Three pieces: clean-fid's resize (every channel a PIL mode-"F" image, BICUBIC straight to 299 x 299 in floating point, clipped to [0, 255]), the FID
+ * variant of Inception-v3 (pytorch-fid's pt_inception-2015-12-05: torchvision's state-dict names; 3x3 average pools that divide by the taps inside the
+ * image; a max pool in Mixed_7c's pool branch; the 2048-d pool3 output) and fp64 feature statistics.  cleanfid is not installed here: the 299, the clip and
+ * the (x - 128) / 128 default are restated from memory.
+ * ---------------------------------------------------------------------- */
+typedef struct CsFidConfig {
+    float image_mean[3];           /* 128, 128, 128: on the 0 .. 255 scale of the resized image */
+    float image_std[3];            /* 128, 128, 128 */
+} CsFidConfig;
+
+typedef struct CsFid CsFid;
+
+/* host only: builds the weight manifest (cs_incep_*'s without fc), touches no GPU */
+int cs_fid_create(const CsFidConfig* cfg, CsFid** out);
+void cs_fid_destroy(CsFid* g);
+/* as cs_incep_set_weight; "fc.*" (1008 classes in that checkpoint) and "AuxLogits.*" are accepted and ignored */
+int cs_fid_set_weight(CsFid* g, const char* name, const float* data_host, const int64_t* shape, int ndim);
+int cs_fid_num_weights(const CsFid* g);
+const char* cs_fid_weight_name(const CsFid* g, int i, int64_t* shape4, int* ndim);
+int cs_fid_finalize(CsFid* g);
+size_t cs_fid_workspace_bytes(const CsFid* g, int batch);
+double cs_fid_flops(const CsFid* g, int batch);
+int cs_fid_patch_cols(const CsFid* g);      /* 8 */
+int cs_fid_num_tokens(const CsFid* g);      /* 64: the last grid is 8 x 8 */
+size_t cs_fid_preprocess_workspace_bytes(const CsFid* g, int batch, int height, int width);
+/* images [batch, 3, height, width], CS_U8 or CS_F16 / CS_F32 in [0, 1] (quantised first as round(clamp(x, 0, 1) * 255), half to even), any height, width
+ * >= 1.  PIL's ImagingResample for 32-bit float images to 299 x 299: horizontal pass first, stored as fp32, then the vertical pass; double taps (not the
+ * 2^22 fixed point of the uint8 path), double accumulation ascending from xmin; a side that is 299 already is a copy.  The result is clipped to [0, 255];
+ * `patches` is ((v - image_mean[c]) / image_std[c]) as [batch * 299 * 299][8] fp16 (NHWC, channels 3 .. 7 zero).  resized_f32 (may be NULL): the clipped
+ * image before normalisation [batch, 3, 299, 299] fp32 */
+int cs_fid_preprocess(CsFid* g, const void* images, int dtype, int batch, int height, int width, void* patches, float* resized_f32,
+                      void* workspace, size_t workspace_bytes, void* stream);
+/* patches from cs_fid_preprocess -> the pool3 features [batch, 2048] fp32: the mean of the last 8 x 8 x 2048 grid, never rounded to fp16 */
+int cs_fid_forward(CsFid* g, const void* patches, int batch, float* features, void* workspace, size_t workspace_bytes, void* stream);
+
+/* feature statistics in fp64 (device pointers): sum[j] += sum_r f[r][j], outer[i][j] += sum_r f[r][i] f[r][j] over the n rows of feats [n][d] fp32; the whole
+ * symmetric matrix is written.  Every output element is owned by one workgroup that walks the rows in order (no atomics): a call is bitwise reproducible.
+ * d a multiple of 16 in 16 .. 4096, n >= 1: anything else is CS_E_SHAPE before a launch */
+int cs_fid_stats_accumulate(const float* feats, int64_t n, int d, double* sum, double* outer, void* stream);
+/* mu = sum / N, sigma = (outer - N mu mu^T) / (N - 1); N < 2 is refused (CS_E_SHAPE) */
+int cs_fid_stats_finalize(const double* sum, const double* outer, int64_t n_total, int d, double* mu, double* sigma, void* stream);
 
 #ifdef __cplusplus
 }

@@ -341,6 +341,12 @@ int cs_op_incep_avgpool(const void* x, int B, int H, int W, int C, void* out, vo
 /* head: mean [B][C] fp32 (scratch) = mean over the HW positions of x [B][HW][C]; logits [B][N] fp32 = mean w^T + bias; w fp16 [N][C], bias fp32 [N]; C % 8 == 0 */
 int cs_op_incep_head(const void* x, int B, int64_t HW, int C, const void* w, const float* bias, int N, float* mean, float* logits, void* stream);
 
+/* the pools of the FID Inception variant (csrc/fid_ops.hip; the 2015 TF graph's rules), 3x3 stride 1 pad 1 on NHWC fp16 x [B][H][W][C] -> out [B][H][W][C],
+ * C % 8 == 0, any H x W >= 1; out must not alias x.  Average: the sum in fp32 divided by the number of taps inside the image (count_include_pad = False: 4 at
+ * corners, 6 on edges, 9 inside), one rounding.  Max: over the taps inside the image (padding does not take part), exact */
+int cs_op_fid_avgpool(const void* x, int B, int H, int W, int C, void* out, void* stream);
+int cs_op_fid_maxpool(const void* x, int B, int H, int W, int C, void* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
