@@ -533,6 +533,8 @@ int launch_time_embedding(const float* t, int Bt, int C0, int D, const f16* w1, 
 int launch_conv_in(const f16* lat, int n_lat, int B, int Cin, int H, int W, const f16* w, const f16* bias, int Cout, f16* out, hipStream_t s, f16* out_lo) {
     if (!lat || !w || !bias || !out) CS_FAIL(CS_E_ARG, "conv_in: null pointer");
     if (Cin != 4 || Cout % 8) CS_FAIL(CS_E_UNSUPPORTED, "conv_in: built for 4 input channels (got %d)", Cin);
+    // the [36][Cout] weight table is dynamic LDS: 64 KB is what a launch gets without opting in to more
+    if (Cout <= 0 || (size_t)36 * Cout * sizeof(f16) > 65536) CS_FAIL(CS_E_SHAPE, "conv_in: Cout=%d unsupported (the weight table must fit 64 KB of LDS)", Cout);
     if (B <= 0) return CS_OK;
     const long total = (long)B * H * W;
     int grid = (int)((total + 255) / 256); if (grid > 4096) grid = 4096;

@@ -412,6 +412,50 @@ int cs_op_layer_norm(const void* x, const void* gamma, const void* beta, void* o
     return launch_layer_norm((const f16*)x, (const f16*)gamma, (const f16*)beta, (f16*)out, M, C, eps, (hipStream_t)stream);
 }
 
+// ---- the small ops at the edges of the denoiser, the VAE and the CLIP text encoder: one launcher call each ----
+int cs_op_time_embedding(const float* t, int Bt, int C0, int D, const void* w1, const void* b1, const void* w2, const void* b2, void* scratch, void* out,
+                         void* stream) {
+    return launch_time_embedding(t, Bt, C0, D, (const f16*)w1, (const f16*)b1, (const f16*)w2, (const f16*)b2, (f16*)scratch, (f16*)out, (hipStream_t)stream);
+}
+int cs_op_rowvec_linear(const void* x, int R, int K, const void* w, const void* bias, int N, void* out, int act_silu, void* stream) {
+    return launch_rowvec_linear((const f16*)x, R, K, (const f16*)w, (const f16*)bias, N, (f16*)out, act_silu, (hipStream_t)stream);
+}
+int cs_op_conv_in(const void* lat, int n_lat, int B, int H, int W, const void* w_packed, const void* bias, int Cout, void* out, void* out_lo, void* stream) {
+    return launch_conv_in((const f16*)lat, n_lat, B, 4, H, W, (const f16*)w_packed, (const f16*)bias, Cout, (f16*)out, (hipStream_t)stream, (f16*)out_lo);
+}
+int cs_op_embed_tokens(const int64_t* ids, const void* tok, const void* pos, void* out, int64_t rows, int L, int C, int vocab, void* stream) {
+    return launch_embed_tokens(ids, (const f16*)tok, (const f16*)pos, (f16*)out, (long)rows, L, C, vocab, (hipStream_t)stream);
+}
+int cs_op_quick_gelu(void* x, int64_t n, void* stream) { return launch_quick_gelu((f16*)x, (long)n, (hipStream_t)stream); }
+int cs_op_gelu_erf(void* x, int64_t n, void* stream) { return launch_gelu_erf((f16*)x, (long)n, (hipStream_t)stream); }
+int cs_op_row_softmax(void* x, int64_t rows, int cols, float scale, void* stream) { return launch_row_softmax((f16*)x, (long)rows, cols, scale, (hipStream_t)stream); }
+int cs_op_latent_to_nhwc64(const void* x, const void* w, const void* b, void* out, int B, int C, int HW, float in_scale, float in_shift, void* stream) {
+    return launch_latent_to_nhwc64((const f16*)x, (const f16*)w, (const f16*)b, (f16*)out, B, C, HW, in_scale, in_shift, (hipStream_t)stream);
+}
+int cs_op_pixel_linear(const void* x, const void* w, const void* b, void* out, int B, int C, int HW, float in_scale, float in_shift, void* stream) {
+    return launch_pixel_linear_nchw((const f16*)x, (const f16*)w, (const f16*)b, (f16*)out, B, C, HW, in_scale, in_shift, (hipStream_t)stream);
+}
+int cs_op_pixel_affine(const void* x, int Cin, const void* w, const void* b, int Cout, void* out, int B, int HW, float out_scale, float out_shift, void* stream) {
+    return launch_pixel_affine_nchw((const f16*)x, Cin, (const f16*)w, (const f16*)b, Cout, (f16*)out, B, HW, out_scale, out_shift, (hipStream_t)stream);
+}
+// the AutoencoderKL encoder's downsample: 3x3, stride 2, pad (0, 1, 0, 1)
+int cs_op_conv_down(const void* x, int Cin, int B, int Hi, int Wi, const void* w_packed, const void* bias, int N, void* out, void* stream) {
+    IgemmArgs a{};
+    a.a0 = (const f16*)x; a.c0 = Cin; a.B = B; a.Hi = Hi; a.Wi = Wi; a.Ho = Hi / 2; a.Wo = Wi / 2; a.taps = 9; a.stride = 2; a.pad_after_only = 1;
+    a.N = N; a.w = (const f16*)w_packed; a.bias = (const f16*)bias; a.out = (f16*)out;
+    return launch_igemm(a, (hipStream_t)stream);
+}
+size_t cs_op_group_norm_workspace_splits(int B, int C, int splits) {
+    return (((size_t)B * ((splits > 0 ? splits : GN_SPLITS) + 1) * C * 2 * sizeof(float)) + 255) & ~(size_t)255;
+}
+int cs_op_group_norm_splits(const void* x0, int c0, const void* x1, int c1, int B, int HW, int groups, float eps, int silu,
+                            const void* gamma, const void* beta, void* workspace, void* out, int splits, void* stream) {
+    GroupNormArgs a{};
+    a.x0 = (const f16*)x0; a.x1 = (const f16*)x1; a.c0 = c0; a.c1 = c1; a.B = B; a.HW = HW; a.groups = groups; a.eps = eps; a.silu = silu;
+    a.gamma = (const f16*)gamma; a.beta = (const f16*)beta; a.partial = (float*)workspace; a.out = (f16*)out; a.splits = splits;
+    return launch_group_norm(a, (hipStream_t)stream);
+}
+
 int cs_debug_trace_read(void* dst_host, size_t bytes) { return debug_trace_read(dst_host, bytes); }
 int cs_debug_attn_trace_read(void* dst_host, size_t bytes) { return debug_attn_trace_read(dst_host, bytes); }
 

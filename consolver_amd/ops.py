@@ -341,6 +341,133 @@ def group_norm(x0, gamma, beta, groups=32, eps=1e-5, silu=False, x1=None, stats0
     return out
 
 
+def group_norm_splits(x0, gamma, beta, splits, groups=32, eps=1e-5, silu=False, x1=None, out=None, ws=None):
+    """group_norm with the statistics pass over up to ``splits`` row ranges per sample (cs_op_group_norm_splits; the VAE runs 256); ``ws``: the caller's workspace
+    of cs_op_group_norm_workspace_splits(B, C, splits) bytes (tests read the partial sums back from it)"""
+    _f16(x0, "x0")
+    B = x0.shape[0]
+    c0 = x0.shape[-1]
+    c1 = x1.shape[-1] if x1 is not None else 0
+    HW = x0.numel() // (B * c0)
+    if ws is None:
+        ws = torch.empty(int(L.lib().cs_op_group_norm_workspace_splits(B, c0 + c1, int(splits))), dtype=torch.uint8, device=x0.device)
+    if out is None:
+        out = torch.empty(x0.shape[:-1] + (c0 + c1,), dtype=torch.float16, device=x0.device)
+    L.check(L.lib().cs_op_group_norm_splits(L.ptr(x0), c0, L.ptr(x1), c1, B, HW, groups, float(eps), int(silu), L.ptr(gamma), L.ptr(beta), L.ptr(ws), L.ptr(out),
+                                            int(splits), L.stream_ptr(x0.device)))
+    return out
+
+
+# ---- the small ops at the edges of the denoiser, the VAE and the CLIP text encoder (csrc/misc.hip).  ``out``: a preallocated result (tests: a view into a
+# NaN-filled buffer) ----
+def time_embedding(t, w1, b1, w2, b2, out=None, scratch=None):
+    """t fp32 [Bt] -> (out [Bt, D], scratch): silu(linear_2(silu(linear_1(sinusoid(t))))); scratch [Bt * C0 + Bt * D] holds the sinusoid and the hidden layer"""
+    L.require_cuda(t, "t")
+    Bt, (D, C0) = t.shape[0], w1.shape
+    if out is None:
+        out = torch.empty(Bt, D, dtype=torch.float16, device=t.device)
+    if scratch is None:
+        scratch = torch.empty(Bt * (C0 + D), dtype=torch.float16, device=t.device)
+    L.check(L.lib().cs_op_time_embedding(L.ptr(t), Bt, C0, D, L.ptr(w1), L.ptr(b1), L.ptr(w2), L.ptr(b2), L.ptr(scratch), L.ptr(out), L.stream_ptr(t.device)))
+    return out, scratch
+
+
+def rowvec_linear(x, w, bias=None, silu=False, out=None):
+    _f16(x, "x")
+    R, K = x.shape
+    N = w.shape[0]
+    if out is None:
+        out = torch.empty(R, N, dtype=torch.float16, device=x.device)
+    L.check(L.lib().cs_op_rowvec_linear(L.ptr(x), R, K, L.ptr(w), L.ptr(bias), N, L.ptr(out), int(silu), L.stream_ptr(x.device)))
+    return out
+
+
+def conv_in(lat, w_packed, bias, B=None, want_lo=False, out=None, out_lo=None):
+    """lat NCHW [n_lat, 4, H, W] -> NHWC [B, H, W, Cout] (sample b reads latent b % n_lat); want_lo / out_lo: also the lo plane of the split-fp16 output"""
+    _f16(lat, "lat")
+    n_lat, _, H, W = lat.shape
+    B = n_lat if B is None else B
+    Cout = w_packed.shape[0]
+    if out is None:
+        out = torch.empty(B, H, W, Cout, dtype=torch.float16, device=lat.device)
+    if want_lo and out_lo is None:
+        out_lo = torch.empty(B, H, W, Cout, dtype=torch.float16, device=lat.device)
+    L.check(L.lib().cs_op_conv_in(L.ptr(lat), n_lat, B, H, W, L.ptr(w_packed), L.ptr(bias), Cout, L.ptr(out), L.ptr(out_lo), L.stream_ptr(lat.device)))
+    return (out, out_lo) if out_lo is not None else out
+
+
+def embed_tokens(ids, tok, pos, out=None):
+    """ids int64 [rows] -> tok[clamp(ids)] + pos[r % L]: [rows, C]"""
+    L.require_cuda(ids, "ids")
+    rows, (vocab, Cc), Lp = ids.numel(), tok.shape, pos.shape[0]
+    if out is None:
+        out = torch.empty(rows, Cc, dtype=torch.float16, device=ids.device)
+    L.check(L.lib().cs_op_embed_tokens(L.ptr(ids), L.ptr(tok), L.ptr(pos), L.ptr(out), rows, Lp, Cc, vocab, L.stream_ptr(ids.device)))
+    return out
+
+
+def quick_gelu_(x, n=None):
+    """in place on the first n elements (default all)"""
+    _f16(x, "x")
+    L.check(L.lib().cs_op_quick_gelu(L.ptr(x), x.numel() if n is None else n, L.stream_ptr(x.device)))
+    return x
+
+
+def gelu_erf_(x, n=None):
+    _f16(x, "x")
+    L.check(L.lib().cs_op_gelu_erf(L.ptr(x), x.numel() if n is None else n, L.stream_ptr(x.device)))
+    return x
+
+
+def row_softmax_(x, scale=1.0):
+    """x [rows, cols] <- softmax(scale * x) in place"""
+    _f16(x, "x")
+    rows, cols = x.shape
+    L.check(L.lib().cs_op_row_softmax(L.ptr(x), rows, cols, float(scale), L.stream_ptr(x.device)))
+    return x
+
+
+def latent_to_nhwc64(x, w=None, b=None, in_scale=1.0, in_shift=0.0, out=None):
+    """NCHW x [B, C, HW] -> NHWC [B, HW, 64]: x * in_scale + in_shift [-> w z + b], channels C .. 63 zero"""
+    _f16(x, "x")
+    B, Cc, HW = x.shape
+    if out is None:
+        out = torch.empty(B, HW, 64, dtype=torch.float16, device=x.device)
+    L.check(L.lib().cs_op_latent_to_nhwc64(L.ptr(x), L.ptr(w), L.ptr(b), L.ptr(out), B, Cc, HW, float(in_scale), float(in_shift), L.stream_ptr(x.device)))
+    return out
+
+
+def pixel_linear(x, w, b, in_scale=1.0, in_shift=0.0, out=None):
+    """NCHW x [B, C, HW] -> [B, C, HW]: w (x * in_scale + in_shift) + b per pixel"""
+    _f16(x, "x")
+    B, Cc, HW = x.shape
+    if out is None:
+        out = torch.empty_like(x)
+    L.check(L.lib().cs_op_pixel_linear(L.ptr(x), L.ptr(w), L.ptr(b), L.ptr(out), B, Cc, HW, float(in_scale), float(in_shift), L.stream_ptr(x.device)))
+    return out
+
+
+def pixel_affine(x, Cout, w=None, b=None, out_scale=1.0, out_shift=0.0, out=None):
+    """NCHW x [B, Cin, HW] -> [B, Cout, HW]: ((w x + b) - out_shift) * out_scale per pixel; w None: the first Cout channels of x"""
+    _f16(x, "x")
+    B, Cin, HW = x.shape
+    if out is None:
+        out = torch.empty(B, Cout, HW, dtype=torch.float16, device=x.device)
+    L.check(L.lib().cs_op_pixel_affine(L.ptr(x), Cin, L.ptr(w), L.ptr(b), Cout, L.ptr(out), B, HW, float(out_scale), float(out_shift), L.stream_ptr(x.device)))
+    return out
+
+
+def conv_down(x, w_packed, bias=None, out=None):
+    """3x3 stride-2 conv padded (0, 1, 0, 1) (cs_op_conv_down): NHWC x [B, Hi, Wi, Cin] -> [B, Hi / 2, Wi / 2, N]"""
+    _f16(x, "x")
+    B, Hi, Wi, Cin = x.shape
+    N = w_packed.shape[0]
+    if out is None:
+        out = torch.empty(B, Hi // 2, Wi // 2, N, dtype=torch.float16, device=x.device)
+    L.check(L.lib().cs_op_conv_down(L.ptr(x), Cin, B, Hi, Wi, L.ptr(w_packed), L.ptr(bias), N, L.ptr(out), L.stream_ptr(x.device)))
+    return out
+
+
 def layer_norm(x, gamma, beta, eps=1e-5):
     _f16(x, "x")
     M, Cc = x.shape

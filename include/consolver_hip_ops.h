@@ -347,6 +347,39 @@ int cs_op_incep_head(const void* x, int B, int64_t HW, int C, const void* w, con
 int cs_op_fid_avgpool(const void* x, int B, int H, int W, int C, void* out, void* stream);
 int cs_op_fid_maxpool(const void* x, int B, int H, int W, int C, void* out, void* stream);
 
+/* ---- the small ops at the edges of the SD1.5 denoiser, the VAE and the CLIP text encoder (csrc/misc.hip), fp16 device pointers unless noted; exported so that
+ * tests/test_edge_ops_gpu.py can compare each with float64 on its own.
+ * Time embedding: sinusoid [cos | sin] of t [Bt] fp32 over C0 channels (flip_sin_to_cos, shift 0, stored fp16) -> Linear(C0, D) + SiLU -> Linear(D, D) + SiLU
+ * -> out [Bt][D].  scratch: [Bt][C0] + [Bt][D] halfs; it holds the sinusoid and the hidden layer afterwards.  C0 and D multiples of 8. */
+int cs_op_time_embedding(const float* t, int Bt, int C0, int D, const void* w1, const void* b1, const void* w2, const void* b2, void* scratch, void* out,
+                         void* stream);
+/* out[R][N] = [silu](x[R][K] w[N][K]^T + bias[N]) for a few rows; bias may be NULL; K % 8 == 0 */
+int cs_op_rowvec_linear(const void* x, int R, int K, const void* w, const void* bias, int N, void* out, int act_silu, void* stream);
+/* conv_in: 3x3 pad 1 over NCHW latents [n_lat][4][H][W] -> NHWC out [B][H][W][Cout]; sample b reads latent b % n_lat; w_packed [Cout][9][4]; Cout % 8 == 0 and
+ * 72 Cout bytes of weights within 64 KB (CS_E_SHAPE otherwise).  out_lo (may be NULL) receives f16(v - float(f16(v))) of the fp32 value v. */
+int cs_op_conv_in(const void* lat, int n_lat, int B, int H, int W, const void* w_packed, const void* bias, int Cout, void* out, void* out_lo, void* stream);
+/* out[r][:] = tok[clamp(ids[r], 0, vocab - 1)][:] + pos[r % L][:]; ids int64 [rows]; C % 8 == 0 */
+int cs_op_embed_tokens(const int64_t* ids, const void* tok, const void* pos, void* out, int64_t rows, int L, int C, int vocab, void* stream);
+/* in place on x [n], n % 8 == 0: x sigmoid(1.702 x); 0.5 x (1 + erf(x / sqrt 2)) */
+int cs_op_quick_gelu(void* x, int64_t n, void* stream);
+int cs_op_gelu_erf(void* x, int64_t n, void* stream);
+/* x [rows][cols] <- softmax(scale * x) along cols, in place; cols % 8 == 0, cols <= 65536 */
+int cs_op_row_softmax(void* x, int64_t rows, int cols, float scale, void* stream);
+/* NCHW x [B][C][HW], C <= 64: z = x * in_scale + in_shift, then w [C][C] z + b when w is not NULL, -> NHWC out [B][HW][64] with the channels C .. 63 zero */
+int cs_op_latent_to_nhwc64(const void* x, const void* w, const void* b, void* out, int B, int C, int HW, float in_scale, float in_shift, void* stream);
+/* NCHW -> NCHW per pixel: out = w [C][C] (x * in_scale + in_shift) + b */
+int cs_op_pixel_linear(const void* x, const void* w, const void* b, void* out, int B, int C, int HW, float in_scale, float in_shift, void* stream);
+/* NCHW [B][Cin][HW] -> [B][Cout][HW] per pixel: out = ((w [Cout][Cin] x + b) - out_shift) * out_scale; w NULL: the first Cout channels of x (Cout <= Cin) */
+int cs_op_pixel_affine(const void* x, int Cin, const void* w, const void* b, int Cout, void* out, int B, int HW, float out_scale, float out_shift, void* stream);
+/* 3x3 stride-2 conv with the padding after the image only (F.pad(x, (0, 1, 0, 1)) + Conv2d(3, stride 2, pad 0): the AutoencoderKL encoder's downsample):
+ * NHWC x [B][Hi][Wi][Cin] -> out [B][Hi / 2][Wi / 2][N]; same kernels and shape rules as cs_op_conv2d */
+int cs_op_conv_down(const void* x, int Cin, int B, int Hi, int Wi, const void* w_packed, const void* bias, int N, void* out, void* stream);
+/* cs_op_group_norm with the statistics pass over up to `splits` row ranges per sample (a power of two; the VAE runs 256, cs_op_group_norm 16);
+ * workspace: cs_op_group_norm_workspace_splits(B, c0 + c1, splits) bytes */
+size_t cs_op_group_norm_workspace_splits(int B, int C, int splits);
+int cs_op_group_norm_splits(const void* x0, int c0, const void* x1, int c1, int B, int HW, int groups, float eps, int silu,
+                            const void* gamma, const void* beta, void* workspace, void* out, int splits, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
