@@ -277,6 +277,7 @@ SYMBOLS = {
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "cs_debug_trace_read": (C.c_int, [C.c_void_p, C.c_size_t]),
     "cs_debug_attn_trace_read": (C.c_int, [C.c_void_p, C.c_size_t]),
+    "cs_debug_igemm_last_route": (C.c_int, [C.POINTER(C.c_int), C.c_int]),
     "cs_op_layer_norm": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p]),
     "cs_op_clipv_tokens_ln": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "cs_op_clipv_head": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),

@@ -175,8 +175,9 @@ __device__ __forceinline__ void glds16(const void* src, void* lds_wave_base) {
 
 // erf GELU (diffusers GEGLU uses F.gelu, approximate='none'): x Phi(x), Phi(x) = 1/2 + x Q(x^2) with Q a degree-9 polynomial
 // fitted on |x| <= 4.5 (Chebyshev nodes) and x clamped to that range (Phi(+-4.5) = 1 - 3.4e-6 / 3.4e-6).  Max abs error of the
-// GELU value 8.2e-5 over all x (at the clamp, where the true value is ~ -1.5e-5) -- an order below the fp16 rounding of the
-// product that follows.  Two values per call so that the Horner chain is v_pk_fma_f32: ~7 VALU issue slots per value and no
+// GELU value 8.2e-5 for |x| <= 10.6 (at the clamp, where the true value is ~ -1.5e-5) -- an order below the fp16 rounding of the
+// product that follows; beyond the clamp Phi stays at Phi_poly(-4.5) = 7.75e-6 (resp. 1 - 7.75e-6), an error of |x| 7.75e-6.
+// Two values per call so that the Horner chain is v_pk_fma_f32: ~7 VALU issue slots per value and no
 // transcendental, against ~22 for the rcp + exp form (A&S 7.1.26) it replaces: the GEGLU epilogue evaluates this 168 M
 // times per L0 layer and was VALU-bound.
 // Two pairs per call, their Horner chains interleaved statement by statement: one chain alone is a string of DEPENDENT v_pk_fma_f32, and hipcc put an s_nop between
@@ -2186,6 +2187,8 @@ template <bool UP, int BN, int KH>
 static int launch_halo(const HaloParams& h, dim3 grid, size_t lds, hipStream_t s) { return launch_halo_sched<UP, BN, KH, KH == 2 ? 2 : 0>(h, grid, lds, s); }
 
 struct LaunchInfo { bool gn_done = false; int row_groups = 0; };    // what the chosen kernel's epilogue left: GroupNorm statistics / row statistics in N / row_groups-column groups
+// the route record of this launch (IgemmRoute, ops.h): one host store per launch site
+static inline void route_set(int family, int tile_cols, int variant, int splits = 1) { t_igemm_route.family = family; t_igemm_route.tile_cols = tile_cols; t_igemm_route.variant = variant; t_igemm_route.splits = splits; }
 static int launch_igemm_impl(const IgemmArgs& a, hipStream_t s, LaunchInfo* li) {
     const int cin = a.c0 + a.c1;
     if (!a.a0 || !a.w || !a.out) CS_FAIL(CS_E_ARG, "igemm: a0, w, out required");
@@ -2271,7 +2274,9 @@ static int launch_igemm_impl(const IgemmArgs& a, hipStream_t s, LaunchInfo* li) 
             configured_sub = true;
         }
         const size_t llw = 2 * ((size_t)h.NQ * 1024) + 3 * ((size_t)sbn * 128);
-        hipLaunchKernelGGL(sub[sbn == 128 ? 2 : f1 ? 0 : 1], dim3(h.e.nblk, 1), dim3(512), llw, s, h);
+        const int sv = sbn == 128 ? 2 : f1 ? 0 : 1;
+        route_set(4, sbn, sv);
+        hipLaunchKernelGGL(sub[sv], dim3(h.e.nblk, 1), dim3(512), llw, s, h);
         CS_CHECK_LAUNCH();
         li->gn_done = stats_ok;
         return CS_OK;
@@ -2311,6 +2316,7 @@ static int launch_igemm_impl(const IgemmArgs& a, hipStream_t s, LaunchInfo* li) 
             const size_t l = 2 * (HALO_ROWS_MAX * 128) + 3 * ((size_t)hbn * (wide ? 64 : 128));
             const dim3 grid(h.e.nblk, splits);
             int rc;
+            route_set(2, hbn, a.upsample ? 1 : 0, splits);         // (conv3_lw_kernel: overwritten below)
             if (lw) {
                 constexpr size_t llw_max = 2 * (HALO_ROWS_MAX * 128) + 3 * (160 * 128);      // = 160 KiB exactly: the whole LDS of a CU
                 const size_t llw = 2 * ((size_t)h.NQ * 1024) + 3 * ((size_t)hbn * 128);
@@ -2331,11 +2337,9 @@ static int launch_igemm_impl(const IgemmArgs& a, hipStream_t s, LaunchInfo* li) 
                 }
                 auto launch = [&](lw_fn kfn) -> int { hipLaunchKernelGGL(kfn, grid, dim3(512), llw, s, h); return CS_OK; };
                 const bool trace = (tune().debug & 16384) && !a.upsample;    // timing experiments: the stamped instantiations (plain conv only)
-                if (fast8) rc = launch(variants[10]);
-                else if (hbn == 128) rc = launch(variants[a.upsample ? (fast ? 9 : 8) : (fast ? 6 : 7)]);
-                else if (trace) rc = launch(variants[fast ? 3 : 4]);
-                else if (a.upsample) rc = launch(variants[fast ? 5 : 2]);
-                else rc = launch(variants[fast ? 0 : 1]);
+                const int lv = fast8 ? 10 : hbn == 128 ? (a.upsample ? (fast ? 9 : 8) : (fast ? 6 : 7)) : trace ? (fast ? 3 : 4) : a.upsample ? (fast ? 5 : 2) : (fast ? 0 : 1);
+                route_set(3, hbn, lv, splits);
+                rc = launch(variants[lv]);
                 if (rc != CS_OK) return rc;
                 rc = CS_OK;
             } else if (wide && hbn == 320) rc = a.upsample ? launch_halo<true, 320, 2>(h, grid, l, s) : launch_halo<false, 320, 2>(h, grid, l, s);
@@ -2352,7 +2356,9 @@ static int launch_igemm_impl(const IgemmArgs& a, hipStream_t s, LaunchInfo* li) 
     if (a.geglu && conv3) CS_FAIL(CS_E_ARG, "igemm: GEGLU epilogue only for linear layers");
     if (tune().biggemm && !conv3 && a.N % 320 == 0) {
         const int tiles_m = (p.M + 255) / 256, tn = a.N / 320;
-        if (tiles_m * tn >= 192 || tune().biggemm == 2) {
+        // (GEGLU with N % 128 != 0 -- 320, 960, ...: the generic tiles below cannot take it (igemm_kernel's GEGLU form is the 128-column one), so it runs here
+        //  whatever the tile count)
+        if (tiles_m * tn >= 192 || tune().biggemm == 2 || (a.geglu && a.N % 128)) {
             p.tiles_n = tn; p.nblk = tiles_m * tn; p.pn = choose_xcd_grid(tiles_m, tn, a_bytes, w_bytes); li->gn_done = stats_ok; li->row_groups = a.N / 160;      // gemm_w8 / gemm_big<., 320>: 64 x 160 wave tiles
             p.gm = tune().gemm_gm >= 0 ? (tune().gemm_gm > 1 ? tune().gemm_gm : 1) : (tn >= 12 ? 4 : 1);
             constexpr size_t lds = 2 * (256 * BK * 2 + 320 * BK * 2);
@@ -2374,10 +2380,13 @@ static int launch_igemm_impl(const IgemmArgs& a, hipStream_t s, LaunchInfo* li) 
                     for (w8_fn f : w8) CS_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(f), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(lds + LN_LDS_W8)));
                     configured_w8 = true;
                 }
-                hipLaunchKernelGGL(w8[epi == 1 ? (lnm == 2 ? 6 : 5) : (epi == 2 && lnm == 0) ? 7 : lnm == 2 ? 4 : 2 * lnm + (a.geglu ? 1 : 0)], dim3(p.nblk), dim3(512), lds + LN_LDS_W8, s, p);
+                const int wv = epi == 1 ? (lnm == 2 ? 6 : 5) : (epi == 2 && lnm == 0) ? 7 : lnm == 2 ? 4 : 2 * lnm + (a.geglu ? 1 : 0);
+                route_set(6, 320, wv);
+                hipLaunchKernelGGL(w8[wv], dim3(p.nblk), dim3(512), lds + LN_LDS_W8, s, p);
                 CS_CHECK_LAUNCH();
                 return CS_OK;
             }
+            route_set(5, 320, a.geglu ? 1 : 0);
             if (a.geglu) hipLaunchKernelGGL((gemm_big_kernel<true, 320>), dim3(p.nblk), dim3(512), lds, s, p);
             else hipLaunchKernelGGL((gemm_big_kernel<false, 320>), dim3(p.nblk), dim3(512), lds, s, p);
             CS_CHECK_LAUNCH();
@@ -2406,10 +2415,13 @@ static int launch_igemm_impl(const IgemmArgs& a, hipStream_t s, LaunchInfo* li) 
                     for (lw_fn f : lwk) CS_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(f), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(lds_lw + LN_LDS_LW)));
                     configured_lw = true;
                 }
-                hipLaunchKernelGGL(lwk[epi == 1 ? (lnm == 2 ? 4 : 3) : (epi == 2 && lnm == 0) ? 5 : lnm], dim3(p.nblk), dim3(512), lds_lw + LN_LDS_LW, s, p);
+                const int kv = epi == 1 ? (lnm == 2 ? 4 : 3) : (epi == 2 && lnm == 0) ? 5 : lnm;
+                route_set(7, 160, kv);
+                hipLaunchKernelGGL(lwk[kv], dim3(p.nblk), dim3(512), lds_lw + LN_LDS_LW, s, p);
                 CS_CHECK_LAUNCH();
                 return CS_OK;
             }
+            route_set(5, 160, 0);
             hipLaunchKernelGGL((gemm_big_kernel<false, 160>), dim3(p.nblk), dim3(512), lds, s, p);
             CS_CHECK_LAUNCH();
             return CS_OK;
@@ -2418,6 +2430,10 @@ static int launch_igemm_impl(const IgemmArgs& a, hipStream_t s, LaunchInfo* li) 
 generic_tiles:
     p.tiles_n = a.N / bn; p.nblk = tiles_m * p.tiles_n; p.gm = 1; p.pn = choose_xcd_grid(tiles_m, p.tiles_n, a_bytes, w_bytes); li->gn_done = false; li->row_groups = 0;
     if (a.geglu) {
+        // the GEGLU form of igemm_kernel is the 128-column one: with N % 128 != 0 (tiles_n counts 160-column tiles) it would leave the columns behind
+        // 128 tiles_n unwritten
+        if (a.N % 128) CS_FAIL(CS_E_SHAPE, "igemm: GEGLU with N %% 128 != 0 (N=%d) needs the 256 x 320 tiles (knob gemm_big != 0)", a.N);
+        route_set(1, 128, (lnm == 1 ? 1 : 0) | 16);
         return lnm == 1 ? launch_variant<128, false, true, 1>(p, s) : launch_variant<128, false, true>(p, s);
     }
     // few tiles and a long k loop (stride-2 convs into the 16 x 16 / 8 x 8 levels, the 8 x 8 linears): split K to fill the chip
@@ -2429,8 +2445,9 @@ generic_tiles:
     }
     li->gn_done = stats_ok && (splits == 1 || reduce_leaves_stats(p));
     li->row_groups = (splits == 1 && !conv3) ? a.N / (bn / 2) : 0;          // igemm_kernel: 64 x bn / 2 wave tiles; the split-K reduce leaves no row statistics
-    if (conv3) return bn == 128 ? launch_variant<128, true, false>(p, s, splits) : launch_variant<160, true, false>(p, s, splits);
     const int lk = splits > 1 ? 0 : lnm;            // (split-K: raw partial sums leave the main kernel; the reduce kernel applies a folded LayerNorm itself)
+    route_set(1, bn, conv3 ? 32 : (lk | ((epi == 1 && splits == 1) ? 1 << 2 : 0)), splits);
+    if (conv3) return bn == 128 ? launch_variant<128, true, false>(p, s, splits) : launch_variant<160, true, false>(p, s, splits);
     if (epi == 1 && splits == 1) {                  // byte planes (split-K: the reduce kernel handles the planes, the main kernel writes raw partial sums)
         if (bn == 128) return lk == 2 ? launch_variant<128, false, false, 2, 1>(p, s, splits) : launch_variant<128, false, false, 0, 1>(p, s, splits);
         return lk == 2 ? launch_variant<160, false, false, 2, 1>(p, s, splits) : launch_variant<160, false, false, 0, 1>(p, s, splits);
@@ -2441,7 +2458,9 @@ generic_tiles:
 
 int launch_igemm(const IgemmArgs& a, hipStream_t s) {
     LaunchInfo li;
+    t_igemm_route = IgemmRoute();
     const int rc = launch_igemm_impl(a, s, &li);
+    t_igemm_route.gn_done = li.gn_done ? 1 : 0; t_igemm_route.row_groups = a.row_stats ? li.row_groups : 0;
     if (rc != CS_OK) return rc;
     if (a.row_stats) {                              // row statistics for a LayerNorm folded into the consumer: by the epilogue, else a pass over the output
         if (li.row_groups > 0) *a.row_stats_groups = li.row_groups;
@@ -2449,14 +2468,16 @@ int launch_igemm(const IgemmArgs& a, hipStream_t s) {
             const int M = a.B * a.Ho * a.Wo;
             hipLaunchKernelGGL(row_stats_kernel, dim3((M + 3) / 4), dim3(256), 0, s, (const f16*)a.out, (const f16*)a.out_lo, M, a.N, a.row_stats, a.lo8);
             CS_CHECK_LAUNCH();
-            *a.row_stats_groups = 1;
+            *a.row_stats_groups = 1; t_igemm_route.fallback |= 2;
         }
     }
     if (!a.gn_stats || li.gn_done) return rc;
     // the chosen kernel has no statistics epilogue (split-K forms) or the knob is off: a statistics pass over the output, same layout
     if (a.geglu || (a.Ho * a.Wo) % 64) CS_FAIL(CS_E_ARG, "igemm: gn_stats needs Ho * Wo %% 64 == 0 and no GEGLU");
+    t_igemm_route.fallback |= 1;
     return launch_gn_stats64(a.out, a.B, a.Ho * a.Wo, a.N, a.gn_stats, s);
 }
+
 
 // cs_unet_calibrate_ln_fold: *dst += sum over rows of mean^2 / (var + eps) from the row statistics rs[M][G][2] a producer left (IgemmArgs::row_stats) -- how many sigma
 // the rows of a hidden state sit away from zero.  A threshold decision: the order of the float atomics does not matter.

@@ -119,6 +119,12 @@ inline bool igemm_sub_pixel(const IgemmArgs& a, const TuneSet& t) {
         return false;
     return (a.Hi % 16 == 0 && a.Wi % 16 == 0 && (a.N % 160 == 0 || a.N % 128 == 0)) || (a.Hi == 8 && a.Wi == 8 && a.N % 160 == 0);
 }
+// Which kernel the calling thread's last launch_igemm took (cs_debug_igemm_last_route; tests assert the dispatch with it).  Host only: one store per launch.
+// family: 0 nothing launched, 1 igemm_kernel, 2 conv3_halo_kernel, 3 conv3_lw_kernel, 4 conv3_lw_kernel in the sub-pixel form, 5 gemm_big_kernel, 6 gemm_w8_kernel,
+// 7 gemm_lw_kernel.  variant: the index into the site's function-pointer table (variants / sub / w8 / lwk); igemm_kernel: LNM | EPI << 2 | GEGLU << 4 | CONV3 << 5;
+// conv3_halo_kernel: 1 with the fused upsample; gemm_big_kernel: 1 with GEGLU.  fallback: bit 0 launch_gn_stats64 ran behind the launch, bit 1 row_stats_kernel.
+struct IgemmRoute { int family = 0, tile_cols = 0, variant = 0, splits = 1, gn_done = 0, row_groups = 0, fallback = 0; };
+extern thread_local IgemmRoute t_igemm_route;      // (defined in ops_api.cpp, next to the knob sets)
 int launch_igemm(const IgemmArgs& a, hipStream_t s);
 double igemm_flops(const IgemmArgs& a);
 void conv_up_fold_pack_host(const f16* w, int N, int Cin, f16* out);     // w [N][9 Cin] -> out [4][N][4 Cin]: the sub-pixel filters of IgemmArgs::w_up_sub

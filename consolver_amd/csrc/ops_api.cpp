@@ -9,6 +9,7 @@ int debug_attn_trace_read(void* dst, size_t bytes);
 #include <mutex>
 TuneSet g_tune;
 thread_local const TuneSet* t_tune = nullptr;
+thread_local IgemmRoute t_igemm_route;
 static std::mutex g_tune_write_mutex;      // writers of the process-wide set (cs_set_tuning / cs_reset_tuning) and tune_snapshot; per-handle overrides never write it (ops.h, TuneSet)
 
 // every kernel-selection knob: name, field, accepted range (or the two-value set {lo, hi} when `pair`); the defaults are TuneSet's member initialisers
@@ -76,6 +77,8 @@ int cs_op_conv2d(const void* x0, int c0, const void* x1, int c1, int B, int Hi, 
     IgemmArgs a{};
     a.a0 = (const f16*)x0; a.a1 = (const f16*)x1; a.c0 = c0; a.c1 = c1; a.B = B; a.Hi = Hi; a.Wi = Wi;
     if (stride != 1 && stride != 2) CS_FAIL(CS_E_ARG, "conv2d: stride must be 1 or 2");
+    // pad 1, stride 2 gives ceil(Hi / 2) rows: the floor below is that only for even sizes (the pad-after-only form, cs_op_conv_down, floors by definition)
+    if (stride == 2 && !upsample && ((Hi | Wi) & 1)) CS_FAIL(CS_E_SHAPE, "conv2d: stride 2 needs an even input size (got %d x %d)", Hi, Wi);
     a.Ho = upsample ? 2 * Hi : (stride == 2 ? Hi / 2 : Hi);
     a.Wo = upsample ? 2 * Wi : (stride == 2 ? Wi / 2 : Wi);
     a.taps = taps; a.stride = stride; a.upsample = upsample; a.N = N; a.w = (const f16*)w; a.bias = (const f16*)bias;
@@ -90,6 +93,8 @@ int cs_op_conv2d_gn(const void* x0, int c0, const void* x1, int c1, int B, int H
     IgemmArgs a{};
     a.a0 = (const f16*)x0; a.a1 = (const f16*)x1; a.c0 = c0; a.c1 = c1; a.B = B; a.Hi = Hi; a.Wi = Wi;
     if (stride != 1 && stride != 2) CS_FAIL(CS_E_ARG, "conv2d: stride must be 1 or 2");
+    // pad 1, stride 2 gives ceil(Hi / 2) rows: the floor below is that only for even sizes (the pad-after-only form, cs_op_conv_down, floors by definition)
+    if (stride == 2 && !upsample && ((Hi | Wi) & 1)) CS_FAIL(CS_E_SHAPE, "conv2d: stride 2 needs an even input size (got %d x %d)", Hi, Wi);
     a.Ho = upsample ? 2 * Hi : (stride == 2 ? Hi / 2 : Hi);
     a.Wo = upsample ? 2 * Wi : (stride == 2 ? Wi / 2 : Wi);
     a.taps = taps; a.stride = stride; a.upsample = upsample; a.N = N; a.w = (const f16*)w; a.bias = (const f16*)bias;
@@ -142,6 +147,8 @@ int cs_op_conv2d_x2(const void* x0, const void* x0_lo, int c0, const void* x1, c
     a.a0_lo = (const f16*)x0_lo; a.a1_lo = (const f16*)x1_lo; a.row_stats = row_stats; a.row_stats_groups = row_groups;
     if (stride != 1 && stride != 2) CS_FAIL(CS_E_ARG, "conv2d: stride must be 1 or 2");
     if (res_lo && !res) CS_FAIL(CS_E_ARG, "conv2d_x2: res_lo without res");
+    // pad 1, stride 2 gives ceil(Hi / 2) rows: the floor below is that only for even sizes (the pad-after-only form, cs_op_conv_down, floors by definition)
+    if (stride == 2 && !upsample && ((Hi | Wi) & 1)) CS_FAIL(CS_E_SHAPE, "conv2d: stride 2 needs an even input size (got %d x %d)", Hi, Wi);
     a.Ho = upsample ? 2 * Hi : (stride == 2 ? Hi / 2 : Hi);
     a.Wo = upsample ? 2 * Wi : (stride == 2 ? Wi / 2 : Wi);
     a.taps = taps; a.stride = stride; a.upsample = upsample; a.N = N; a.w = (const f16*)w; a.bias = (const f16*)bias;
@@ -458,5 +465,12 @@ int cs_op_group_norm_splits(const void* x0, int c0, const void* x1, int c1, int 
 
 int cs_debug_trace_read(void* dst_host, size_t bytes) { return debug_trace_read(dst_host, bytes); }
 int cs_debug_attn_trace_read(void* dst_host, size_t bytes) { return debug_attn_trace_read(dst_host, bytes); }
+int cs_debug_igemm_last_route(int* out, int n) {
+    if (!out || n < 0) CS_FAIL(CS_E_ARG, "igemm_last_route: out is NULL");
+    const IgemmRoute& r = t_igemm_route;
+    const int v[7] = {r.family, r.tile_cols, r.variant, r.splits, r.gn_done, r.row_groups, r.fallback};
+    for (int i = 0; i < n && i < 7; ++i) out[i] = v[i];
+    return 7;
+}
 
 }  // extern "C"

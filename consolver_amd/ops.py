@@ -3,6 +3,7 @@
 Used by the kernel parity tests and available to callers that want the individual HIP ops.
 Activations are NHWC fp16 CUDA tensors.
 """
+import collections
 import ctypes as C
 
 import torch
@@ -26,15 +27,17 @@ def pack_conv_weight(w):
 _SPLITK_WS = {}
 
 
-def conv2d(x0, w_packed, bias=None, x1=None, taps=9, stride=1, upsample=False, temb=None, res=None, splitk=True, gn_stats=False):
-    """gn_stats=True: also return the GroupNorm partial sums of the output, fp32 [B, Ho*Wo/64, N/2, 2] (cs_op_conv2d_gn)."""
+def conv2d(x0, w_packed, bias=None, x1=None, taps=9, stride=1, upsample=False, temb=None, res=None, splitk=True, gn_stats=False, out=None, st=None):
+    """gn_stats=True: also return the GroupNorm partial sums of the output, fp32 [B, Ho*Wo/64, N/2, 2] (cs_op_conv2d_gn).  out / st: preallocated (pre-filled)
+    result and statistics buffers (tests: views into NaN-filled buffers)."""
     _f16(x0, "x0")
     B, Hi, Wi, c0 = x0.shape
     c1 = x1.shape[-1] if x1 is not None else 0
     N = w_packed.shape[0]
     Ho = 2 * Hi if upsample else (Hi // 2 if stride == 2 else Hi)
     Wo = 2 * Wi if upsample else (Wi // 2 if stride == 2 else Wi)
-    out = torch.empty(B, Ho, Wo, N, dtype=torch.float16, device=x0.device)
+    if out is None:
+        out = torch.empty(B, Ho, Wo, N, dtype=torch.float16, device=x0.device)
     tstride = 0 if (temb is None or temb.shape[0] == 1) else temb.shape[1]
     ws = None
     if splitk and taps == 9:
@@ -42,7 +45,8 @@ def conv2d(x0, w_packed, bias=None, x1=None, taps=9, stride=1, upsample=False, t
         if ws is None:
             ws = _SPLITK_WS[x0.device] = torch.empty(64 << 20, dtype=torch.uint8, device=x0.device)
     if gn_stats:
-        st = torch.zeros(B, Ho * Wo // 64, N // 2, 2, dtype=torch.float32, device=x0.device)
+        if st is None:
+            st = torch.zeros(B, Ho * Wo // 64, N // 2, 2, dtype=torch.float32, device=x0.device)
         L.check(L.lib().cs_op_conv2d_gn(L.ptr(x0), c0, L.ptr(x1), c1, B, Hi, Wi, taps, stride, int(upsample), L.ptr(w_packed),
                                         L.ptr(bias), N, L.ptr(temb), tstride, L.ptr(res), L.ptr(out),
                                         L.ptr(ws), ws.numel() if ws is not None else 0, L.ptr(st), L.stream_ptr(x0.device)))
@@ -65,13 +69,17 @@ def conv_up_fold_pack(w_packed):
     return out
 
 
-def conv_up_sub(x, w_packed, w_sub, bias=None, gn_stats=False):
+def conv_up_sub(x, w_packed, w_sub, bias=None, gn_stats=False, out=None, st=None):
     """nearest-x2 upsample + 3x3 conv through the sub-pixel kernel (cs_op_conv_up_sub): x [B, Hi, Wi, Cin] -> [B, 2 Hi, 2 Wi, N]"""
     _f16(x, "x")
     B, Hi, Wi, Cin = x.shape
     N = w_packed.shape[0]
-    out = torch.empty(B, 2 * Hi, 2 * Wi, N, dtype=torch.float16, device=x.device)
-    st = torch.zeros(B, 4 * Hi * Wi // 64, N // 2, 2, dtype=torch.float32, device=x.device) if gn_stats else None
+    if out is None:
+        out = torch.empty(B, 2 * Hi, 2 * Wi, N, dtype=torch.float16, device=x.device)
+    if gn_stats and st is None:
+        st = torch.zeros(B, 4 * Hi * Wi // 64, N // 2, 2, dtype=torch.float32, device=x.device)
+    if not gn_stats:
+        st = None
     L.check(L.lib().cs_op_conv_up_sub(L.ptr(x), Cin, B, Hi, Wi, L.ptr(w_packed), L.ptr(w_sub), L.ptr(bias), N, L.ptr(out), L.ptr(st), L.stream_ptr(x.device)))
     return (out, st) if gn_stats else out
 
@@ -95,7 +103,7 @@ def split_f16(x):
 
 
 def conv2d_x2(x0, w_packed, bias=None, x1=None, taps=9, stride=1, upsample=False, temb=None, res=None, res_lo=None, splitk=True, x0_lo=None, x1_lo=None,
-              row_stats=False, want_lo=True):
+              row_stats=False, want_lo=True, out=None, out_lo=None, st=None):
     """cs_op_conv2d_x2: returns (out_hi, out_lo); res / res_lo are the planes of a split-fp16 residual (res_lo may be None); x0_lo / x1_lo (1x1 only)
     the lo planes of a split-fp16 A operand."""
     _f16(x0, "x0")
@@ -104,15 +112,17 @@ def conv2d_x2(x0, w_packed, bias=None, x1=None, taps=9, stride=1, upsample=False
     N = w_packed.shape[0]
     Ho = 2 * Hi if upsample else (Hi // 2 if stride == 2 else Hi)
     Wo = 2 * Wi if upsample else (Wi // 2 if stride == 2 else Wi)
-    out = torch.empty(B, Ho, Wo, N, dtype=torch.float16, device=x0.device)
-    out_lo = torch.empty_like(out) if want_lo else None
+    if out is None:
+        out = torch.empty(B, Ho, Wo, N, dtype=torch.float16, device=x0.device)
+    if out_lo is None and want_lo:
+        out_lo = torch.empty_like(out)
     tstride = 0 if (temb is None or temb.shape[0] == 1) else temb.shape[1]
     ws = None
     if splitk:
         ws = _SPLITK_WS.get(x0.device)
         if ws is None:
             ws = _SPLITK_WS[x0.device] = torch.empty(64 << 20, dtype=torch.uint8, device=x0.device)
-    rs, G = (torch.zeros(B * Ho * Wo, N // 64, 2, dtype=torch.float32, device=x0.device), C.c_int(0)) if row_stats else (None, None)
+    rs, G = (st if st is not None else torch.zeros(B * Ho * Wo, N // 64, 2, dtype=torch.float32, device=x0.device), C.c_int(0)) if row_stats else (None, None)
     L.check(L.lib().cs_op_conv2d_x2(L.ptr(x0), L.ptr(x0_lo), c0, L.ptr(x1), L.ptr(x1_lo), c1, B, Hi, Wi, taps, stride, int(upsample), L.ptr(w_packed),
                                     L.ptr(bias), N, L.ptr(temb), tstride, L.ptr(res), L.ptr(res_lo), L.ptr(out), L.ptr(out_lo),
                                     L.ptr(rs), C.byref(G) if row_stats else None,
@@ -122,7 +132,7 @@ def conv2d_x2(x0, w_packed, bias=None, x1=None, taps=9, stride=1, upsample=False
     return out, out_lo
 
 
-def linear_x2(x, w, bias=None, res=None, res_lo=None, splitk=True, want_lo=True, x_lo=None, row_stats=False, out=None, out_lo=None):
+def linear_x2(x, w, bias=None, res=None, res_lo=None, splitk=True, want_lo=True, x_lo=None, row_stats=False, out=None, out_lo=None, st=None):
     """cs_op_linear_x2: returns (out_hi, out_lo) (out_lo None with want_lo=False: the fp16 rounding of the fp32 sum only); row_stats=True appends
     (stats [M, N/64, 2] fp32 of which the first G groups are valid, G): the row statistics a folded LayerNorm's consumer (linear_ln) reads."""
     _f16(x, "x")
@@ -136,7 +146,7 @@ def linear_x2(x, w, bias=None, res=None, res_lo=None, splitk=True, want_lo=True,
         ws = _SPLITK_WS.get(x.device)
         if ws is None:
             ws = _SPLITK_WS[x.device] = torch.empty(64 << 20, dtype=torch.uint8, device=x.device)
-    rs, G = (torch.zeros(M, N // 64, 2, dtype=torch.float32, device=x.device), C.c_int(0)) if row_stats else (None, None)
+    rs, G = (st if st is not None else torch.zeros(M, N // 64, 2, dtype=torch.float32, device=x.device), C.c_int(0)) if row_stats else (None, None)
     L.check(L.lib().cs_op_linear_x2(L.ptr(x), L.ptr(x_lo), M, K, L.ptr(w), L.ptr(bias), N, L.ptr(res), L.ptr(res_lo), L.ptr(out), L.ptr(out_lo),
                                     L.ptr(rs), C.byref(G) if row_stats else None,
                                     L.ptr(ws), ws.numel() if ws is not None else 0, L.stream_ptr(x.device)))
@@ -312,12 +322,13 @@ def attention(q, k, v, heads, scale=None, q_stride=None, k_stride=None, v_stride
     return out
 
 
-def conv_out(x, w_packed, bias, postprocess=False):
+def conv_out(x, w_packed, bias, postprocess=False, out=None):
     """3x3 conv (pad 1) NHWC x [B, H, W, Cin] -> NCHW [B, Cout, H, W] for a small Cout (cs_op_conv_out: the UNet's eps head, the VAE's image / moments heads)."""
     _f16(x, "x")
     B, H, W, Cin = x.shape
     Cout = w_packed.shape[0]
-    out = torch.empty(B, Cout, H, W, dtype=torch.float16, device=x.device)
+    if out is None:
+        out = torch.empty(B, Cout, H, W, dtype=torch.float16, device=x.device)
     L.check(L.lib().cs_op_conv_out(L.ptr(x.contiguous()), B, Cin, H, W, L.ptr(w_packed.contiguous()), L.ptr(bias.to(x.device, torch.float16).contiguous()), Cout,
                                    L.ptr(out), int(postprocess), L.stream_ptr(x.device)))
     return out
@@ -487,6 +498,21 @@ def xattn_block(h, ln_gamma, ln_beta, wq, kv, wo, bo, heads=8, eps=1e-5, hw=None
     L.check(L.lib().cs_op_xattn_block(L.ptr(h), L.ptr(ln_gamma), L.ptr(ln_beta), float(eps), L.ptr(wq), L.ptr(kv), kv.shape[1], L.ptr(wo),
                                       L.ptr(bo), M, hw, Cc, heads, float((Cc // heads) ** -0.5), L.ptr(out), L.stream_ptr(h.device)))
     return out
+
+
+IgemmRoute = collections.namedtuple("IgemmRoute", "family tile_cols variant splits gn_done row_groups fallback")
+IGEMM_FAMILIES = ("none", "generic", "halo", "conv3_lw", "sub_pixel", "gemm_big", "gemm_w8", "gemm_lw")
+
+
+def igemm_last_route():
+    """which kernel this thread's last conv / linear launch took (cs_debug_igemm_last_route): family as its name from IGEMM_FAMILIES, tile columns, the variant
+    index of the launch site's table, split-K factor, whether the kernel left the GroupNorm statistics, its row-statistics groups, the fallback passes that ran
+    (bit 0 GroupNorm statistics, bit 1 row statistics)"""
+    v = (C.c_int * 7)()
+    n = L.lib().cs_debug_igemm_last_route(v, 7)
+    if n != 7:
+        raise RuntimeError(f"cs_debug_igemm_last_route: {n}")
+    return IgemmRoute(IGEMM_FAMILIES[v[0]], *list(v)[1:])
 
 
 def set_tuning(key, value):

@@ -24,7 +24,9 @@ extern "C" {
  * over the channel concatenation of x0 [B,Hi,Wi,c0] and x1 [B,Hi,Wi,c1] (x1 may be NULL, c1 = 0).
  * out[B,Ho,Wo,N] = conv + bias[N] + temb[b*temb_stride + n] + res[B,Ho,Wo,N]  (each optional).
  * splitk_ws: optional fp32 scratch (device) that lets small-image 3x3 convs split their channel chunks over
- * more workgroups (needs splits * M * N * 4 bytes; NULL disables). */
+ * more workgroups (needs splits * M * N * 4 bytes; NULL disables).
+ * stride 2 (pad 1) needs an even Hi and Wi: Ho = Hi / 2 is the conv's size only then (odd sizes are CS_E_SHAPE, here and in cs_op_conv2d_gn / cs_op_conv2d_x2;
+ * the pad-after-only form, cs_op_conv_down, floors by definition). */
 int cs_op_conv2d(const void* x0, int c0, const void* x1, int c1, int B, int Hi, int Wi, int taps, int stride, int upsample,
                  const void* w, const void* bias, int N, const void* temb, int temb_stride, const void* res, void* out,
                  void* splitk_ws, size_t splitk_ws_bytes, void* stream);
@@ -50,7 +52,8 @@ int cs_op_conv_up_sub(const void* x, int Cin, int B, int Hi, int Wi, const void*
                       void* stream);
 
 /* out[M,N] = x[M,K] w[N,K]^T + bias + res ; geglu != 0: w rows pre-permuted in (16 value | 16 gate)
- * blocks (see cs_op_geglu_pack) and out[M,N/2] = value * gelu(gate). */
+ * blocks (see cs_op_geglu_pack) and out[M,N/2] = value * gelu(gate); GEGLU needs N % 256 == 0 or N % 320 == 0, and with
+ * N % 128 != 0 it always runs on the 320-column kernels (CS_E_SHAPE when the knob gemm_big is 0). */
 int cs_op_linear(const void* x, int M, int K, const void* w, const void* bias, int N, const void* res, void* out, int geglu, void* stream);
 
 /* host helper: permute a [2*Hd, K] GEGLU projection (rows [0,Hd) value, [Hd,2Hd) gate; fp16) and its
@@ -287,6 +290,19 @@ int cs_debug_trace_read(void* dst_host, size_t bytes);
 /* the same for attn40_lw_kernel (head dim 40 self-attention): [slot][6] uint64: shader cycles of compute wave 0 over the steady loop, 100 MHz ticks
  * over the same, tiles in it, loader wave 4's cycles in its DMA waits, at the tile barriers, unused (at most 4096 slots; tools/attn_lw_trace.py). */
 int cs_debug_attn_trace_read(void* dst_host, size_t bytes);
+/* Which kernel the CALLING THREAD's last conv / linear launch (cs_op_conv2d* / cs_op_conv_up_sub / cs_op_conv_down / cs_op_linear*) took: writes up to n ints to
+ * out (host) and returns how many the record has (7):
+ *   [0] family: 0 nothing launched (refused or empty), 1 igemm_kernel (generic), 2 conv3_halo_kernel, 3 conv3_lw_kernel, 4 conv3_lw_kernel in the sub-pixel form,
+ *       5 gemm_big_kernel, 6 gemm_w8_kernel, 7 gemm_lw_kernel;
+ *   [1] tile columns: 128, 160, 256 or 320;
+ *   [2] variant: the index into that launch site's function-pointer table (csrc/igemm.hip: variants / sub / w8 / lwk); igemm_kernel: LNM | EPI << 2 | GEGLU << 4 |
+ *       CONV3 << 5 of the instantiation; conv3_halo_kernel: 1 with the fused upsample; gemm_big_kernel: 1 with GEGLU;
+ *   [3] splits: the split-K factor (1 = none; > 1: a reduce kernel ran behind the main one);
+ *   [4] gn_done: 1 when the kernel (or the split-K reduce) left the GroupNorm statistics itself;
+ *   [5] row_groups: column groups of the row statistics the epilogue left (0: it left none);
+ *   [6] fallback passes that ran behind the launch: bit 0 the GroupNorm statistics pass, bit 1 the row statistics pass.
+ * Host bookkeeping only (one store per launch); the tests use it to assert the dispatch. */
+int cs_debug_igemm_last_route(int* out, int n);
 
 /* the two ends of the CLIP vision tower (csrc/vit_ops.hip), all device pointers fp16 unless noted:
  * x [B * (NP + 1)][D] = LayerNorm((t == 0 ? cls : pe[b * NP + t - 1]) + pos[t]) -- sum and normalisation in fp32, one rounding; D % 128 == 0, D <= 2048 */
