@@ -9,6 +9,7 @@ hand-written HIP kernels behind ``include/consolver_hip.h``; there is no CPU fal
 from .scheduling_ppo import PPOScheduler, SolverOutput  # noqa: F401
 from ._scheduler_base import HAVE_DIFFUSERS, SolverConfig  # noqa: F401
 from .scheduling_fmppo import FMPPOScheduler  # noqa: F401
+from .scheduling_fm import FlowMatchGeneralDiscreteScheduler  # noqa: F401
 from .factor_net import FactorNetPPO, FluxFactorNetPPO  # noqa: F401
 from .scheduling_dpm import DPMSolverMultistepScheduler, SD15_MULTISTEP_DPM_KWARGS  # noqa: F401
 from .fid import FIDStatistics, HipFIDInception, compute_fid, frechet_distance, load_fid_inception  # noqa: F401

@@ -39,6 +39,11 @@ class CsDpmStepArgs(C.Structure):
                 ("conv_x", C.c_float), ("conv_e", C.c_float), ("cx", C.c_float), ("c0", C.c_float), ("c1", C.c_float)]
 
 
+class CsFmStepArgs(C.Structure):
+    _fields_ = [("x_base", C.c_void_p), ("v2", C.c_void_p), ("v1", C.c_void_p), ("c", C.c_float), ("B", C.c_int), ("elems", C.c_int64),
+                ("io_dtype", C.c_int), ("out_dtype", C.c_int), ("x_is_f32", C.c_int), ("x_out", C.c_void_p)]
+
+
 class CsFluxConfig(C.Structure):
     _fields_ = [("in_channels", C.c_int), ("num_layers", C.c_int), ("num_single_layers", C.c_int), ("num_heads", C.c_int),
                 ("head_dim", C.c_int), ("joint_attention_dim", C.c_int), ("pooled_projection_dim", C.c_int),
@@ -126,6 +131,7 @@ SYMBOLS = {
     "cs_lms_ddim_step": (C.c_int, [C.POINTER(CsStepArgs), C.c_void_p]),
     "cs_lms_euler_step": (C.c_int, [C.POINTER(CsStepArgs), C.c_void_p]),
     "cs_dpm_multistep_step": (C.c_int, [C.POINTER(CsDpmStepArgs), C.c_void_p]),
+    "cs_fm_general_step": (C.c_int, [C.POINTER(CsFmStepArgs), C.c_void_p]),
     "cs_psnr_workspace_bytes": (C.c_size_t, [C.c_int]),
     "cs_image_psnr": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_size_t,
                                 C.c_void_p]),

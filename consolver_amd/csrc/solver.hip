@@ -5,6 +5,7 @@
 //   cs_lms_euler_step : same with the flow-matching Euler epilogue
 //                       (edit_ppo/scheduler_fmppo.py:400-436)
 //   cs_dpm_multistep_step : CFG combine + model-output conversion + Multistep DPM-Solver update (orders 1, 2)
+//   cs_fm_general_step : the flow-matching baselines' update (Euler / Heun / dpm-solver / multistep, edit_ppo/scheduler_fm.py:405-482)
 //   cs_factor_probs   : FactorNetPPO.forward_ (factor_net_ppo.py:137-157)
 //   cs_cosine_features: compute_cosine_similarity (factor_net_ppo.py:108-130)
 //   cs_sample_actions / cs_gather_actions / cs_action_probs / cs_step_masks / cs_stack_history
@@ -371,6 +372,96 @@ int launch_dpm_step(const CsDpmStepArgs* a, void* stream) {
     return CS_OK;
 }
 
+// ---------------------------------------------------------------- flow-matching baselines (edit_ppo/scheduler_fm.py:405-482)
+// Every branch of the Euler / Heun / dpm-solver / multistep step is x' = cast_out(x_base + c * w) with w = v2 or v1 + v2; which base, whether
+// v1 is read and the scalar c are decided on the host (scheduling_fm.py).  c is a 0-d fp32 tensor in the reference, so with a 16-bit model
+// output `v1 + v2` and `c * w` are 16-bit ops (c cast to the model dtype, each result rounded to it) before the fp32 add -- the m == 1 form
+// of solve_one.
+struct FmParams {
+    const void* x; const void* v2; const void* v1; float c;
+    int64_t total;   // B * elems: no per-sample coefficient, so the batch is one flat range and the vector body stays 16-byte aligned whatever elems is
+    void* x_out;
+    int x_f32;   // as StepParams::x_f32
+};
+
+template <typename TI>
+__device__ __forceinline__ float fm_one(const FmParams& p, float x, float v2, float v1) {
+    const float w = p.v1 ? Io<TI>::round(v1 + v2) : v2;
+    return x + Io<TI>::round(Io<TI>::round(p.c) * w);
+}
+
+template <typename TI, typename TO>
+__global__ __launch_bounds__(256) void fm_step_kernel(FmParams p) {
+    constexpr int V = Io<TI>::VEC;
+    const int64_t nvec = p.total / V;
+    for (int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; v < nvec; v += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t i = v * V;
+        float x[V], e[V], h[V], o[V];
+        if (p.x_f32) {   // block-uniform
+#pragma unroll
+            for (int j = 0; j < V; ++j) x[j] = reinterpret_cast<const float*>(p.x)[i + j];
+        } else {
+            Io<TI>::load(p.x, i, x);
+        }
+        Io<TI>::load(p.v2, i, e);
+        if (p.v1) {
+            Io<TI>::load(p.v1, i, h);
+        } else {
+#pragma unroll
+            for (int j = 0; j < V; ++j) h[j] = 0.f;
+        }
+#pragma unroll
+        for (int j = 0; j < V; ++j) o[j] = fm_one<TI>(p, x[j], e[j], h[j]);
+        if constexpr (Io<TO>::VEC == V) {
+            Io<TO>::store(p.x_out, i, o);
+        } else {
+#pragma unroll
+            for (int j = 0; j < V; ++j) Io<TO>::store1(p.x_out, i + j, o[j]);
+        }
+    }
+    // scalar tail (total % V != 0): handled by the first block
+    if (blockIdx.x == 0) {
+        for (int64_t i = nvec * V + threadIdx.x; i < p.total; i += blockDim.x) {
+            const float x = p.x_f32 ? reinterpret_cast<const float*>(p.x)[i] : Io<TI>::load1(p.x, i);
+            const float h = p.v1 ? Io<TI>::load1(p.v1, i) : 0.f;
+            Io<TO>::store1(p.x_out, i, fm_one<TI>(p, x, Io<TI>::load1(p.v2, i), h));
+        }
+    }
+}
+
+int launch_fm_step(const CsFmStepArgs* a, void* stream) {
+    if (!a) CS_FAIL(CS_E_ARG, "args is NULL");
+    if (a->B < 0 || a->elems < 0) CS_FAIL(CS_E_SHAPE, "negative shape");
+    const bool empty = (a->B == 0 || a->elems == 0);
+    if (!empty && (!a->x_base || !a->v2 || !a->x_out)) CS_FAIL(CS_E_ARG, "x_base, v2 and x_out are required");
+    const int io = a->io_dtype, od = a->out_dtype;
+    const bool pair_ok = (io == CS_F32 && od == CS_F32) || (io == CS_F16 && (od == CS_F16 || od == CS_F32)) || (io == CS_BF16 && (od == CS_BF16 || od == CS_F32));
+    if (!pair_ok) CS_FAIL(CS_E_DTYPE, "unsupported io/out dtype pair (%d,%d)", io, od);
+    if (empty) return CS_OK;
+    FmParams p;
+    p.x = a->x_base; p.v2 = a->v2; p.v1 = a->v1; p.c = a->c; p.total = (int64_t)a->B * a->elems; p.x_out = a->x_out;
+    p.x_f32 = (a->x_is_f32 != 0 && io != CS_F32);
+    // one 16-byte load / store per lane and tensor (4 bytes per element of an fp32 base next to 16-bit outputs)
+    if ((((uintptr_t)a->v2 | (uintptr_t)a->v1) & 15) || ((uintptr_t)a->x_base & (p.x_f32 ? 3 : 15)) || ((uintptr_t)a->x_out & (io != CS_F32 && od == CS_F32 ? 3 : 15)))
+        CS_FAIL(CS_E_ARG, "x_base, v1, v2 and x_out must be 16-byte aligned");
+    const int vec = (io == CS_F32) ? 4 : 8;
+    int64_t nvec = p.total / vec;
+    // the same capped grid as launch_step: ~8 blocks per CU overall, grid-stride the rest
+    int64_t gx = (nvec + 255) / 256;
+    if (gx > 2048) gx = 2048; if (gx < 1) gx = 1;
+    dim3 grid((unsigned)gx), block(256);
+    hipStream_t s = (hipStream_t)stream;
+#define LAUNCH(TI, TO) hipLaunchKernelGGL((fm_step_kernel<TI, TO>), grid, block, 0, s, p)
+    if (io == CS_F32) LAUNCH(float, float);
+    else if (io == CS_F16 && od == CS_F16) LAUNCH(f16, f16);
+    else if (io == CS_F16) LAUNCH(f16, float);
+    else if (od == CS_BF16) LAUNCH(bf16_tag, bf16_tag);
+    else LAUNCH(bf16_tag, float);
+#undef LAUNCH
+    CS_CHECK_LAUNCH();
+    return CS_OK;
+}
+
 // ---------------------------------------------------------------- policy MLP
 // one workgroup per DISTINCT conditioning row; weights (<= ~1 MB) stay in L2.  When one row is
 // broadcast to all B samples (x_row_stride == 0, no cosine features: every sampling step), a single
@@ -592,6 +683,7 @@ extern "C" {
 int cs_lms_ddim_step(const CsStepArgs* args, void* stream) { return launch_step<false>(args, stream); }
 int cs_lms_euler_step(const CsStepArgs* args, void* stream) { return launch_step<true>(args, stream); }
 int cs_dpm_multistep_step(const CsDpmStepArgs* args, void* stream) { return launch_dpm_step(args, stream); }
+int cs_fm_general_step(const CsFmStepArgs* args, void* stream) { return launch_fm_step(args, stream); }
 
 int cs_factor_probs(const CsFactorNet* n, const float* x, int x_row_stride, const float* cos_feat, int B, float* probs, void* stream) {
     if (!n) CS_FAIL(CS_E_ARG, "net is NULL");

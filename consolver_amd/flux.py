@@ -232,7 +232,8 @@ class HipFluxTransformer2DModel:
 
 class FluxKontextSamplingEngine:
     """The FLUX edit loop (edit_ppo/pipeline.py:1009-1140 minus encoders / VAE): sigma schedule with the
-    resolution-dependent shift, [latents | image_latents] joint input, FMPPOScheduler update."""
+    resolution-dependent shift, [latents | image_latents] joint input, and the scheduler's update: ``FMPPOScheduler`` or any scheduler of
+    the same protocol whose ``step(..., return_dict=False)`` returns at least ``(prev_sample,)`` (scheduling_fm.py, baselines.py)."""
 
     def __init__(self, transformer, scheduler, guidance_scale=2.5):
         self.transformer, self.scheduler, self.guidance_scale = transformer, scheduler, float(guidance_scale)
@@ -260,19 +261,30 @@ class FluxKontextSamplingEngine:
         sig = (sch.timesteps.to(latents.dtype) / 1000).to(torch.float32)
         x = latents
         rec = dict(x=[], epsilon=[], probs=[], actions=[], masks=[])
-        prev_record = sch.record_conds
-        sch.record_conds = bool(record)
+        # a policy-free scheduler (scheduling_fm.py, baselines.py) steps to (prev_sample,) and has nothing to record
+        has_policy = getattr(sch, "factor_net", None) is not None
+        if record and not has_policy:
+            raise ValueError(f"record=True needs a scheduler with a policy; {type(sch).__name__} has none")
+        keeps_conds = hasattr(sch, "record_conds")
+        if keeps_conds:
+            prev_record = sch.record_conds
+            sch.record_conds = bool(record)
         try:
             for i, t in enumerate(sch.timesteps):
                 # [latents | image_latents] is read in place by the embedder; v holds the latent rows only
                 v = self.transformer(x, sig[i:i + 1].expand(B), guidance=guidance, pooled_projections=pooled_prompt_embeds,
                                      encoder_hidden_states=prompt_embeds, txt_ids=txt_ids, img_ids=ids, image_latents=image_latents)[0]
-                x, actions, probs, conds, masks = sch.step(v, t, x, return_dict=False)
+                stepped = sch.step(v, t, x, return_dict=False)
+                x = stepped[0]
                 if record and i > 0:
+                    if len(stepped) != 5:
+                        raise ValueError(f"record=True: {type(sch).__name__}.step returned {len(stepped)} entries, not the five of a learned solver")
+                    _, actions, probs, conds, masks = stepped
                     rec["x"].append(conds["x"].unsqueeze(1)); rec["epsilon"].append(conds["epsilon"].unsqueeze(1))
                     rec["probs"].append(probs.unsqueeze(1)); rec["actions"].append(actions.unsqueeze(1)); rec["masks"].append(masks.unsqueeze(1))
         finally:
-            sch.record_conds = prev_record
+            if keeps_conds:
+                sch.record_conds = prev_record
         if not record:
             return x
         cat = {k: torch.cat(v, dim=1) for k, v in rec.items()}

@@ -123,5 +123,120 @@ def shard_for_rank(data, world, rank):
     return chunks[rank] if rank < len(chunks) else []
 
 
+FLUX_SOLVERS = ("consistencysolver", "euler", "heun", "dpm-solver", "dpm-solver-multistep")
+# generate_ours.py:122-134: the learned solver's policy as the reference driver builds it
+FLUX_POLICY_KWARGS = dict(order_dim=2, scaler_dim=0, mu_dim=0, factor_net_kwargs=dict(embedding_dim=1024, hidden_dim=256, num_actions=11))
+
+
+def make_scheduler(solver, **policy_kwargs):
+    """the scheduler of generate_ours.py:127-134 (``"consistencysolver"``; ``policy_kwargs`` override ``FLUX_POLICY_KWARGS``) or of
+    generate_pretrain.py:118-122 (``type = solver``), on FLUX.1-Kontext's published scheduler config.  The baselines have no policy."""
+    import consolver_amd
+    from .scheduling_fmppo import KONTEXT_SCHEDULER_CONFIG
+    if solver == "consistencysolver":
+        return consolver_amd.FMPPOScheduler.from_config(dict(KONTEXT_SCHEDULER_CONFIG), **{**FLUX_POLICY_KWARGS, **policy_kwargs})
+    if solver not in FLUX_SOLVERS:
+        raise ValueError(f"unknown solver {solver!r}; expected one of {FLUX_SOLVERS}")
+    if policy_kwargs:
+        raise ValueError(f"solver {solver!r} has no policy: unexpected {sorted(policy_kwargs)}")
+    return consolver_amd.FlowMatchGeneralDiscreteScheduler.from_config(dict(KONTEXT_SCHEDULER_CONFIG), type=solver)
+
+
+def synthetic_inputs(n, work_dir, joint_attention_dim, pooled_projection_dim, image_size, seq_len=64, seed=1001, key="synthetic_{}"):
+    """n seeded stand-ins for a dataset (no checkpoints or datasets exist offline): reference images, JSONL-style entries (keys
+    ``key.format(i)``) and their instruction cache under ``work_dir``.  Returns (entries, image_dir, cache_path)."""
+    from PIL import Image
+    image_dir, cache_path = os.path.join(work_dir, "images"), os.path.join(work_dir, "instructions.safetensors")
+    os.makedirs(image_dir, exist_ok=True)
+    rng, g = np.random.default_rng(seed), torch.Generator().manual_seed(seed)
+    entries, embeds = [], {}
+    for i in range(n):
+        Image.fromarray(rng.integers(0, 255, (image_size, image_size, 3), dtype=np.uint8)).save(os.path.join(image_dir, f"{i}.jpg"))
+        entries.append(dict(key=key.format(i), category="synthetic", file_name=f"{i}.jpg", instruction=f"synthetic instruction {i}"))
+        embeds[entries[-1]["key"]] = (torch.randn(seq_len, joint_attention_dim, generator=g), torch.randn(pooled_projection_dim, generator=g))
+    save_instruction_cache(cache_path, embeds)
+    return entries, image_dir, cache_path
+
+
+def _load_sd(path):
+    from safetensors.torch import load_file
+    return load_file(path) if path.endswith(".safetensors") else torch.load(path, map_location="cpu")
+
+
+def load_models(args, ap, dev, transformer=None, vae=None):
+    """the DiT and the FLUX VAE (with its encoder) of a driver run: the handles passed in, else built from ``--transformer`` / ``--vae`` state
+    dicts, else (``--synthetic``) full-size networks with seeded random weights."""
+    from .flux import HipFluxTransformer2DModel
+    from .synth import synthetic_flux_state_dict, synthetic_vae_state_dict
+    from .vae import FLUX_VAE_CONFIG, HipAutoencoderKL
+    if transformer is not None and vae is not None:
+        return transformer, vae
+    if not args.synthetic and not (args.transformer and args.vae):
+        ap.error("pass --transformer and --vae, or --synthetic N")
+    transformer = HipFluxTransformer2DModel(device=dev)
+    vae = HipAutoencoderKL(dict(FLUX_VAE_CONFIG, with_encoder=True), device=dev)
+    # (the 11.9 B synthetic parameters are drawn on the device in the model dtype: 24 GB there instead of 48 GB of host fp32)
+    transformer.load_state_dict(_load_sd(args.transformer) if args.transformer else
+                                synthetic_flux_state_dict(transformer.manifest(), device=dev, dtype=transformer.dtype))
+    vae.load_state_dict(_load_sd(args.vae) if args.vae else synthetic_vae_state_dict(vae.manifest()))
+    return transformer, vae
+
+
+def main(argv=None, *, transformer=None, vae=None):
+    """``python -m consolver_amd.generate_flux``: generate_ours.py / generate_pretrain.py as one command, one process per GPU
+    (``launch``).  ``transformer`` / ``vae``: already loaded HIP handles to run on instead of building them from the arguments."""
+    import argparse
+    import tempfile
+    import time
+    from .flux import FluxKontextSamplingEngine
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--out", required=True)
+    ap.add_argument("--jsonl"), ap.add_argument("--image-dir"), ap.add_argument("--instruction-cache")
+    ap.add_argument("--transformer"), ap.add_argument("--vae"), ap.add_argument("--policy")
+    ap.add_argument("--synthetic", type=int, default=0, help="N synthetic entries (seeded images and embeddings; seeded random weights unless given)")
+    ap.add_argument("--steps", type=int, default=8)
+    ap.add_argument("--guidance", type=float, default=2.5)
+    ap.add_argument("--solver", default="consistencysolver", choices=FLUX_SOLVERS,
+                    help="the learned solver (default) or a comparison method of generate_pretrain.py (scheduler type); those have no policy")
+    args = ap.parse_args(argv)
+    if args.solver != "consistencysolver" and args.policy:
+        ap.error(f"--policy belongs to the learned solver; --solver {args.solver} has no policy")
+    if not args.synthetic and not (args.jsonl and args.image_dir and args.instruction_cache):
+        ap.error("pass --jsonl, --image-dir and --instruction-cache, or --synthetic N")
+    rank, world, local, dist = launch.init_distributed()
+    torch.cuda.set_device(local)
+    dev = torch.device("cuda", local)
+    transformer, vae = load_models(args, ap, dev, transformer, vae)
+    sch = make_scheduler(args.solver)
+    if getattr(sch, "factor_net", None) is not None:
+        if args.policy:
+            sch.factor_net.load_state_dict(torch.load(args.policy, map_location="cpu"))
+        sch.factor_net.to(dev)
+    eng = FluxKontextSamplingEngine(transformer, sch, guidance_scale=args.guidance)
+    with tempfile.TemporaryDirectory() as work:
+        if args.synthetic:
+            data, image_dir, cache = synthetic_inputs(args.synthetic, work, transformer.config["joint_attention_dim"],
+                                                      transformer.config["pooled_projection_dim"], 8 * vae.config.sample_size)
+        else:
+            data, image_dir, cache = load_jsonl(args.jsonl), args.image_dir, args.instruction_cache
+        if dist is not None:
+            dist.barrier()
+        t0 = time.perf_counter()
+        n = worker(shard_for_rank(data, world, rank), eng, vae, cache, image_dir, args.out, dev, num_inference_steps=args.steps)
+        torch.cuda.synchronize()
+    secs = launch.reduce_max_seconds(dist, time.perf_counter() - t0, device=dev)
+    report = launch.gather_report(dist, n, 0.0, device=dev)
+    if rank == 0:
+        total = sum(c for c, _ in report)
+        print(f"{total} edits in {secs:.2f} s = {total / secs:.2f} edits/s on {world} GPU(s); per rank: {[c for c, _ in report]}")
+    if dist is not None:
+        dist.destroy_process_group()
+    return {"edits": n, "seconds": secs, "solver": args.solver, "steps": args.steps}
+
+
 __all__ = ["sanitize_folder_name", "ensure_unique_path", "load_jsonl", "chunk_entries", "shard_for_rank", "save_instruction_cache",
-           "process_instruction", "worker", "launch"]
+           "process_instruction", "worker", "launch", "FLUX_SOLVERS", "make_scheduler", "main"]
+
+
+if __name__ == "__main__":
+    main()

@@ -28,48 +28,10 @@ KONTEXT_SCHEDULER_CONFIG = dict(shift=3.0, use_dynamic_shifting=True, base_shift
                                 base_image_seq_len=256, max_image_seq_len=4096)
 
 
-class FMPPOScheduler(HistoryMixin, SchedulerMixin, ConfigMixin):
-    """``class FMPPOScheduler(SchedulerMixin, ConfigMixin)`` of edit_ppo/scheduler_fmppo.py:56 (mixins: see
-    ``_scheduler_base``)."""
-    _compatibles = []
-    order = 1
-
-    @register_to_config
-    def __init__(self, num_train_timesteps=1000, shift=1.0, use_dynamic_shifting=False, base_shift=0.5,
-                 max_shift=1.15, base_image_seq_len=256, max_image_seq_len=4096, invert_sigmas=False,
-                 shift_terminal=None, use_karras_sigmas=False, use_exponential_sigmas=False,
-                 use_beta_sigmas=False, time_shift_type="exponential", stochastic_sampling=False,
-                 order_dim=4, scaler_dim=2, mu_dim=1, use_conv=False, ppo_type="discrete",
-                 factor_net_kwargs=None):
-        if sum([use_beta_sigmas, use_exponential_sigmas, use_karras_sigmas]) > 1:
-            raise ValueError("Only one of `use_beta_sigmas`, `use_exponential_sigmas`, `use_karras_sigmas` can be used.")
-        if time_shift_type not in {"exponential", "linear"}:
-            raise ValueError("`time_shift_type` must either be 'exponential' or 'linear'.")
-        if not (1 < order_dim <= L.CS_MAX_ORDER):
-            raise ValueError(f"order_dim must be in [2, {L.CS_MAX_ORDER}]")
-        T = num_train_timesteps
-        ts = np.linspace(1, T, T, dtype=np.float32)[::-1].copy()
-        sig = (ts / np.float32(T)).astype(np.float32)
-        if not use_dynamic_shifting:
-            sig = (np.float32(shift) * sig / (np.float32(1) + np.float32(shift - 1) * sig)).astype(np.float32)
-        self._sigmas = sig
-        self.sigmas = torch.from_numpy(sig)
-        self.timesteps = self.sigmas * T
-        self.sigma_min, self.sigma_max = float(sig[-1]), float(sig[0])
-        self._shift = shift
-        self._step_index = None
-        self._begin_index = None
-        self.num_inference_steps = None
-        self.ets = []
-        kw = dict(factor_net_kwargs) if factor_net_kwargs is not None else {}
-        kw["order_dim"], kw["scaler_dim"], kw["mu_dim"], kw["use_conv"] = order_dim, scaler_dim, mu_dim, use_conv
-        kw.setdefault("embedding_dim", 32)
-        kw.setdefault("hidden_dim", 256)
-        if ppo_type != "discrete":
-            raise AssertionError("only ppo_type='discrete' exists (scheduler_fmppo.py:169-170)")
-        kw.setdefault("num_actions", 161)
-        self.factor_net = FluxFactorNetPPO(**kw)
-        self._cond_dev = None
+class FlowMatchScheduleMixin:
+    """What the FLUX-side schedulers share (``FMPPOScheduler`` here, ``FlowMatchGeneralDiscreteScheduler`` in scheduling_fm.py): loading the
+    published Kontext scheduler config, the step / begin index protocol on the host sigma table (``_sigmas`` / ``_timesteps``) and the forward
+    process."""
 
     @classmethod
     def from_pretrained(cls, pretrained_model_name_or_path=None, subfolder=None, return_unused_kwargs=False, **kw):
@@ -102,6 +64,38 @@ class FMPPOScheduler(HistoryMixin, SchedulerMixin, ConfigMixin):
                 warnings.warn(f"{src!r} could not be resolved ({type(e).__name__}); using the published FLUX.1-Kontext scheduler config")
         return cls.from_config(dict(KONTEXT_SCHEDULER_CONFIG), return_unused_kwargs=return_unused_kwargs, **kw)
 
+    def _init_schedule(self):
+        """the training-time table of the constructor (scheduler_fmppo.py:141-160, scheduler_fm.py:108-134), from the registered config."""
+        c = self.config
+        if sum([c.use_beta_sigmas, c.use_exponential_sigmas, c.use_karras_sigmas]) > 1:
+            raise ValueError("Only one of `use_beta_sigmas`, `use_exponential_sigmas`, `use_karras_sigmas` can be used.")
+        if c.time_shift_type not in {"exponential", "linear"}:
+            raise ValueError("`time_shift_type` must either be 'exponential' or 'linear'.")
+        T, shift = c.num_train_timesteps, c.shift
+        ts = np.linspace(1, T, T, dtype=np.float32)[::-1].copy()
+        sig = (ts / np.float32(T)).astype(np.float32)
+        if not c.use_dynamic_shifting:
+            sig = (np.float32(shift) * sig / (np.float32(1) + np.float32(shift - 1) * sig)).astype(np.float32)
+        self._sigmas = sig
+        self.sigmas = torch.from_numpy(sig)
+        self.timesteps = self.sigmas * T
+        self.sigma_min, self.sigma_max = float(sig[-1]), float(sig[0])
+        self._shift = shift
+        self._step_index = None
+        self._begin_index = None
+        self.num_inference_steps = None
+
+    def _set_schedule(self, num_inference_steps, device, sigmas, mu, timesteps):
+        """``set_timesteps`` without the solver's own state: the run's sigma / timestep tables (host copies ``_sigmas`` / ``_timesteps``)."""
+        sig, ts = tables.flux_sigma_schedule(self.config, self._shift, self.sigma_min, self.sigma_max,
+                                             num_inference_steps, sigmas, mu, timesteps)
+        self.num_inference_steps = len(ts)
+        self._sigmas, self._timesteps = sig, ts
+        self.sigmas = torch.from_numpy(sig).to(device)
+        self.timesteps = torch.from_numpy(ts).to(device)
+        self._step_index = None
+        self._begin_index = None
+
     # ------------------------------------------------------------------ properties
     @property
     def step_index(self):
@@ -127,19 +121,6 @@ class FMPPOScheduler(HistoryMixin, SchedulerMixin, ConfigMixin):
     def __len__(self):
         return self.config.num_train_timesteps
 
-    # ------------------------------------------------------------------ protocol
-    def set_timesteps(self, num_inference_steps=None, device=None, sigmas=None, mu=None, timesteps=None):
-        sig, ts = tables.flux_sigma_schedule(self.config, self._shift, self.sigma_min, self.sigma_max,
-                                             num_inference_steps, sigmas, mu, timesteps)
-        self.num_inference_steps = len(ts)
-        self._sigmas, self._timesteps = sig, ts
-        self.sigmas = torch.from_numpy(sig).to(device)
-        self.timesteps = torch.from_numpy(ts).to(device)
-        self._step_index = None
-        self._begin_index = None
-        self.ets = []
-        self._cond_dev = None
-
     def index_for_timestep(self, timestep, schedule_timesteps=None):
         ts = self._timesteps if schedule_timesteps is None else np.asarray(schedule_timesteps.cpu())
         idx = np.nonzero(ts == np.float32(float(timestep)))[0]
@@ -156,6 +137,56 @@ class FMPPOScheduler(HistoryMixin, SchedulerMixin, ConfigMixin):
             self._step_index = self.index_for_timestep(timestep)
         else:
             self._step_index = self._begin_index
+
+    def scale_noise(self, sample, timestep, noise=None):
+        """scheduler_fmppo.py:457-484 (forward process; not on the sampling path)."""
+        sigmas = self.sigmas.to(device=sample.device, dtype=sample.dtype)
+        ts = self.timesteps.to(sample.device)
+        timestep = timestep.to(sample.device)
+        if self._begin_index is None:
+            idx = [self.index_for_timestep(t, ts) for t in timestep]
+        elif self._step_index is not None:
+            idx = [self._step_index] * timestep.shape[0]
+        else:
+            idx = [self._begin_index] * timestep.shape[0]
+        sigma = sigmas[idx].flatten()
+        while len(sigma.shape) < len(sample.shape):
+            sigma = sigma.unsqueeze(-1)
+        return sigma * noise + (1.0 - sigma) * sample
+
+
+class FMPPOScheduler(HistoryMixin, FlowMatchScheduleMixin, SchedulerMixin, ConfigMixin):
+    """``class FMPPOScheduler(SchedulerMixin, ConfigMixin)`` of edit_ppo/scheduler_fmppo.py:56 (mixins: see
+    ``_scheduler_base``)."""
+    _compatibles = []
+    order = 1
+
+    @register_to_config
+    def __init__(self, num_train_timesteps=1000, shift=1.0, use_dynamic_shifting=False, base_shift=0.5,
+                 max_shift=1.15, base_image_seq_len=256, max_image_seq_len=4096, invert_sigmas=False,
+                 shift_terminal=None, use_karras_sigmas=False, use_exponential_sigmas=False,
+                 use_beta_sigmas=False, time_shift_type="exponential", stochastic_sampling=False,
+                 order_dim=4, scaler_dim=2, mu_dim=1, use_conv=False, ppo_type="discrete",
+                 factor_net_kwargs=None):
+        if not (1 < order_dim <= L.CS_MAX_ORDER):
+            raise ValueError(f"order_dim must be in [2, {L.CS_MAX_ORDER}]")
+        self._init_schedule()
+        self.ets = []
+        kw = dict(factor_net_kwargs) if factor_net_kwargs is not None else {}
+        kw["order_dim"], kw["scaler_dim"], kw["mu_dim"], kw["use_conv"] = order_dim, scaler_dim, mu_dim, use_conv
+        kw.setdefault("embedding_dim", 32)
+        kw.setdefault("hidden_dim", 256)
+        if ppo_type != "discrete":
+            raise AssertionError("only ppo_type='discrete' exists (scheduler_fmppo.py:169-170)")
+        kw.setdefault("num_actions", 161)
+        self.factor_net = FluxFactorNetPPO(**kw)
+        self._cond_dev = None
+
+    # ------------------------------------------------------------------ protocol
+    def set_timesteps(self, num_inference_steps=None, device=None, sigmas=None, mu=None, timesteps=None):
+        self._set_schedule(num_inference_steps, device, sigmas, mu, timesteps)
+        self.ets = []
+        self._cond_dev = None
 
     def step(self, model_output, timestep, sample, s_churn=0.0, s_tmin=0.0, s_tmax=float("inf"), s_noise=1.0,
              generator=None, per_token_timesteps=None, return_dict=True, *, out=None):
@@ -216,19 +247,3 @@ class FMPPOScheduler(HistoryMixin, SchedulerMixin, ConfigMixin):
         if not return_dict:
             return (prev, actions, aprobs, conds, masks)
         return SolverOutput(prev_sample=prev, actions=actions, probs=aprobs, conds=conds, masks=masks)
-
-    def scale_noise(self, sample, timestep, noise=None):
-        """scheduler_fmppo.py:457-484 (forward process; not on the sampling path)."""
-        sigmas = self.sigmas.to(device=sample.device, dtype=sample.dtype)
-        ts = self.timesteps.to(sample.device)
-        timestep = timestep.to(sample.device)
-        if self._begin_index is None:
-            idx = [self.index_for_timestep(t, ts) for t in timestep]
-        elif self._step_index is not None:
-            idx = [self._step_index] * timestep.shape[0]
-        else:
-            idx = [self._begin_index] * timestep.shape[0]
-        sigma = sigmas[idx].flatten()
-        while len(sigma.shape) < len(sample.shape):
-            sigma = sigma.unsqueeze(-1)
-        return sigma * noise + (1.0 - sigma) * sample

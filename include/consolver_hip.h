@@ -179,6 +179,29 @@ typedef struct CsDpmStepArgs {
 int cs_dpm_multistep_step(const CsDpmStepArgs* args, void* stream);
 
 /* ------------------------------------------------------------------------
+ * Flow-matching baseline update (consolver_amd/scheduling_fm.py; edit_ppo/scheduler_fm.py:405-482).
+ * Every branch of the Euler, Heun, dpm-solver and multistep steps is
+ *     w  = v1 ? round_io(v1 + v2) : v2
+ *     x' = cast_out(x_base + round_io(round_io(c) * w))
+ * (round_io is the identity for fp32 io).  Which sample is the base, whether v1 is read and the
+ * scalar c are the host's step plan.  [B, elems] tensors are contiguous and 16-byte aligned.
+ * ---------------------------------------------------------------------- */
+typedef struct CsFmStepArgs {
+    const void* x_base;       /* [B, elems] this step's or the saved sample (io_dtype, or fp32 when x_is_f32) */
+    const void* v2;           /* [B, elems] this step's model output                */
+    const void* v1;           /* [B, elems] the saved model output, or NULL         */
+    float c;                  /* dt | 0.5 dt_saved | dt_saved + (sigma_next - sigma) */
+    int B;
+    int64_t elems;            /* elements per sample                                */
+    int io_dtype;             /* dtype of v1, v2 (and of x_base unless x_is_f32)    */
+    int out_dtype;            /* dtype of x_out: io_dtype, or CS_F32                */
+    int x_is_f32;             /* as CsStepArgs::x_is_f32                            */
+    void* x_out;              /* [B, elems]                                         */
+} CsFmStepArgs;
+
+int cs_fm_general_step(const CsFmStepArgs* args, void* stream);
+
+/* ------------------------------------------------------------------------
  * SD1.5 UNet2DConditionModel forward (denoiser).  See DESIGN.md for the
  * activation layout (NHWC fp16) and the kernels behind it.
  * ---------------------------------------------------------------------- */

@@ -5,7 +5,11 @@ Algorithmic bytes per step: passes = [x] + [eps_u, eps_c] + [hist 
 ``--dpm``: the Multistep DPM-Solver update (cs_dpm_multistep_step) in the engine's form -- fp32 state, fp16 model outputs, CFG, second order, the fp16
 copy of the result in the same pass -- next to cs_lms_ddim_step with a history of 2 on the same tensors (the same 18 bytes per element), and a 1 GiB
 device copy (read + write bytes, what bench.py --full reports as dtod_copy_1gib_tbps) as the rate both are a share of.  The two kernels are timed
-as hipGraph replays of 500 captured launches (a Python launch loop measures the host's enqueue rate at this size), alternating, median of 5."""
+as hipGraph replays of 500 captured launches (a Python launch loop measures the host's enqueue rate at this size), alternating, median of 5.
+
+``--fm``: the flow-matching baselines' update (cs_fm_general_step; Euler form x + dt v, Heun form x + c (v1 + v2)) at FLUX's packed latent size
+[1, 4096, 64] bf16 next to cs_lms_euler_step with a history of one on the same tensors, timed the same way in the same run as the 1 GiB copy.  At
+0.5 MB per tensor the kernels are launch-latency-bound: the figure is microseconds per launch, not a share of a roofline."""
 import ctypes as C, json, os, sys
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -99,6 +103,41 @@ def run_dpm(B=32, elems=4 * 64 * 64):
                          GBps=round(nbytes / us / 1e3, 1), copy_1gib_GBps=round(copy_gbps, 1), share_of_copy_rate=round(nbytes / us / 1e3 / copy_gbps, 3)))
     return rows
 
+
+def run_fm(B=1, elems=4096 * 64):
+    t = lambda: torch.randn(B, elems, device=dev).bfloat16()
+    x, v, v1, out = t(), t(), t(), t()
+    f = L.CsFmStepArgs()
+    f.x_base, f.v2, f.v1, f.c, f.x_out = x.data_ptr(), v.data_ptr(), None, -0.1, out.data_ptr()
+    f.B, f.elems, f.io_dtype, f.out_dtype = B, elems, L.CS_BF16, L.CS_BF16
+    fh = L.CsFmStepArgs.from_buffer_copy(f)
+    fh.v1 = v1.data_ptr()
+    actions = torch.zeros(B, 1, device=dev)
+    a = L.CsStepArgs()
+    a.x, a.eps_text, a.m, a.order_dim, a.scaler_dim = x.data_ptr(), v.data_ptr(), 1, 2, 0
+    a.actions, a.actions_stride, a.B, a.elems = actions.data_ptr(), 1, B, elems
+    a.io_dtype = a.out_dtype = L.CS_BF16
+    a.x_out, a.dt = out.data_ptr(), -0.1
+    src = torch.randn(1 << 28, device=dev); dst = torch.empty_like(src)
+    copy_gbps = 2.0 * (1 << 30) / time_us(lambda: dst.copy_(src), 20) / 1e3
+    del src, dst
+    kernels = (("cs_fm_general_step", lib.cs_fm_general_step, f, 3), ("cs_fm_general_step_v1", lib.cs_fm_general_step, fh, 4),
+               ("cs_lms_euler_step_m1", lib.cs_lms_euler_step, a, 3))
+    times = {name: [] for name, _, _, _ in kernels}
+    for _ in range(5):                                        # alternate the kernels; report the median window
+        for name, fn, args, _ in kernels:
+            times[name].append(graph_us(lambda: L.check(fn(C.byref(args), L.stream_ptr(dev)))))
+    rows = []
+    for name, _, _, passes in kernels:
+        us, nbytes = sorted(times[name])[2], passes * B * elems * 2
+        rows.append(dict(kernel=name, B=B, elems=elems, dtype="bfloat16", us=round(us, 2), us_min_max=[round(min(times[name]), 2), round(max(times[name]), 2)],
+                         MB=round(nbytes / 1e6, 2), GBps=round(nbytes / us / 1e3, 1), copy_1gib_GBps=round(copy_gbps, 1)))
+    return rows
+
+
+if "--fm" in sys.argv:
+    for r in run_fm(): print(json.dumps(r))
+    sys.exit(0)
 
 if "--dpm" in sys.argv:
     for r in run_dpm(): print(json.dumps(r))
