@@ -90,6 +90,38 @@ __global__ __launch_bounds__(256) void advantages_kernel(const float* __restrict
     }
 }
 
+// adv[b*(n-1) + j][a] = (r[b] - clamp(mean, *base, hi)) / (std_unbiased + 1e-8) * masks[b*(n-1) + j][a]      (edit_ppo/train_ppo.py:326-341)
+// The centre is the batch mean raised to the baseline rollout's reward (read from the device: no host sync) and capped at hi, in
+// torch.clamp's order (min(max(mean, base), hi)); the spread is taken around the mean, not around the centre; no x 10.
+__global__ __launch_bounds__(256) void advantages_baseline_kernel(const float* __restrict__ r, const float* __restrict__ base, float hi, int B, int steps,
+                                                                  int A, const float* __restrict__ masks, float* __restrict__ out) {
+    __shared__ float red[4];
+    __shared__ float stat[2];
+    float s = 0.f;
+    for (int i = threadIdx.x; i < B; i += 256) s += r[i];
+    s = wave_sum(s);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+    __syncthreads();
+    const float mean = (red[0] + red[1] + red[2] + red[3]) / (float)B;
+    __syncthreads();
+    float q = 0.f;
+    for (int i = threadIdx.x; i < B; i += 256) { const float d = r[i] - mean; q += d * d; }
+    q = wave_sum(q);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = q;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        stat[0] = mean != mean ? mean : fminf(fmaxf(mean, base[0]), hi);             // torch.clamp keeps a NaN mean
+        stat[1] = sqrtf((red[0] + red[1] + red[2] + red[3]) / (float)(B - 1));      // B == 1 -> 0/0 = NaN, like torch.std
+    }
+    __syncthreads();
+    const float den = stat[1] + 1e-8f;
+    const long total = (long)B * steps * A;
+    for (long i = threadIdx.x; i < total; i += 256) {
+        const int b = (int)(i / ((long)steps * A));
+        out[i] = (r[b] - stat[0]) / den * masks[i];
+    }
+}
+
 // loss = -mean_{r,a} min(adv ratio, adv clip(ratio)) - coef * mean(entropy);  ratio[r] = exp(sum_a log(p+1e-9) - sum_a log(q+1e-9))
 __global__ __launch_bounds__(256) void ppo_loss_kernel(const float* __restrict__ cur, const float* __restrict__ old, const float* __restrict__ ent,
                                                        const float* __restrict__ adv, int R, int A, float clip, float coef, float* __restrict__ out) {
@@ -133,7 +165,7 @@ __global__ __launch_bounds__(256) void policy_row_kernel(PolicyRowArgs a) {
     const CsFactorNet& n = a.net;
     const int IN = n.in_dim, H = n.hidden, A = n.action_dims, K = n.num_actions, AK = A * K;
     float* h0 = sm; float* h1 = h0 + POL_MAX_IN; float* h2 = h1 + H; float* lg = h2 + H; float* d2 = lg + AK; float* d1 = d2 + H;
-    float* sc = d1 + H;                                // [A]: s, H, (scratch)
+    float* sc = d1 + H;                                // 4 x [POL_MAX_A]: s, H, selected bin, unclamped mass
     __shared__ float rowstat[4];
     const int r = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     if (tid < IN) h0[tid] = tid < 2 ? a.x[(size_t)r * 2 + tid] * n.input_scale : a.cosf[(size_t)r * (IN - 2) + tid - 2];
@@ -170,6 +202,14 @@ __global__ __launch_bounds__(256) void policy_row_kernel(PolicyRowArgs a) {
         float ent = 0.f;
         for (int k = lane; k < K; k += 64) { const float p = lg[ad * K + k] * inv; lg[ad * K + k] = p; ent -= p * logf(fminf(fmaxf(p, 1.1920929e-07f), 1.f - 1.1920929e-07f)); }
         ent = wave_sum(ent);
+        // Categorical clamps the probabilities to [eps, 1 - eps] before the log, and a clamped bin's log has no derivative: U = the mass of the
+        // bins that are NOT clamped, or -1 when none is (every row of an unsaturated softmax: the backward below is then the unclamped formula)
+        float un = 0.f, ncl = 0.f;
+        for (int k = lane; k < K; k += 64) {
+            const float p = lg[ad * K + k];
+            if (p < 1.1920929e-07f || p > 1.f - 1.1920929e-07f) ncl += 1.f; else un += p;
+        }
+        un = wave_sum(un); ncl = wave_sum(ncl);
         // nearest grid bin (first minimum), factor_net_ppo.py:174-178
         const float act = a.actions[(size_t)r * A + ad];
         float bd = INFINITY; int bi = 0;
@@ -178,7 +218,7 @@ __global__ __launch_bounds__(256) void policy_row_kernel(PolicyRowArgs a) {
             const float od = __shfl_xor(bd, off, 64); const int oi = __shfl_xor(bi, off, 64);
             if (od < bd || (od == bd && oi < bi)) { bd = od; bi = oi; }
         }
-        if (lane == 0) { sc[ad] = lg[ad * K + bi]; sc[POL_MAX_A + ad] = ent; sc[2 * POL_MAX_A + ad] = (float)bi; }
+        if (lane == 0) { sc[ad] = lg[ad * K + bi]; sc[POL_MAX_A + ad] = ent; sc[2 * POL_MAX_A + ad] = (float)bi; sc[3 * POL_MAX_A + ad] = ncl > 0.f ? un : -1.f; }
     }
     __syncthreads();
     if (tid == 0) {
@@ -203,7 +243,11 @@ __global__ __launch_bounds__(256) void policy_row_kernel(PolicyRowArgs a) {
         const float p = lg[j], s = sc[ad], Hh = sc[POL_MAX_A + ad];
         const float onehot = (k == (int)sc[2 * POL_MAX_A + ad]) ? 1.f : 0.f;
         float dz = rowstat[0] * (s / (s + 1e-9f)) * (onehot - p);
-        dz += rowstat[1] * (-p * (logf(fmaxf(p, 1.1920929e-07f)) + Hh));
+        dz += rowstat[1] * (-p * (logf(fminf(fmaxf(p, 1.1920929e-07f), 1.f - 1.1920929e-07f)) + Hh));
+        // saturated softmax (T = 0.01 on the FLUX side): dH/dz_k = -p_k (L_k + H) - p_k (u_k - U) with L the clamped log, u_k = 1 where p_k is inside
+        // the clamp range and U = sum_k p_k u_k; with no clamped bin u = U = 1 and the second term is dropped, not evaluated
+        const float U = sc[3 * POL_MAX_A + ad];
+        if (U >= 0.f) dz += rowstat[1] * (-p * (((p < 1.1920929e-07f || p > 1.f - 1.1920929e-07f) ? 0.f : 1.f) - U));
         lg[j] = dz * n.inv_temperature;
     }
     __syncthreads();
@@ -320,6 +364,17 @@ int cs_ppo_advantages(const float* rewards, int B, int recorded_steps, int A, co
     return CS_OK;
 }
 
+int cs_ppo_advantages_baseline(const float* rewards, const float* base_reward, float clip_hi, int B, int recorded_steps, int A, const float* masks,
+                               float* out, void* stream) {
+    if (B < 0 || recorded_steps < 0 || A < 0) CS_FAIL(CS_E_ARG, "negative size");
+    if (B == 0 || recorded_steps == 0 || A == 0) return CS_OK;
+    if (!rewards || !base_reward || !masks || !out) CS_FAIL(CS_E_ARG, "null pointer");
+    hipLaunchKernelGGL(advantages_baseline_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, rewards, base_reward, clip_hi, B, recorded_steps, A, masks,
+                       out);
+    CS_CHECK_LAUNCH();
+    return CS_OK;
+}
+
 int cs_ppo_loss(const float* curr_probs, const float* old_probs, const float* entropy, const float* advantages, int R, int A, float clip_range,
                 float entropy_coef, float* loss, void* stream) {
     if (R <= 0 || A <= 0) CS_FAIL(CS_E_SHAPE, "ppo_loss: empty batch");
@@ -358,7 +413,7 @@ int cs_ppo_policy_grads(const CsFactorNet* net, const float* x, const float* cos
     float* ws = (float*)workspace;
     a.h0 = ws; ws += (size_t)R * IN; a.h1 = ws; ws += (size_t)R * H; a.h2 = ws; ws += (size_t)R * H; a.dlog = ws; ws += (size_t)R * AK;
     a.d2 = ws; ws += (size_t)R * H; a.d1 = ws; ws += (size_t)R * H; a.part = ws;
-    const size_t lds = (size_t)(POL_MAX_IN + 4 * H + AK + 3 * POL_MAX_A) * sizeof(float);
+    const size_t lds = (size_t)(POL_MAX_IN + 4 * H + AK + 4 * POL_MAX_A) * sizeof(float);
     hipLaunchKernelGGL(policy_row_kernel, dim3(R), dim3(256), lds, s, a);
     // grads packed in state-dict order: w0 [H, IN], b0 [H], w1 [H, H], b1 [H], w2 [AK, H], b2 [AK]
     float* g_w0 = grads; float* g_b0 = g_w0 + (size_t)H * IN; float* g_w1 = g_b0 + H; float* g_b1 = g_w1 + (size_t)H * H;

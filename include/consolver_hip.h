@@ -409,6 +409,12 @@ int cs_image_psnr(const void* pred, const void* target, int B, int64_t elems, in
  * j over the recorded steps (n - 1) (train_ppo.py:376-390).  All fp32. */
 int cs_ppo_advantages(const float* rewards, int B, int recorded_steps, int A, const float* masks,
                       float* out, void* stream);
+/* The FLUX trainer's form (edit_ppo/train_ppo.py:326-341): advantages[(b, j), a] =
+ * (r[b] - min(max(mean(r), *base_reward), clip_hi)) / (std_unbiased(r) + 1e-8) * masks[(b, j), a] -- no x 10.
+ * base_reward: ONE fp32 on the device (the reward of the baseline rollout), so no host sync sits
+ * between reward and update.  One workgroup, no atomics: deterministic.  All fp32. */
+int cs_ppo_advantages_baseline(const float* rewards, const float* base_reward, float clip_hi, int B,
+                               int recorded_steps, int A, const float* masks, float* out, void* stream);
 /* value of the clipped surrogate + entropy bonus (train_ppo.py:408-421); inputs [R, A] fp32,
  * loss: one fp32 on the device. */
 int cs_ppo_loss(const float* curr_probs, const float* old_probs, const float* entropy,
