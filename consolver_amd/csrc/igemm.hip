@@ -1680,6 +1680,260 @@ __global__ __launch_bounds__(512, 2) void gemm_w8_kernel(IgemmParams p) {
     else igemm_epilogue<GEGLU, NT, MT, NT, LinearRows, 2, LNM, true, EPI>(p, acc, LinearRows{m_blk + wm * 64, p.M}, n_blk + wn * (BNX / 2), lane, smem + w * 11264, ln_tab, ln_rows);
 }
 
+// ------------------------------------------------------------------------------------------------
+// K = 320 linear layers with the ACTIVATIONS stationary in registers (gemm_as_kernel).  gemm_w8_kernel's k loop reads (64 + 160) x 64 halfs of fragments per 40
+// MFMAs and wave and runs at half the matrix pipe's rate against the CU's LDS port (DESIGN, "activation-stationary linears").  At K = 320 a wave's 64 rows x 320 k
+// are 4 m-tiles x 10 k-steps x 4 registers = 160 VGPRs of MFMA operand fragments -- what the 64 x 160 accumulator block costs there -- so here:
+//   * a workgroup (8 waves, two per SIMD) owns 512 rows and ALL of N; wave w loads its 64 x 320 activations ONCE, straight from global memory in the B-operand
+//     layout (row = lane & 15, k = 8 (lane >> 4) .. + 7 of each 32-deep step); rows past M are clamped to row M - 1;
+//   * the weights stream through a ring of three 20 KB LDS stages, one 32-row slice (w[n .. n + 32][0 .. 320), GEGLU: a 16-column value block + its gate block) per
+//     stage, laid out [5 k-chunks][32 rows][128 B] with gemm_w8_kernel's swizzle; 20 one-KiB buffer_load ... lds pieces per stage, three per wave (four pieces are
+//     fetched by two waves each: same bytes to the same place);
+//   * per slice a wave runs 2 n-tiles x 10 k-steps x 4 m-tiles = 80 MFMAs into 32 accumulator registers: one chain per accumulator, k steps 0 .. 9 in order,
+//     weights = MFMA A, activations = MFMA B -- bit for bit gemm_w8_kernel's accumulators; 20 fragment reads (256 B per MFMA against 358 B there);
+//   * the epilogue of a slice (the arithmetic of igemm_epilogue_impl, LTAB forms) goes through a wave-private 64-row x 128-byte LDS patch that collects two (GEGLU:
+//     four) slices = 64 output columns, then leaves as eight 16-byte-per-lane stores of whole 128-byte lines.  Waves 4-7 run the epilogue of slice j - 1 behind
+//     the barrier of slice j, waves 0-3 that of slice j in front of the next barrier: while one wave of a SIMD multiplies its partner converts and stores.
+// Waits.  vmcnt counts loads, stores and LDS-DMA together, in issue order, and hipcc drains it (vmcnt(0)) in front of any LDS access while an LDS-DMA it knows of
+// is in flight.  So the DMA is issued from inline assembly (hipcc does not see it), and the wait for stage j at the top of slice j is hand-counted: behind stage
+// j's three pieces this wave issued the three pieces of stage j + 1 and, where one of its two epilogues in between flushed a patch, eight stores: vmcnt(3) or
+// vmcnt(11); at the last slice, behind which nothing was staged, vmcnt(0) or vmcnt(8) -- so no LDS-DMA is in flight when a wave ends.  For the count to be exact every
+// store of a flush is issued unconditionally: a patch row past M goes to row M - 1, whose value it equals (clamped activations, clamped row constants).
+// ------------------------------------------------------------------------------------------------
+typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
+// one LDS-DMA piece hipcc neither counts nor waits for: 16 bytes per lane from rsrc + voff + soff to LDS lds_dst + 16 lane (M0 saved and restored: it is the compiler's)
+__device__ __forceinline__ void dma16_uncounted(unsigned lds_dst, unsigned voff, u32x4_t rsrc, unsigned soff) {
+    unsigned keep;
+    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 4\n\tbuffer_load_dwordx4 %2, %3, %4 offen lds\n\ts_mov_b32 m0, %0"
+                 : "=&s"(keep) : "s"(lds_dst), "v"(voff), "s"(rsrc), "s"(soff) : "memory");
+}
+// first MFMA of an accumulator chain: C = 0 as an inline constant instead of 32 v_mov per slice
+__device__ __forceinline__ void mfma_first(f32x4& c, const f16x8& a, const f16x8& b) {
+    asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, 0" : "=&v"(c) : "v"(a), "v"(b));
+}
+constexpr int AS_SLICE = 32 * 640, AS_RING = 3, AS_PATCH = 8192;
+// dynamic LDS: the ring, eight patches, 512 x (rstd, mean rstd), the (b' | s) tables (or the bias)
+static inline size_t gemm_as_lds(int N) { return (size_t)AS_RING * AS_SLICE + 8 * AS_PATCH + 512 * 8 + (size_t)N * 8; }
+constexpr int AS_MAX_N = (160 * 1024 - AS_RING * AS_SLICE - 8 * AS_PATCH - 512 * 8) / 8;      // = 4096
+
+template <bool GEGLU, int LNM>
+__global__ __launch_bounds__(512) void gemm_as_kernel(IgemmParams p) {
+    static_assert(LNM == 0 || LNM == 1, "bias or folded-LayerNorm epilogue");
+    constexpr int KS = 10, MT = 4, NQ = 2 * KS, LA = 3;
+    constexpr int G = GEGLU ? 4 : 2;            // slices per 64-column group of the output
+    constexpr int CPS = GEGLU ? 16 : 32;        // output columns per slice
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int m_wg = blockIdx.x * 512, m_base = m_wg + w * 64;
+    const int NS = p.N >> 5, Nout = GEGLU ? (p.N >> 1) : p.N;
+    char* const patch = smem + AS_RING * AS_SLICE + w * AS_PATCH;
+    char* const lnx = smem + AS_RING * AS_SLICE + 8 * AS_PATCH;
+    const int gq = lane >> 4, i16 = lane & 15, g4 = gq * 4;
+
+    // ---- activations: 40 fragments, one 16-byte load each ---------------------------------------------------------------------------------------
+    f16x8 fa[KS][MT];
+#pragma unroll
+    for (int j = 0; j < MT; ++j) {
+        const int m = min(m_base + j * 16 + i16, p.M - 1);
+        const f16* ap = p.a0 + (size_t)m * 320 + gq * 8;
+#pragma unroll
+        for (int s = 0; s < KS; ++s) fa[s][j] = *reinterpret_cast<const f16x8*>(ap + s * 32);
+    }
+
+    // ---- weight staging: piece pc of a stage = k-chunk pc >> 2, rows 8 (pc & 3) .. + 7; wave w fetches pieces (w >> 2) * 4 + (w & 3), + 8 and 16 + (w & 3) ------
+    const int pch = lane & 7, wr = (w & 3) * 8 + (lane >> 3);
+    const unsigned voff = (unsigned)(wr * 640 + ((pch ^ ((wr >> 1) & 7)) * 16));
+    const unsigned long long wa = (unsigned long long)(uintptr_t)p.w;
+    const u32x4_t rw = {(unsigned)wa, (unsigned)(wa >> 32) & 0xffffu, 0xffffffffu, 0x00020000u};
+    const unsigned sbase = lds_addr(smem);
+    const int kh = w >> 2;
+    auto stage = [&](int sl, int buf) __attribute__((always_inline)) {
+        const unsigned src = (unsigned)sl * AS_SLICE;                     // (a slice of w is 32 rows x 640 B = one stage)
+        const unsigned dst = sbase + buf * AS_SLICE + (w & 3) * 1024;
+        dma16_uncounted(dst + kh * 4096, voff, rw, src + kh * 128);
+        dma16_uncounted(dst + (2 + kh) * 4096, voff, rw, src + (2 + kh) * 128);
+        dma16_uncounted(dst + 4 * 4096, voff, rw, src + 4 * 128);
+    };
+    stage(0, 0);
+    if (NS > 1) stage(1, 1);
+    // row constants / tables of the workgroup's 512 rows and all N columns, one memory round trip behind the first stages
+    if constexpr (LNM == 1) ln_tile_prologue(p, lnx, tid, 512, m_wg, 512, 0, p.N, 1);
+    else bias_tile_prologue(p, lnx, tid, 0, p.N);
+#pragma unroll
+    for (int s = 0; s < KS; ++s)
+#pragma unroll
+        for (int j = 0; j < MT; ++j) asm volatile("" : "+v"(fa[s][j]));         // (hipcc's waits for the activation loads land here, not in the slice loop)
+    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+
+    // ---- fragment addressing (gemm_w8_kernel's): per-wave registers + immediates -----------------------------------------------------------------
+    const int swz = (lane >> 1) & 7;
+    const unsigned wfrag0 = sbase + i16 * 128 + (gq ^ swz) * 16, wfrag1 = sbase + i16 * 128 + ((4 + gq) ^ swz) * 16;
+    f32x4 acc[2][MT];
+
+    // top of slice j (sh: 1 for the waves whose epilogue runs one slice late): stage j has landed, every wave has left stage j - 1, stage j + 2 goes into its buffer
+    auto top = [&](int j, int sh) __attribute__((always_inline)) {
+        const int e1 = j - 1 - sh, e2 = j - 2 - sh;                        // the epilogues issued behind stage j's pieces
+        const bool st = (e1 >= 0 && e1 % G == G - 1) || (e2 >= 0 && e2 % G == G - 1);
+        if (j + 1 < NS) {                                                  // (stage j + 1 is in flight behind stage j)
+            if (st) asm volatile("s_waitcnt vmcnt(11) lgkmcnt(0)" ::: "memory");
+            else asm volatile("s_waitcnt vmcnt(3) lgkmcnt(0)" ::: "memory");
+        } else {                                                           // last slice: nothing was staged behind it, only a flush can be
+            if (st) asm volatile("s_waitcnt vmcnt(8) lgkmcnt(0)" ::: "memory");
+            else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+        }
+        __builtin_amdgcn_s_barrier();
+        if (j + 2 < NS) {
+            int b2 = j + 2; b2 -= (b2 / AS_RING) * AS_RING;
+            stage(j + 2, b2);
+        }
+    };
+    // the 80 MFMAs of a slice out of stage buffer buf: item q = (k step q >> 1, n-tile q & 1), fragments through a ring of four, LA items ahead
+    auto mm = [&](int buf) __attribute__((always_inline)) {
+        const unsigned b0 = wfrag0 + buf * AS_SLICE, b1 = wfrag1 + buf * AS_SLICE;
+        f16x8 fw[LA + 1];
+        auto rd = [&](auto qc) __attribute__((always_inline)) {
+            constexpr int q = decltype(qc)::value, s = q >> 1, i = q & 1;
+            lds_read<(s >> 1) * 4096 + i * 2048>(fw[q % (LA + 1)], (s & 1) ? b1 : b0);
+        };
+        static_for<LA>([&](auto qc) { rd(qc); });
+        static_for<NQ>([&](auto qc) {
+            constexpr int q = decltype(qc)::value, s = q >> 1, i = q & 1;
+            if constexpr (q + LA < NQ) rd(std::integral_constant<int, (q + LA < NQ ? q + LA : 0)>{});
+            asm volatile("s_waitcnt lgkmcnt(%0)" :: "n"(NQ - 1 - q < LA ? NQ - 1 - q : LA));
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int j = 0; j < MT; ++j) {
+                if constexpr (s == 0) mfma_first(acc[i][j], fw[q % (LA + 1)], fa[s][j]);
+                else mfma_inplace(acc[i][j], fw[q % (LA + 1)], fa[s][j]);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+        });
+        asm volatile("s_nop 7\n s_nop 7" ::: "memory");
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int j = 0; j < MT; ++j) asm volatile("" : "+v"(acc[i][j]));
+    };
+    // epilogue of slice j: igemm_epilogue_impl's phase 1 (same expressions, same explicit fused multiply-adds) into the patch, the patch out when its 64 columns are full
+    auto epi = [&](int j) __attribute__((always_inline)) {
+        const int slot = j % G;
+        const float* const tabf = reinterpret_cast<const float*>(lnx + 512 * 8);      // LNM == 1: b'[N] | s[N]
+        const f16* const tabh = reinterpret_cast<const f16*>(lnx);                     // LNM == 0: bias[N]
+#pragma unroll
+        for (int i = 0; i < (GEGLU ? 1 : 2); ++i) {
+            const int n = j * 32 + i * 16 + g4;                  // (GEGLU: row of the permuted weight, value half; its gate row is n + 16)
+            float bv[4] = {0.f, 0.f, 0.f, 0.f}, bg[4] = {0.f, 0.f, 0.f, 0.f};
+            float sv[4] = {0.f, 0.f, 0.f, 0.f}, sg[4] = {0.f, 0.f, 0.f, 0.f};
+            // zo: an offset (zero) hipcc cannot see through.  The GEGLU forms fetch the column constants again for every m-tile and every form fetches the rows'
+            // (rstd, mean rstd) where it uses them: kept in registers across the m-tiles (16 + 8 of them) or hoisted out of the slice loop they are live across the
+            // MFMAs, and the LayerNorm + GEGLU instantiation spilled -- scratch traffic counts on vmcnt like the stores and would break the hand-counted waits.
+            auto tables = [&](int zo) __attribute__((always_inline)) {
+                if constexpr (LNM == 1) {
+                    const f32x4 t = *reinterpret_cast<const f32x4*>(tabf + zo + n), u = *reinterpret_cast<const f32x4*>(tabf + zo + p.N + n);
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) { bv[r] = t[r]; sv[r] = u[r]; }
+                    if constexpr (GEGLU) {
+                        const f32x4 t2 = *reinterpret_cast<const f32x4*>(tabf + zo + n + 16), u2 = *reinterpret_cast<const f32x4*>(tabf + zo + p.N + n + 16);
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) { bg[r] = t2[r]; sg[r] = u2[r]; }
+                    }
+                } else if (p.bias) {
+                    const f16x4 t = *reinterpret_cast<const f16x4*>(tabh + zo + n);
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) bv[r] = (float)t[r];
+                    if constexpr (GEGLU) {
+                        const f16x4 u = *reinterpret_cast<const f16x4*>(tabh + zo + n + 16);
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) bg[r] = (float)u[r];
+                    }
+                }
+            };
+            if constexpr (!GEGLU) tables(0);
+#pragma unroll
+            for (int jm = 0; jm < MT; ++jm) {
+                int zo = 0;
+                asm volatile("" : "+v"(zo));
+                if constexpr (GEGLU) tables(zo);
+                float ln_r = 0.f, ln_mr = 0.f;
+                if constexpr (LNM == 1) {
+                    const f32x2 t = *reinterpret_cast<const f32x2*>(lnx + zo + (w * 64 + jm * 16 + i16) * 8);
+                    ln_r = t[0]; ln_mr = t[1];
+                }
+                f32x4 val;
+                if constexpr (LNM == 1) {
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) val[r] = __builtin_fmaf(acc[i][jm][r], ln_r, __builtin_fmaf(-ln_mr, sv[r], bv[r]));
+                } else {
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) val[r] = acc[i][jm][r] + bv[r];
+                }
+                f16x4 o;
+                if constexpr (GEGLU) {
+                    const f32x4 ga = acc[1][jm];
+                    f32x4 gt;
+                    if constexpr (LNM == 1) {
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) gt[r] = __builtin_fmaf(ga[r], ln_r, __builtin_fmaf(-ln_mr, sg[r], bg[r]));
+                    } else {
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) gt[r] = ga[r] + bg[r];
+                    }
+                    f32x2 g01, g23;
+                    gelu_erf4(f32x2{gt[0], gt[1]}, f32x2{gt[2], gt[3]}, g01, g23);
+                    o[0] = (f16)(val[0] * g01[0]); o[1] = (f16)(val[1] * g01[1]);
+                    o[2] = (f16)(val[2] * g23[0]); o[3] = (f16)(val[3] * g23[1]);
+                } else {
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) o[r] = (f16)val[r];
+                }
+                // patch [64 rows][128 B], the 16-byte chunk index XORed with row & 7 (rows are 128 B apart: unswizzled, a wave's 16 rows would share their banks)
+                const int row = jm * 16 + i16, col = slot * CPS + (GEGLU ? 0 : i * 16) + g4;
+                *reinterpret_cast<f16x4*>(patch + row * 128 + (((col >> 3) ^ (row & 7)) << 4) + (col & 7) * 2) = o;
+                if constexpr (GEGLU) __builtin_amdgcn_sched_barrier(0);          // (one m-tile's GELU chains at a time: interleaved over the four they cost ~30 more registers)
+            }
+        }
+        // the patch out: lane = (row lane >> 3 of each 8-row band, chunk lane & 7); eight stores of eight whole 128-byte lines each, ALWAYS issued (see the waits)
+        const int colbase = (j / G) * 64, ch = lane & 7, r8 = lane >> 3;
+        if (slot == G - 1) {
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                const int row = r8 + 8 * k;
+                const f16x8 v = *reinterpret_cast<const f16x8*>(patch + row * 128 + ((ch ^ r8) << 4));
+                const int m = min(m_base + row, p.M - 1);
+                *reinterpret_cast<f16x8*>(p.out + (size_t)m * Nout + colbase + ch * 8) = v;
+            }
+        } else if (j == NS - 1) {                                // the last group of an N that is no multiple of 64 output columns: nothing is waited for behind it
+            const int chn = (slot + 1) * CPS / 8;
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                const int row = r8 + 8 * k;
+                const f16x8 v = *reinterpret_cast<const f16x8*>(patch + row * 128 + ((ch ^ r8) << 4));
+                const int m = min(m_base + row, p.M - 1);
+                if (ch < chn) *reinterpret_cast<f16x8*>(p.out + (size_t)m * Nout + colbase + ch * 8) = v;
+            }
+        }
+    };
+
+    if (w < 4) {
+        for (int j = 0, buf = 0; j < NS; ++j) {
+            top(j, 0);
+            mm(buf);
+            epi(j);
+            buf = buf == AS_RING - 1 ? 0 : buf + 1;
+        }
+    } else {
+        for (int j = 0, buf = 0; j <= NS; ++j) {                 // (one more trip for the last epilogue: a second copy of it behind the loop kept a value live across the loop -- a spill)
+            if (j < NS) top(j, 1);
+            if (j > 0) epi(j - 1);
+            if (j == NS) break;
+            mm(buf);
+            buf = buf == AS_RING - 1 ? 0 : buf + 1;
+        }
+    }
+}
+
 // row statistics of a [M][C] tensor (value = x + x_lo when x_lo != null): stats[M][1][2] = (sum, sum of squares) per row.  The fallback of IgemmArgs::row_stats
 // for the kernels whose epilogue cannot leave them (split-K forms), and cs_op_row_stats.  One wave per row.
 __global__ __launch_bounds__(256) void row_stats_kernel(const f16* __restrict__ x, const f16* __restrict__ x_lo, int M, int C, float* __restrict__ stats, int lo8) {
@@ -2196,7 +2450,17 @@ static int launch_igemm_impl(const IgemmArgs& a, hipStream_t s, LaunchInfo* li) 
     if (cin % BK || a.c0 % BK || (a.c1 && !a.a1)) CS_FAIL(CS_E_SHAPE, "igemm: channels (%d,%d) must be multiples of %d", a.c0, a.c1, BK);
     if (a.B <= 0 || a.Ho <= 0 || a.Wo <= 0) return (a.B < 0) ? CS_E_SHAPE : CS_OK;
     if (a.taps == 1 && (a.stride != 1 || a.upsample || a.Hi != a.Ho || a.Wi != a.Wo)) CS_FAIL(CS_E_ARG, "igemm: 1x1 needs stride 1, no upsample");
-    if (a.geglu && (a.N % 256) && (a.N % 320)) CS_FAIL(CS_E_SHAPE, "igemm: GEGLU needs N %% 256 == 0 or N %% 320 == 0 (N=%d)", a.N);
+    // gemm_as_kernel (knob gemm_as): a K = 320 linear layer with a bias or folded-LayerNorm epilogue (GEGLU or not) and nothing else -- one A source, no lo plane, no
+    // time embedding / residual / lo plane out / statistics -- N a multiple of the 32-row weight slice that fits the LDS tables (which also keeps the weight buffer's
+    // 32-bit offsets in range), debug off.  The activation-size condition is gemm_w8_kernel's 32-bit-offset rule, kept so that the two routes cover the same shapes;
+    // this kernel itself reaches activations and outputs through 64-bit pointers.
+    // Auto: at least 192 512-row workgroups (the 64 x 64 level at batch >= 24; below that the 256 x 320 / 256 x 160 tiles have more workgroups to fill the chip with)
+    // and N >= 960 (QKV, the GEGLU projection): the N = 320 projections are at the HBM roof on gemm_w8_kernel and stay there.
+    const long long as_m = (long long)a.B * a.Ho * a.Wo;
+    const bool as_route = tune().gemm_as != 0 && a.taps == 1 && a.c1 == 0 && cin == 320 && !a.a0_lo && !a.temb && !a.res && !a.out_lo && !a.row_stats && !a.gn_stats &&
+                          a.N > 0 && a.N % 32 == 0 && a.N <= AS_MAX_N && !tune().debug && (double)as_m * 640 < 4.0e9 &&
+                          (tune().gemm_as == 2 || ((as_m + 511) / 512 >= 192 && a.N >= 960));
+    if (!as_route && a.geglu && (a.N % 256) && (a.N % 320)) CS_FAIL(CS_E_SHAPE, "igemm: GEGLU needs N %% 256 == 0 or N %% 320 == 0 (N=%d)", a.N);
     IgemmParams p;
     p.a0 = a.a0; p.a1 = a.a1; p.c0 = a.c0; p.c1 = a.c1;
     p.Hi = a.Hi; p.Wi = a.Wi; p.Ho = a.Ho; p.Wo = a.Wo; p.HoWo = a.Ho * a.Wo;
@@ -2234,6 +2498,20 @@ static int launch_igemm_impl(const IgemmArgs& a, hipStream_t s, LaunchInfo* li) 
     p.gn_stats = stats_ok ? a.gn_stats : nullptr;
     p.gm = 1; p.pn = 0;
     const double a_bytes = 2.0 * a.B * a.Hi * a.Wi * cin, w_bytes = 2.0 * a.N * a.taps * cin;
+    if (as_route) {
+        typedef void (*as_fn)(IgemmParams);
+        static const as_fn asv[4] = {gemm_as_kernel<false, 0>, gemm_as_kernel<true, 0>, gemm_as_kernel<false, 1>, gemm_as_kernel<true, 1>};
+        static bool configured_as = false;
+        if (!configured_as) {
+            for (as_fn f : asv) CS_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(f), hipFuncAttributeMaxDynamicSharedMemorySize, (int)gemm_as_lds(AS_MAX_N)));
+            configured_as = true;
+        }
+        const int av = 2 * lnm + (a.geglu ? 1 : 0);
+        route_set(8, 32, av);
+        hipLaunchKernelGGL(asv[av], dim3((p.M + 511) / 512), dim3(512), gemm_as_lds(a.N), s, p);
+        CS_CHECK_LAUNCH();
+        return CS_OK;
+    }
     const int tiles_m = (p.M + BM - 1) / BM;
     int bn;
     if (a.N % 128 == 0) bn = 128;

@@ -13,6 +13,7 @@ struct TuneSet {
     int halo = 1;           // conv3_halo_kernel use: 0 never, 1 when it pays, 2 whenever the shape allows (tests), 3 force the 320 / 256-wide form, 4 never the wide form
     int conv_lw = 1;        // 1: stride-1 3x3 convs with N % 160 == 0 or N % 128 == 0 through conv3_lw_kernel (loader waves), 2: the same without its immediate-offset (FAST) path, 3: N % 160 == 0 only, 0: the 8-wave halo kernels
     int gemm_w8 = 1;        // 1: the 256 x 320 linear / 1x1 layers through gemm_w8_kernel (hand-scheduled k loop), 0: gemm_big_kernel
+    int gemm_as = 1;        // K = 320 linear layers through gemm_as_kernel (activations stationary in registers, weights streamed in 32-row slices): 0 never, 1 when at least 192 512-row workgroups fill the chip and N >= 960, 2 whenever the layer is eligible (tests)
     int gemm_lw = 1;        // 1: the 256 x 160 linear / 1x1 layers (too few 256 x 320 tiles) through gemm_lw_kernel (loader waves), 0: gemm_big_kernel<false, 160>
     int gemm2_w8 = 1;       // 1: gemm2 main launches run the hand-scheduled k loop (W8 instantiation of gemm2_kernel; bit-identical), 0: the compiler-scheduled one
     int attn_lw = 1;        // 1: head dim 40 self-attention (Nq % 256 == 0, Nk % 64 == 0) runs attn40_lw_kernel, 2: the same with 16x16x32 MFMAs for both k steps (bit-identical to attn_kernel), 0: attn_kernel
@@ -121,7 +122,7 @@ inline bool igemm_sub_pixel(const IgemmArgs& a, const TuneSet& t) {
 }
 // Which kernel the calling thread's last launch_igemm took (cs_debug_igemm_last_route; tests assert the dispatch with it).  Host only: one store per launch.
 // family: 0 nothing launched, 1 igemm_kernel, 2 conv3_halo_kernel, 3 conv3_lw_kernel, 4 conv3_lw_kernel in the sub-pixel form, 5 gemm_big_kernel, 6 gemm_w8_kernel,
-// 7 gemm_lw_kernel.  variant: the index into the site's function-pointer table (variants / sub / w8 / lwk); igemm_kernel: LNM | EPI << 2 | GEGLU << 4 | CONV3 << 5;
+// 7 gemm_lw_kernel, 8 gemm_as_kernel (variant 2 LNM + GEGLU, tile_cols 32).  variant: the index into the site's function-pointer table (variants / sub / w8 / lwk); igemm_kernel: LNM | EPI << 2 | GEGLU << 4 | CONV3 << 5;
 // conv3_halo_kernel: 1 with the fused upsample; gemm_big_kernel: 1 with GEGLU.  fallback: bit 0 launch_gn_stats64 ran behind the launch, bit 1 row_stats_kernel.
 struct IgemmRoute { int family = 0, tile_cols = 0, variant = 0, splits = 1, gn_done = 0, row_groups = 0, fallback = 0; };
 extern thread_local IgemmRoute t_igemm_route;      // (defined in ops_api.cpp, next to the knob sets)

@@ -26,6 +26,7 @@ static const TuneKnob* tune_knobs(int* n) {
         {"conv_out_mfma", &TuneSet::conv_out_mfma, 0, 1, false},
         {"up_fold", &TuneSet::up_fold, 0, 2, false},
         {"head_x2", &TuneSet::head_x2, 0, 1, false},
+        {"gemm_as", &TuneSet::gemm_as, 0, 2, false},
     };
     *n = (int)(sizeof(k) / sizeof(k[0]));
     return k;

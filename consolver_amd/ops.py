@@ -234,13 +234,14 @@ def ln_fold_pack(w, bias, gamma, beta):
     return wo, so, bo
 
 
-def linear_ln(x, w_folded, ln_s, ln_b, stats, groups, eps=1e-5, geglu=False, splitk=True):
+def linear_ln(x, w_folded, ln_s, ln_b, stats, groups, eps=1e-5, geglu=False, splitk=True, out=None):
     """out = LayerNorm(h) W^T + b with the LayerNorm folded in (cs_op_linear_ln): x is the RAW hidden state [M, K] fp16, (stats, groups) the row statistics
     its producer left (linear_x2 / conv2d_x2 / xattn_block_x2 with row_stats=True, or row_stats())."""
     _f16(x, "x")
     M, K = x.shape
     N = w_folded.shape[0]
-    out = torch.empty(M, N // 2 if geglu else N, dtype=torch.float16, device=x.device)
+    if out is None:
+        out = torch.empty(M, N // 2 if geglu else N, dtype=torch.float16, device=x.device)
     ws = None
     if splitk:
         ws = _SPLITK_WS.get(x.device)
@@ -501,7 +502,7 @@ def xattn_block(h, ln_gamma, ln_beta, wq, kv, wo, bo, heads=8, eps=1e-5, hw=None
 
 
 IgemmRoute = collections.namedtuple("IgemmRoute", "family tile_cols variant splits gn_done row_groups fallback")
-IGEMM_FAMILIES = ("none", "generic", "halo", "conv3_lw", "sub_pixel", "gemm_big", "gemm_w8", "gemm_lw")
+IGEMM_FAMILIES = ("none", "generic", "halo", "conv3_lw", "sub_pixel", "gemm_big", "gemm_w8", "gemm_lw", "gemm_as")
 
 
 def igemm_last_route():

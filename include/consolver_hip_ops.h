@@ -266,6 +266,9 @@ int cs_op_attention_bias(const void* q, int q_stride, const void* k, int k_strid
  *                halo kernels;
  *   "gemm_w8":   1 (default) the 256x320 GEMM runs its hand-scheduled k loop (gemm_w8_kernel; needs 32-bit operand offsets), 0 the
  *                compiler-scheduled gemm_big_kernel (bit-identical results);
+ *   "gemm_as":   K = 320 linear layers (one source, no lo plane, bias or folded-LayerNorm epilogue with or without GEGLU, N % 32 == 0, N <= 4096, 32-bit operand
+ *                offsets, debug off) on gemm_as_kernel -- a wave keeps its 64 x 320 activations in registers and walks N in 32-row weight slices; bit-identical to
+ *                gemm_w8_kernel: 0 never, 1 (default) when ceil(M / 512) >= 192 and N >= 960, 2 whenever the layer is eligible (tests);
  *   "gemm_lw":   1 (default) layers served by the 256x160 GEMM tile run the loader-wave kernel (gemm_lw_kernel), 0 gemm_big_kernel<.,160>;
  *   "gemm2_w8":  1 (default) cs_op_gemm2 / cs_op_gemm2_pair run the hand-scheduled k loop of gemm2_kernel where 32-bit operand offsets suffice (bit-identical),
  *                0 the compiler-scheduled loop;
@@ -293,10 +296,10 @@ int cs_debug_attn_trace_read(void* dst_host, size_t bytes);
 /* Which kernel the CALLING THREAD's last conv / linear launch (cs_op_conv2d* / cs_op_conv_up_sub / cs_op_conv_down / cs_op_linear*) took: writes up to n ints to
  * out (host) and returns how many the record has (7):
  *   [0] family: 0 nothing launched (refused or empty), 1 igemm_kernel (generic), 2 conv3_halo_kernel, 3 conv3_lw_kernel, 4 conv3_lw_kernel in the sub-pixel form,
- *       5 gemm_big_kernel, 6 gemm_w8_kernel, 7 gemm_lw_kernel;
- *   [1] tile columns: 128, 160, 256 or 320;
+ *       5 gemm_big_kernel, 6 gemm_w8_kernel, 7 gemm_lw_kernel, 8 gemm_as_kernel;
+ *   [1] tile columns: 128, 160, 256 or 320 (gemm_as_kernel: 32, its weight slice);
  *   [2] variant: the index into that launch site's function-pointer table (csrc/igemm.hip: variants / sub / w8 / lwk); igemm_kernel: LNM | EPI << 2 | GEGLU << 4 |
- *       CONV3 << 5 of the instantiation; conv3_halo_kernel: 1 with the fused upsample; gemm_big_kernel: 1 with GEGLU;
+ *       CONV3 << 5 of the instantiation; conv3_halo_kernel: 1 with the fused upsample; gemm_big_kernel: 1 with GEGLU; gemm_as_kernel: 2 LNM + GEGLU;
  *   [3] splits: the split-K factor (1 = none; > 1: a reduce kernel ran behind the main one);
  *   [4] gn_done: 1 when the kernel (or the split-K reduce) left the GroupNorm statistics itself;
  *   [5] row_groups: column groups of the row statistics the epilogue left (0: it left none);

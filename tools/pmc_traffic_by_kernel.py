@@ -63,7 +63,7 @@ def klass(name):
     n = short(name)
     if n.startswith(("conv3_lw", "conv3_halo")) or re.match(r"igemm_kernel<\d+, ?true", n):
         return "conv3x3_igemm"
-    if n.startswith(("gemm_w8", "gemm_lw", "gemm_big", "igemm_kernel", "splitk_reduce")):
+    if n.startswith(("gemm_w8", "gemm_as", "gemm_lw", "gemm_big", "igemm_kernel", "splitk_reduce")):
         return "gemm_1x1_linear"
     if n.startswith(("attn", "xattn")) or "attn" in n[:24]:
         return "attention (self + cross)"
