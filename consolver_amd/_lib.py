@@ -39,6 +39,15 @@ class CsDpmStepArgs(C.Structure):
                 ("conv_x", C.c_float), ("conv_e", C.c_float), ("cx", C.c_float), ("c0", C.c_float), ("c1", C.c_float)]
 
 
+class CsUnipcStepArgs(C.Structure):
+    _fields_ = [("x", C.c_void_p), ("eps_text", C.c_void_p), ("eps_uncond", C.c_void_p), ("guidance", C.c_float), ("x_last", C.c_void_p),
+                ("m_prev0", C.c_void_p), ("m_prev1", C.c_void_p), ("B", C.c_int), ("elems", C.c_int64), ("io_dtype", C.c_int), ("out_dtype", C.c_int),
+                ("x_is_f32", C.c_int), ("use_corr", C.c_int), ("x_out", C.c_void_p), ("m_out", C.c_void_p), ("x_last_out", C.c_void_p),
+                ("x_out_lp", C.c_void_p), ("lp_dtype", C.c_int),
+                ("conv_x", C.c_float), ("conv_e", C.c_float), ("a_x", C.c_float), ("a_0", C.c_float), ("a_1", C.c_float), ("a_n", C.c_float),
+                ("p_x", C.c_float), ("p_0", C.c_float), ("p_1", C.c_float)]
+
+
 class CsFmStepArgs(C.Structure):
     _fields_ = [("x_base", C.c_void_p), ("v2", C.c_void_p), ("v1", C.c_void_p), ("c", C.c_float), ("B", C.c_int), ("elems", C.c_int64),
                 ("io_dtype", C.c_int), ("out_dtype", C.c_int), ("x_is_f32", C.c_int), ("x_out", C.c_void_p)]
@@ -131,6 +140,7 @@ SYMBOLS = {
     "cs_lms_ddim_step": (C.c_int, [C.POINTER(CsStepArgs), C.c_void_p]),
     "cs_lms_euler_step": (C.c_int, [C.POINTER(CsStepArgs), C.c_void_p]),
     "cs_dpm_multistep_step": (C.c_int, [C.POINTER(CsDpmStepArgs), C.c_void_p]),
+    "cs_unipc_step": (C.c_int, [C.POINTER(CsUnipcStepArgs), C.c_void_p]),
     "cs_fm_general_step": (C.c_int, [C.POINTER(CsFmStepArgs), C.c_void_p]),
     "cs_psnr_workspace_bytes": (C.c_size_t, [C.c_int]),
     "cs_image_psnr": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_size_t,

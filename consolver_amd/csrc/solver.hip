@@ -5,6 +5,7 @@
 //   cs_lms_euler_step : same with the flow-matching Euler epilogue
 //                       (edit_ppo/scheduler_fmppo.py:400-436)
 //   cs_dpm_multistep_step : CFG combine + model-output conversion + Multistep DPM-Solver update (orders 1, 2)
+//   cs_unipc_step : CFG combine + x0 conversion + UniPC corrector of the previous update + predictor (bh1 / bh2, orders 1, 2)
 //   cs_fm_general_step : the flow-matching baselines' update (Euler / Heun / dpm-solver / multistep, edit_ppo/scheduler_fm.py:405-482)
 //   cs_factor_probs   : FactorNetPPO.forward_ (factor_net_ppo.py:137-157)
 //   cs_cosine_features: compute_cosine_similarity (factor_net_ppo.py:108-130)
@@ -21,6 +22,8 @@ template <typename T> struct Io;
 template <> struct Io<float> {
     static constexpr int VEC = 4;
     typedef f32x4 vec_t;
+    __device__ static vec_t load_raw(const void* p, int64_t i) { return *reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(p) + i); }
+    __device__ static void unpack(vec_t v, float* o) { o[0] = v[0]; o[1] = v[1]; o[2] = v[2]; o[3] = v[3]; }
     __device__ static void load(const void* p, int64_t i, float (&o)[4]) {
         f32x4 v = *reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(p) + i);
         o[0] = v[0]; o[1] = v[1]; o[2] = v[2]; o[3] = v[3];
@@ -35,6 +38,12 @@ template <> struct Io<float> {
 };
 template <> struct Io<f16> {
     static constexpr int VEC = 8;
+    typedef f16x8 vec_t;
+    __device__ static vec_t load_raw(const void* p, int64_t i) { return *reinterpret_cast<const f16x8*>(reinterpret_cast<const f16*>(p) + i); }
+    __device__ static void unpack(vec_t v, float* o) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) o[j] = (float)v[j];
+    }
     __device__ static void load(const void* p, int64_t i, float (&o)[8]) {
         f16x8 v = *reinterpret_cast<const f16x8*>(reinterpret_cast<const f16*>(p) + i);
 #pragma unroll
@@ -53,6 +62,12 @@ template <> struct Io<f16> {
 struct bf16_tag {};
 template <> struct Io<bf16_tag> {
     static constexpr int VEC = 8;
+    typedef u32x4 vec_t;
+    __device__ static vec_t load_raw(const void* p, int64_t i) { return *reinterpret_cast<const u32x4*>(reinterpret_cast<const u16*>(p) + i); }
+    __device__ static void unpack(vec_t v, float* o) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) { o[2 * j] = __uint_as_float(v[j] << 16); o[2 * j + 1] = __uint_as_float(v[j] & 0xffff0000u); }
+    }
     __device__ static void load(const void* p, int64_t i, float (&o)[8]) {
         u32x4 v = *reinterpret_cast<const u32x4*>(reinterpret_cast<const u16*>(p) + i);
 #pragma unroll
@@ -362,6 +377,159 @@ int launch_dpm_step(const CsDpmStepArgs* a, void* stream) {
     dim3 grid(gx, a->B), block(256);
     hipStream_t s = (hipStream_t)stream;
 #define LAUNCH(TI, TO) hipLaunchKernelGGL((dpm_step_kernel<TI, TO>), grid, block, 0, s, p)
+    if (io == CS_F32) LAUNCH(float, float);
+    else if (io == CS_F16 && od == CS_F16) LAUNCH(f16, f16);
+    else if (io == CS_F16) LAUNCH(f16, float);
+    else if (od == CS_BF16) LAUNCH(bf16_tag, bf16_tag);
+    else LAUNCH(bf16_tag, float);
+#undef LAUNCH
+    CS_CHECK_LAUNCH();
+    return CS_OK;
+}
+
+// ---------------------------------------------------------------- UniPC (bh1 / bh2, orders 1 and 2, x0 prediction)
+// One step of UniPC is the corrector of the PREVIOUS update (it needs this step's model output) followed by this step's predictor.  Both are
+// linear in the same tensors, so the step is one pass: the variant lives in nine host scalars (scheduling_unipc.py).  x is the predicted sample
+// (the previous predictor's output), x_last the previous step's corrected sample, m0 / m1 the converted outputs of the two previous steps.
+// As in fm_step_kernel there is no per-sample coefficient: the batch is one flat range and the vector body stays 16-byte aligned whatever elems is.
+struct UnipcParams {
+    const void* x; const void* ec; const void* eu; float g;
+    const void* x_last; const void* m0; const void* m1;
+    int64_t total;   // B * elems
+    void* x_out; void* m_out; void* x_last_out;
+    float conv_x, conv_e, a_x, a_0, a_1, a_n, p_x, p_0, p_1;
+    int corr;    // apply the corrector (else x_c = x)
+    void* x_lp;  // as StepParams::x_lp
+    int lp_bf16;
+};
+
+// x_c is rounded to the dtype it is stored in before the predictor reads it: the pass is a corrector launch followed by a predictor launch.
+// A history value that is not read arrives as zero (its coefficient is zero as well: the term adds an exact 0), so the update has no branch.
+template <typename TO>
+__device__ __forceinline__ void unipc_one(const UnipcParams& p, float x, float xl, float mn, float m0, float m1, float& xc, float& xn) {
+    const float c = Io<TO>::round(p.a_x * xl + p.a_0 * m0 + p.a_1 * m1 + p.a_n * mn);
+    xc = p.corr ? c : x;
+    xn = p.p_x * xc + p.p_0 * mn + p.p_1 * m0;
+}
+
+// V values of the state (x, x_last, x_c, x_next): the io vector, or two fp32 vectors beside 16-bit model outputs
+template <typename TS, int V>
+struct StateRaw {
+    static constexpr int N = V / Io<TS>::VEC;
+    static_assert(N == 1 || (V == 8 && Io<TS>::VEC == 4), "an fp32 state beside 8-wide 16-bit vectors");
+    typename Io<TS>::vec_t r[N];
+    __device__ void load(const void* p, int64_t i) {
+#pragma unroll
+        for (int k = 0; k < N; ++k) r[k] = Io<TS>::load_raw(p, i + k * Io<TS>::VEC);
+    }
+    __device__ void unpack(float (&o)[V]) const {
+#pragma unroll
+        for (int k = 0; k < N; ++k) Io<TS>::unpack(r[k], o + k * Io<TS>::VEC);
+    }
+};
+template <typename TS, int V>
+__device__ __forceinline__ void store_state(void* p, int64_t i, const float (&o)[V]) {
+    if constexpr (Io<TS>::VEC == V) {
+        Io<TS>::store(p, i, o);
+    } else {
+        const float a[4] = {o[0], o[1], o[2], o[3]}, b[4] = {o[4], o[5], o[6], o[7]};
+        Io<TS>::store(p, i, a); Io<TS>::store(p, i + 4, b);
+    }
+}
+
+template <typename TI, typename TO>
+__global__ __launch_bounds__(256) void unipc_step_kernel(UnipcParams p) {
+    constexpr int V = Io<TI>::VEC;
+    const int64_t nvec = p.total / V;
+    for (int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; v < nvec; v += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t i = v * V;
+        // every load is issued, as raw vectors, before the first value is converted (the branches are block-uniform): one round trip to memory per iteration
+        StateRaw<TO, V> rx, rxl = {};                 // (the state has the result's dtype: launch_unipc_step checks it)
+        typename Io<TI>::vec_t re, ru = {}, r0 = {}, r1 = {};
+        rx.load(p.x, i);
+        re = Io<TI>::load_raw(p.ec, i);
+        if (p.eu) ru = Io<TI>::load_raw(p.eu, i);
+        if (p.corr) rxl.load(p.x_last, i);
+        if (p.m0) r0 = Io<TI>::load_raw(p.m0, i);
+        if (p.m1) r1 = Io<TI>::load_raw(p.m1, i);
+        float x[V], xl[V], e[V], u[V], h0[V], h1[V], oc[V], on[V];
+        rx.unpack(x); rxl.unpack(xl);
+        Io<TI>::unpack(re, e); Io<TI>::unpack(ru, u); Io<TI>::unpack(r0, h0); Io<TI>::unpack(r1, h1);
+        if (p.eu) {
+#pragma unroll
+            for (int j = 0; j < V; ++j) e[j] = Io<TI>::round(u[j] + p.g * (e[j] - u[j]));
+        }
+#pragma unroll
+        for (int j = 0; j < V; ++j) {
+            e[j] = Io<TI>::round(p.conv_x * x[j] + p.conv_e * e[j]);
+            unipc_one<TO>(p, x[j], xl[j], e[j], h0[j], h1[j], oc[j], on[j]);
+        }
+        Io<TI>::store(p.m_out, i, e);
+        if (p.x_last_out) store_state<TO, V>(p.x_last_out, i, oc);
+        store_state<TO, V>(p.x_out, i, on);
+        if (p.x_lp) store_lp<V>(p.x_lp, i, on, p.lp_bf16);
+    }
+    // scalar tail (total % V != 0): handled by the first block
+    if (blockIdx.x == 0) {
+        for (int64_t i = nvec * V + threadIdx.x; i < p.total; i += blockDim.x) {
+            const float x = Io<TO>::load1(p.x, i);
+            const float xl = p.corr ? Io<TO>::load1(p.x_last, i) : 0.f;
+            float e = Io<TI>::load1(p.ec, i);
+            if (p.eu) { float u = Io<TI>::load1(p.eu, i); e = Io<TI>::round(u + p.g * (e - u)); }
+            e = Io<TI>::round(p.conv_x * x + p.conv_e * e);
+            const float h0 = p.m0 ? Io<TI>::load1(p.m0, i) : 0.f;
+            const float h1 = p.m1 ? Io<TI>::load1(p.m1, i) : 0.f;
+            Io<TI>::store1(p.m_out, i, e);
+            float xc, xn;
+            unipc_one<TO>(p, x, xl, e, h0, h1, xc, xn);
+            if (p.x_last_out) Io<TO>::store1(p.x_last_out, i, xc);
+            Io<TO>::store1(p.x_out, i, xn);
+            if (p.x_lp) store_lp1(p.x_lp, i, xn, p.lp_bf16);
+        }
+    }
+}
+
+int launch_unipc_step(const CsUnipcStepArgs* a, void* stream) {
+    if (!a) CS_FAIL(CS_E_ARG, "args is NULL");
+    if (a->B < 0 || a->elems < 0) CS_FAIL(CS_E_SHAPE, "negative shape");
+    const bool empty = (a->B == 0 || a->elems == 0);
+    if (!empty && (!a->x || !a->eps_text || !a->x_out || !a->m_out)) CS_FAIL(CS_E_ARG, "x, eps_text, x_out and m_out are required");
+    if (a->x_out_lp && (a->out_dtype != CS_F32 || (a->lp_dtype != CS_F16 && a->lp_dtype != CS_BF16)))
+        CS_FAIL(CS_E_ARG, "x_out_lp is the 16-bit copy (lp_dtype CS_F16 or CS_BF16) of an fp32 result (out_dtype CS_F32)");
+    const int io = a->io_dtype, od = a->out_dtype;
+    const bool pair_ok = (io == CS_F32 && od == CS_F32) || (io == CS_F16 && (od == CS_F16 || od == CS_F32)) || (io == CS_BF16 && (od == CS_BF16 || od == CS_F32));
+    if (!pair_ok) CS_FAIL(CS_E_DTYPE, "unsupported io/out dtype pair (%d,%d)", io, od);
+    if (a->x_is_f32 && io == CS_F32) CS_FAIL(CS_E_DTYPE, "x_is_f32 marks an fp32 sample beside 16-bit model outputs (io_dtype %d is fp32 already)", io);
+    // x_c has the sample's dtype (it is the next step's x_last), so the result dtype is the sample's
+    if ((a->x_is_f32 != 0) != (io != CS_F32 && od == CS_F32)) CS_FAIL(CS_E_DTYPE, "out_dtype %d is not the sample's dtype (x_is_f32 = %d, io_dtype %d)", od, a->x_is_f32, io);
+    if (empty) return CS_OK;
+    if (a->use_corr && !a->x_last) CS_FAIL(CS_E_ARG, "x_last is required with the corrector");
+    if (((a->use_corr && a->a_0 != 0.f) || a->p_1 != 0.f) && !a->m_prev0) CS_FAIL(CS_E_ARG, "m_prev0 is NULL but a_0 or p_1 is not zero");
+    if (a->use_corr && a->a_1 != 0.f && !a->m_prev1) CS_FAIL(CS_E_ARG, "m_prev1 is NULL but a_1 is not zero");
+    UnipcParams p;
+    p.x = a->x; p.ec = a->eps_text; p.eu = a->eps_uncond; p.g = a->guidance;
+    p.corr = a->use_corr != 0;
+    p.x_last = p.corr ? a->x_last : nullptr;
+    // a history tensor is read only where a coefficient uses it
+    p.m0 = ((p.corr && a->a_0 != 0.f) || a->p_1 != 0.f) ? a->m_prev0 : nullptr;
+    p.m1 = (p.corr && a->a_1 != 0.f) ? a->m_prev1 : nullptr;
+    p.total = (int64_t)a->B * a->elems;
+    p.x_out = a->x_out; p.m_out = a->m_out; p.x_last_out = a->x_last_out;
+    p.conv_x = a->conv_x; p.conv_e = a->conv_e;
+    p.a_x = a->a_x; p.a_0 = a->a_0; p.a_1 = a->a_1; p.a_n = a->a_n; p.p_x = a->p_x; p.p_0 = a->p_0; p.p_1 = a->p_1;
+    p.x_lp = a->x_out_lp; p.lp_bf16 = a->lp_dtype == CS_BF16;
+    // 16-byte loads / stores on every tensor (two per lane on an fp32 state next to 16-bit outputs; the 16-bit copy of a 4-wide fp32 result is 8 bytes)
+    if ((((uintptr_t)a->eps_text | (uintptr_t)a->eps_uncond | (uintptr_t)p.m0 | (uintptr_t)p.m1 | (uintptr_t)a->m_out | (uintptr_t)a->x | (uintptr_t)p.x_last |
+          (uintptr_t)a->x_out | (uintptr_t)a->x_last_out) & 15) || ((uintptr_t)a->x_out_lp & (a->x_is_f32 ? 15 : 7)))
+        CS_FAIL(CS_E_ARG, "x, x_last, eps_*, m_prev*, m_out, x_out, x_last_out and x_out_lp must be 16-byte aligned");
+    const int vec = (io == CS_F32) ? 4 : 8;
+    int64_t nvec = p.total / vec;
+    // the same capped grid as launch_step: ~8 blocks per CU overall, grid-stride the rest
+    int64_t gx = (nvec + 255) / 256;
+    if (gx > 2048) gx = 2048; if (gx < 1) gx = 1;
+    dim3 grid((unsigned)gx), block(256);
+    hipStream_t s = (hipStream_t)stream;
+#define LAUNCH(TI, TO) hipLaunchKernelGGL((unipc_step_kernel<TI, TO>), grid, block, 0, s, p)
     if (io == CS_F32) LAUNCH(float, float);
     else if (io == CS_F16 && od == CS_F16) LAUNCH(f16, f16);
     else if (io == CS_F16) LAUNCH(f16, float);
@@ -683,6 +851,7 @@ extern "C" {
 int cs_lms_ddim_step(const CsStepArgs* args, void* stream) { return launch_step<false>(args, stream); }
 int cs_lms_euler_step(const CsStepArgs* args, void* stream) { return launch_step<true>(args, stream); }
 int cs_dpm_multistep_step(const CsDpmStepArgs* args, void* stream) { return launch_dpm_step(args, stream); }
+int cs_unipc_step(const CsUnipcStepArgs* args, void* stream) { return launch_unipc_step(args, stream); }
 int cs_fm_general_step(const CsFmStepArgs* args, void* stream) { return launch_fm_step(args, stream); }
 
 int cs_factor_probs(const CsFactorNet* n, const float* x, int x_row_stride, const float* cos_feat, int B, float* probs, void* stream) {

@@ -70,7 +70,8 @@ class SDSamplingEngine:
         key = (B, tuple(shape), str(device), self.latents_dtype, self.eps_dtype)
         if self._bufs is None or self._bufs["key"] != key:
             cfg = self.scheduler.config
-            order = cfg.get("order_dim") or cfg["solver_order"]       # (DPMSolverMultistepScheduler keeps `solver_order` converted outputs)
+            # (DPMSolverMultistepScheduler keeps `solver_order` converted outputs; UniPCMultistepScheduler reads that many and writes one more: history_slots)
+            order = cfg.get("order_dim") or getattr(self.scheduler, "history_slots", None) or cfg["solver_order"]
             C, H, W = shape
             self._graph = self._graph_key = None      # a captured graph holds the OLD buffers' addresses (latents_dtype is a public attribute and part of the key)
             self._bufs = dict(

@@ -63,12 +63,13 @@ def _load_sd(path):
     return torch.load(path, map_location="cpu")
 
 
-SOLVERS = ("consistencysolver", "multistep-dpmsolver", "ddim")
+SOLVERS = ("consistencysolver", "multistep-dpmsolver", "ddim", "unipc", "amed")
 
 
-def make_scheduler(solver, order_dim=4, scaler_dim=0, use_conv=False, num_actions=11):
+def make_scheduler(solver, order_dim=4, scaler_dim=0, use_conv=False, num_actions=11, amed_schedule=None):
     """the in-tree equivalent of ``gen_ppo.load_pipeline(type=...)`` (gen_ppo.py:108-169) on SD1.5's schedule: the learned solver, the
-    Multistep-DPM-Solver baseline (:149-155) or eta = 0 DDIM on the learned solver's grid (baselines.py)."""
+    Multistep-DPM-Solver baseline (:149-155), UniPC (:133-137), the AMED plugin (:157-163; ``amed_schedule``: the JSON file of its learned
+    tables, which are not part of this package) or eta = 0 DDIM on the learned solver's grid (baselines.py)."""
     import consolver_amd
     sd15 = dict(beta_start=0.00085, beta_end=0.012, beta_schedule="scaled_linear")
     if solver == "consistencysolver":
@@ -76,19 +77,19 @@ def make_scheduler(solver, order_dim=4, scaler_dim=0, use_conv=False, num_action
                                           factor_net_kwargs=dict(embedding_dim=32, hidden_dim=256, num_actions=num_actions), **sd15)
     if solver == "multistep-dpmsolver":
         return consolver_amd.DPMSolverMultistepScheduler(**consolver_amd.SD15_MULTISTEP_DPM_KWARGS)
+    if solver == "unipc":
+        return consolver_amd.UniPCMultistepScheduler(**consolver_amd.SD15_UNIPC_KWARGS)
+    if solver == "amed":
+        if not amed_schedule:
+            raise ValueError("solver 'amed' needs amed_schedule: a JSON file {\"<n>\": {\"amed\": [...], \"grad_scale\": [...], \"time_scale\": [...]}}")
+        return consolver_amd.AMEDSolverScheduler(**consolver_amd.SD15_AMED_KWARGS).load_schedules(amed_schedule)
     if solver == "ddim":
         from .baselines import DDIMBaselineScheduler
         return DDIMBaselineScheduler(timestep_spacing="trailing", **sd15)
     raise ValueError(f"unknown solver {solver!r}; expected one of {SOLVERS}")
 
 
-def main(argv=None, *, unet=None, vae=None):
-    """``unet`` / ``vae``: already loaded HIP handles to run on instead of building them from the arguments."""
-    from .engine import SDSamplingEngine
-    from .synth import synthetic_prompt_embeds, synthetic_unet_state_dict, synthetic_vae_state_dict
-    from .text_encoder import load_prompt_cache
-    from .unet import HipUNet2DConditionModel
-    from .vae import HipAutoencoderKL
+def parse_args(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--out", required=True)
     ap.add_argument("--prompt-cache")
@@ -104,12 +105,26 @@ def main(argv=None, *, unet=None, vae=None):
     ap.add_argument("--use_conv", "--use-conv", dest="use_conv", action="store_true",
                     help="gen_ppo.py:399: the policy also sees the cosine-similarity features of the eps history (factor_net_ppo.py:72-73,146-149)")
     ap.add_argument("--solver", default="consistencysolver", choices=SOLVERS,
-                    help="gen_ppo.load_pipeline(type=...): the learned solver (default), the Multistep-DPM-Solver baseline or DDIM; the baselines have no policy")
+                    help="gen_ppo.load_pipeline(type=...): the learned solver (default), the Multistep-DPM-Solver, UniPC or AMED baseline, or DDIM; the baselines have no policy")
+    ap.add_argument("--amed-schedule", help="--solver amed: JSON file of the AMED tables {\"<steps>\": {\"amed\": [...], \"grad_scale\": [...], \"time_scale\": [...]}}")
     ap.add_argument("--residual", default="f16x2", choices=["f16", "f16x2", "residual_fp32"],
                     help="residual-stream storage of the UNet executor (include/consolver_hip.h): f16x2 meets the 1e-3 latent gate, f16 is ~8 %% faster")
     args = ap.parse_args(argv)
     if args.solver != "consistencysolver" and (args.policy or args.use_conv):
         ap.error(f"--policy / --use_conv belong to the learned solver; --solver {args.solver} has no policy")
+    if (args.solver == "amed") != bool(args.amed_schedule):
+        ap.error("--amed-schedule FILE.json goes with --solver amed, and only with it")
+    return args
+
+
+def main(argv=None, *, unet=None, vae=None):
+    """``unet`` / ``vae``: already loaded HIP handles to run on instead of building them from the arguments."""
+    from .engine import SDSamplingEngine
+    from .synth import synthetic_prompt_embeds, synthetic_unet_state_dict, synthetic_vae_state_dict
+    from .text_encoder import load_prompt_cache
+    from .unet import HipUNet2DConditionModel
+    from .vae import HipAutoencoderKL
+    args = parse_args(argv)
     rank, world, local, dist = launch.init_distributed()
     torch.cuda.set_device(local)
     dev = torch.device("cuda", local)
@@ -127,7 +142,7 @@ def main(argv=None, *, unet=None, vae=None):
             unet.load_state_dict(_load_sd(args.unet))
             vae.load_state_dict(_load_sd(args.vae))
         prompts, pe, ne = load_prompt_cache(args.prompt_cache)
-    sch = make_scheduler(args.solver, args.order_dim, args.scaler_dim, args.use_conv, args.num_actions)
+    sch = make_scheduler(args.solver, args.order_dim, args.scaler_dim, args.use_conv, args.num_actions, args.amed_schedule)
     if sch.factor_net is not None:
         if args.policy:
             sch.factor_net.load_state_dict(torch.load(args.policy, map_location="cpu"))

@@ -31,43 +31,12 @@ SD15_MULTISTEP_DPM_KWARGS = dict(beta_start=0.00085, beta_end=0.012, beta_schedu
                                  algorithm_type="dpmsolver", final_sigmas_type="sigma_min")
 
 
-class DPMSolverMultistepScheduler(SchedulerMixin, ConfigMixin):
-    _compatibles = list(KARRAS_COMPATIBLES)
-    order = 1
-    prev_sample_dtype = None      # as HistoryMixin.prev_sample_dtype: torch.float32 promotes a 16-bit sample
-    factor_net = None             # no policy (SDSamplingEngine probes it)
+class SigmaGridMixin:
+    """what the sigma-parametrised multistep schedulers (this module, scheduling_unipc.py, scheduling_amed.py) share: the beta tables, the
+    timestep / sigma grid of diffusers 0.26.3's ``set_timesteps``, the step counter and the protocol stubs.  The class needs ``config`` with
+    ``num_train_timesteps``, ``timestep_spacing``, ``steps_offset`` and ``final_sigmas_type``."""
 
-    @register_to_config
-    def __init__(self, num_train_timesteps=1000, beta_start=0.0001, beta_end=0.02, beta_schedule="linear", trained_betas=None,
-                 solver_order=2, prediction_type="epsilon", thresholding=False, dynamic_thresholding_ratio=0.995, sample_max_value=1.0,
-                 algorithm_type="dpmsolver++", solver_type="midpoint", lower_order_final=True, euler_at_final=False,
-                 use_karras_sigmas=False, use_lu_lambdas=False, use_exponential_sigmas=False, final_sigmas_type="zero",
-                 lambda_min_clipped=-float("inf"), variance_type=None, timestep_spacing="linspace", steps_offset=0):
-        if solver_order not in (1, 2):
-            raise NotImplementedError(f"solver_order={solver_order}: orders 1 and 2 are implemented")
-        if thresholding:
-            raise NotImplementedError("thresholding is not implemented (a per-sample quantile, not a linear update)")
-        if use_karras_sigmas or use_lu_lambdas or use_exponential_sigmas:
-            raise NotImplementedError("the Karras / Lu / exponential sigma options are not implemented")
-        if algorithm_type in ("sde-dpmsolver", "sde-dpmsolver++"):
-            raise NotImplementedError(f"algorithm_type={algorithm_type!r}: the SDE variants are not implemented")
-        if algorithm_type not in ("dpmsolver", "dpmsolver++"):
-            raise NotImplementedError(f"{algorithm_type} is not implemented for {self.__class__}")
-        if variance_type is not None:
-            raise NotImplementedError("variance_type (learned-variance model outputs) is not implemented")
-        if lambda_min_clipped != -float("inf"):
-            raise NotImplementedError("lambda_min_clipped is not implemented")
-        if solver_type not in ("midpoint", "heun"):
-            raise NotImplementedError(f"{solver_type} is not implemented for {self.__class__}")
-        if prediction_type not in ("epsilon", "v_prediction"):
-            raise ValueError(f"prediction_type given as {prediction_type} must be one of `epsilon` or `v_prediction`")
-        if final_sigmas_type not in ("zero", "sigma_min"):
-            raise ValueError(f"`final_sigmas_type` must be one of 'zero', or 'sigma_min', but got {final_sigmas_type}")
-        if algorithm_type == "dpmsolver" and final_sigmas_type == "zero":
-            raise ValueError(f"`final_sigmas_type` {final_sigmas_type} is not supported for `algorithm_type` {algorithm_type}. "
-                             "Please choose `sigma_min` instead.")
-        if timestep_spacing not in ("linspace", "leading", "trailing"):
-            raise ValueError(f"{timestep_spacing} is not supported. Please make sure to choose one of 'linspace', 'leading' or 'trailing'.")
+    def _init_tables(self, beta_schedule, beta_start, beta_end, num_train_timesteps, trained_betas):
         self._betas = tables.make_betas(beta_schedule, beta_start, beta_end, num_train_timesteps, trained_betas)
         self._ac = tables.alphas_cumprod(self._betas)
         self.betas = torch.from_numpy(self._betas)
@@ -81,7 +50,7 @@ class DPMSolverMultistepScheduler(SchedulerMixin, ConfigMixin):
         self._sigmas = None
         self._step_index = None
         self._lower_order_nums = 0
-        self._m = []                                  # converted model outputs, newest first, at most solver_order long
+        self._m = []                                  # converted model outputs, newest first
         self._grid_key = None
 
     # ------------------------------------------------------------------ protocol
@@ -98,7 +67,8 @@ class DPMSolverMultistepScheduler(SchedulerMixin, ConfigMixin):
     def verify_timesteps(self):
         """nothing to verify: after the first step the grid position is a host counter (as in diffusers)."""
 
-    def set_timesteps(self, num_inference_steps, device=None):
+    def _set_grid(self, num_inference_steps, device=None):
+        """the timestep grid of ``timestep_spacing`` and its sigmas (interpolated, plus the final sigma); resets the step counter and the history"""
         cfg = self.config
         T, n = cfg.num_train_timesteps, int(num_inference_steps)
         if n < 1 or n > T:
@@ -141,7 +111,6 @@ class DPMSolverMultistepScheduler(SchedulerMixin, ConfigMixin):
             raise ValueError(f"timestep {int(timestep)} is not on the grid of set_timesteps({self.num_inference_steps})")
         return int(idx[1 if len(idx) > 1 else 0])
 
-    # ------------------------------------------------------------------ host scalars
     @staticmethod
     def _alpha_sigma_lambda(sigma):
         sigma = np.float64(sigma)
@@ -151,6 +120,50 @@ class DPMSolverMultistepScheduler(SchedulerMixin, ConfigMixin):
             lam = np.log(alpha) - np.log(sh)
         return alpha, sh, lam
 
+
+class DPMSolverMultistepScheduler(SigmaGridMixin, SchedulerMixin, ConfigMixin):
+    _compatibles = list(KARRAS_COMPATIBLES)
+    order = 1
+    prev_sample_dtype = None      # as HistoryMixin.prev_sample_dtype: torch.float32 promotes a 16-bit sample
+    factor_net = None             # no policy (SDSamplingEngine probes it)
+
+    @register_to_config
+    def __init__(self, num_train_timesteps=1000, beta_start=0.0001, beta_end=0.02, beta_schedule="linear", trained_betas=None,
+                 solver_order=2, prediction_type="epsilon", thresholding=False, dynamic_thresholding_ratio=0.995, sample_max_value=1.0,
+                 algorithm_type="dpmsolver++", solver_type="midpoint", lower_order_final=True, euler_at_final=False,
+                 use_karras_sigmas=False, use_lu_lambdas=False, use_exponential_sigmas=False, final_sigmas_type="zero",
+                 lambda_min_clipped=-float("inf"), variance_type=None, timestep_spacing="linspace", steps_offset=0):
+        if solver_order not in (1, 2):
+            raise NotImplementedError(f"solver_order={solver_order}: orders 1 and 2 are implemented")
+        if thresholding:
+            raise NotImplementedError("thresholding is not implemented (a per-sample quantile, not a linear update)")
+        if use_karras_sigmas or use_lu_lambdas or use_exponential_sigmas:
+            raise NotImplementedError("the Karras / Lu / exponential sigma options are not implemented")
+        if algorithm_type in ("sde-dpmsolver", "sde-dpmsolver++"):
+            raise NotImplementedError(f"algorithm_type={algorithm_type!r}: the SDE variants are not implemented")
+        if algorithm_type not in ("dpmsolver", "dpmsolver++"):
+            raise NotImplementedError(f"{algorithm_type} is not implemented for {self.__class__}")
+        if variance_type is not None:
+            raise NotImplementedError("variance_type (learned-variance model outputs) is not implemented")
+        if lambda_min_clipped != -float("inf"):
+            raise NotImplementedError("lambda_min_clipped is not implemented")
+        if solver_type not in ("midpoint", "heun"):
+            raise NotImplementedError(f"{solver_type} is not implemented for {self.__class__}")
+        if prediction_type not in ("epsilon", "v_prediction"):
+            raise ValueError(f"prediction_type given as {prediction_type} must be one of `epsilon` or `v_prediction`")
+        if final_sigmas_type not in ("zero", "sigma_min"):
+            raise ValueError(f"`final_sigmas_type` must be one of 'zero', or 'sigma_min', but got {final_sigmas_type}")
+        if algorithm_type == "dpmsolver" and final_sigmas_type == "zero":
+            raise ValueError(f"`final_sigmas_type` {final_sigmas_type} is not supported for `algorithm_type` {algorithm_type}. "
+                             "Please choose `sigma_min` instead.")
+        if timestep_spacing not in ("linspace", "leading", "trailing"):
+            raise ValueError(f"{timestep_spacing} is not supported. Please make sure to choose one of 'linspace', 'leading' or 'trailing'.")
+        self._init_tables(beta_schedule, beta_start, beta_end, num_train_timesteps, trained_betas)
+
+    def set_timesteps(self, num_inference_steps, device=None):
+        self._set_grid(num_inference_steps, device)
+
+    # ------------------------------------------------------------------ host scalars
     def _first_order(self, i, lower_order_nums):
         cfg, n = self.config, self.num_inference_steps
         final = (i == n - 1) and (cfg.euler_at_final or (cfg.lower_order_final and n < 15) or cfg.final_sigmas_type == "zero")

@@ -179,6 +179,44 @@ typedef struct CsDpmStepArgs {
 int cs_dpm_multistep_step(const CsDpmStepArgs* args, void* stream);
 
 /* ------------------------------------------------------------------------
+ * UniPC update (bh1 / bh2, orders 1 and 2, x0 prediction; consolver_amd/scheduling_unipc.py).
+ * One step is the corrector of the PREVIOUS update, which needs this step's model output, and this
+ * step's predictor from the corrected sample -- one pass, the variant in nine host scalars:
+ *     eps    = eps_uncond ? round_io(u + guidance * (c - u)) : c
+ *     m_new  = round_io(conv_x * x + conv_e * eps)     the converted output at the PREDICTED sample x, written to m_out
+ *     x_c    = use_corr ? round_out(a_x * x_last + a_0 * m_prev0 + a_1 * m_prev1 + a_n * m_new) : x
+ *     x_next = p_x * x_c + p_0 * m_new + p_1 * m_prev0
+ * (a term whose coefficient is zero is not read).  Pointer and dtype fields mean what they mean in
+ * CsDpmStepArgs; x_last and x_last_out have the dtype of x, which is out_dtype.  All [B, elems] tensors are
+ * contiguous and 16-byte aligned.
+ * Aliasing: x_last_out may be x_last (each element is read, then written, by the same thread); x_out
+ * aliases none of the inputs; m_out aliases none of m_prev0, m_prev1.
+ * ---------------------------------------------------------------------- */
+typedef struct CsUnipcStepArgs {
+    const void* x;            /* [B, elems] this step's sample: the previous predictor's output (io_dtype, or fp32 when x_is_f32) */
+    const void* eps_text;     /* [B, elems] model output (conditional branch)       */
+    const void* eps_uncond;   /* [B, elems] unconditional branch, or NULL (no CFG)  */
+    float guidance;
+    const void* x_last;       /* [B, elems] the previous step's corrected sample; may be NULL iff use_corr == 0 */
+    const void* m_prev0;      /* [B, elems] m_new of step i - 1; may be NULL iff a_0 == 0 (or use_corr == 0) and p_1 == 0 */
+    const void* m_prev1;      /* [B, elems] m_new of step i - 2; may be NULL iff a_1 == 0 (or use_corr == 0) */
+    int B;
+    int64_t elems;            /* elements per sample                                */
+    int io_dtype;             /* dtype of eps_*, m_prev*, m_out (and of x, x_last unless x_is_f32) */
+    int out_dtype;            /* dtype of x_out and x_last_out: the sample's        */
+    int x_is_f32;             /* the sample is fp32 beside 16-bit model outputs (an error with fp32 io) */
+    int use_corr;
+    void* x_out;              /* [B, elems] x_next                                  */
+    void* m_out;              /* [B, elems] m_new (required: the conversion is never the identity) */
+    void* x_last_out;         /* [B, elems] x_c, the next step's x_last; NULL: not stored */
+    void* x_out_lp;           /* optional 16-bit copy of an fp32 x_next, as CsStepArgs::x_out_lp */
+    int lp_dtype;
+    float conv_x, conv_e, a_x, a_0, a_1, a_n, p_x, p_0, p_1;
+} CsUnipcStepArgs;
+
+int cs_unipc_step(const CsUnipcStepArgs* args, void* stream);
+
+/* ------------------------------------------------------------------------
  * Flow-matching baseline update (consolver_amd/scheduling_fm.py; edit_ppo/scheduler_fm.py:405-482).
  * Every branch of the Euler, Heun, dpm-solver and multistep steps is
  *     w  = v1 ? round_io(v1 + v2) : v2

@@ -7,6 +7,10 @@ copy of the result in the same pass -- next to cs_lms_ddim_step with a history o
 device copy (read + write bytes, what bench.py --full reports as dtod_copy_1gib_tbps) as the rate both are a share of.  The two kernels are timed
 as hipGraph replays of 500 captured launches (a Python launch loop measures the host's enqueue rate at this size), alternating, median of 5.
 
+``--unipc``: the fused UniPC corrector + predictor (cs_unipc_step) in the engine's form -- fp32 state, fp16 model outputs, CFG, second order, x_last
+updated in place, the fp16 copy of the result in the same pass: 16 bytes read and 12 written per element -- next to cs_dpm_multistep_step (18 bytes per
+element) on the same tensors and the 1 GiB device copy, timed in the same run by the same captured-graph method as ``--dpm``.
+
 ``--fm``: the flow-matching baselines' update (cs_fm_general_step; Euler form x + dt v, Heun form x + c (v1 + v2)) at FLUX's packed latent size
 [1, 4096, 64] bf16 next to cs_lms_euler_step with a history of one on the same tensors, timed the same way in the same run as the 1 GiB copy.  At
 0.5 MB per tensor the kernels are launch-latency-bound: the figure is microseconds per launch, not a share of a roofline."""
@@ -104,6 +108,41 @@ def run_dpm(B=32, elems=4 * 64 * 64):
     return rows
 
 
+def run_unipc(B=32, elems=4 * 64 * 64):
+    h = lambda: torch.randn(B, elems, device=dev).half()
+    x, xl, out = torch.randn(B, elems, device=dev), torch.randn(B, elems, device=dev), torch.empty(B, elems, device=dev)
+    eu, ec, m0, m1, mo, lp = h(), h(), h(), h(), h(), h()
+    u = L.CsUnipcStepArgs()
+    u.x, u.eps_text, u.eps_uncond, u.guidance = x.data_ptr(), ec.data_ptr(), eu.data_ptr(), 3.0
+    u.x_last, u.m_prev0, u.m_prev1, u.use_corr = xl.data_ptr(), m0.data_ptr(), m1.data_ptr(), 1
+    u.B, u.elems, u.io_dtype, u.out_dtype, u.x_is_f32 = B, elems, L.CS_F16, L.CS_F32, 1
+    u.x_out, u.m_out, u.x_last_out, u.x_out_lp, u.lp_dtype = out.data_ptr(), mo.data_ptr(), xl.data_ptr(), lp.data_ptr(), L.CS_F16
+    # (a_x + a_0 + a_1 + a_n = 1 and |a_x| < 1: x_last, rewritten in place 500 times per replay, stays bounded)
+    u.conv_x, u.conv_e, u.a_x, u.a_0, u.a_1, u.a_n, u.p_x, u.p_0, u.p_1 = 1.05, -0.31, 0.8, 0.05, -0.02, 0.17, 0.8, 0.27, -0.07
+    d = L.CsDpmStepArgs()
+    d.x, d.eps_text, d.eps_uncond, d.guidance, d.m_prev = x.data_ptr(), ec.data_ptr(), eu.data_ptr(), 3.0, m0.data_ptr()
+    d.B, d.elems, d.io_dtype, d.out_dtype, d.x_is_f32 = B, elems, L.CS_F16, L.CS_F32, 1
+    d.x_out, d.m_out, d.x_out_lp, d.lp_dtype = out.data_ptr(), mo.data_ptr(), lp.data_ptr(), L.CS_F16
+    d.conv_x, d.conv_e, d.cx, d.c0, d.c1 = 1.05, -0.31, 0.8, 0.27, -0.07
+    src = torch.randn(1 << 28, device=dev); dst = torch.empty_like(src)
+    copy_gbps = 2.0 * (1 << 30) / time_us(lambda: dst.copy_(src), 20) / 1e3
+    del src, dst
+    # bytes per element: x, x_last, eps_u, eps_c, m_prev0, m_prev1 | x', x_c, m_new, fp16 copy of x'   and   x, eps_u, eps_c, m_prev | x', m0, fp16 copy
+    kernels = (("cs_unipc_step", lib.cs_unipc_step, u, 28), ("cs_dpm_multistep_step", lib.cs_dpm_multistep_step, d, 18))
+    times = {name: [] for name, _, _, _ in kernels}
+    for _ in range(5):                                        # alternate the two kernels; report the median window
+        for name, fn, args, _ in kernels:
+            times[name].append(graph_us(lambda: L.check(fn(C.byref(args), L.stream_ptr(dev)))))
+    rows = []
+    for name, _, _, bpe in kernels:
+        us, nbytes = sorted(times[name])[2], bpe * B * elems
+        rows.append(dict(kernel=name, B=B, elems=elems, state="float32", outputs="float16", cfg=True, order=2, bytes_per_elem=bpe, us=round(us, 2),
+                         us_min_max=[round(min(times[name]), 2), round(max(times[name]), 2)], MB=round(nbytes / 1e6, 2),
+                         GBps=round(nbytes / us / 1e3, 1), copy_1gib_GBps=round(copy_gbps, 1), share_of_copy_rate=round(nbytes / us / 1e3 / copy_gbps, 3)))
+    rows.append(dict(unipc_over_dpm_time=round(rows[0]["us"] / rows[1]["us"], 3), bytes_ratio=round(28 / 18, 3)))
+    return rows
+
+
 def run_fm(B=1, elems=4096 * 64):
     t = lambda: torch.randn(B, elems, device=dev).bfloat16()
     x, v, v1, out = t(), t(), t(), t()
@@ -137,6 +176,10 @@ def run_fm(B=1, elems=4096 * 64):
 
 if "--fm" in sys.argv:
     for r in run_fm(): print(json.dumps(r))
+    sys.exit(0)
+
+if "--unipc" in sys.argv:
+    for r in run_unipc(): print(json.dumps(r))
     sys.exit(0)
 
 if "--dpm" in sys.argv:
