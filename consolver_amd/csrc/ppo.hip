@@ -12,14 +12,15 @@ namespace {
 constexpr int PSNR_SPLITS = 64;
 
 // partial[b][s] = sum over the s-th slice of (pred - target)^2
+// target_stride: elements between the target rows; 0 = one target row shared by every pred row (cs_image_psnr_bcast)
 template <typename T>
-__global__ __launch_bounds__(256) void sqdiff_partial_kernel(const T* __restrict__ pred, const T* __restrict__ target, long n,
+__global__ __launch_bounds__(256) void sqdiff_partial_kernel(const T* __restrict__ pred, const T* __restrict__ target, long n, long target_stride,
                                                              float* __restrict__ partial) {
     const int b = blockIdx.y, s = blockIdx.x, S = gridDim.x;
     const long nv = n >> 3;                                   // 8-element vectors
     const long per = (nv + S - 1) / S, v0 = s * per, v1 = v0 + per < nv ? v0 + per : nv;
     const T* p = pred + (size_t)b * n;
-    const T* t = target + (size_t)b * n;
+    const T* t = target + (size_t)b * target_stride;
     float acc = 0.f;
     for (long v = v0 + threadIdx.x; v < v1; v += 256) {
         float a[8], c[8];
@@ -330,6 +331,31 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const
     p[i] = pi - (lr / bc1) * (mi / denom);
 }
 
+// dst[r][:] = src[index[r]][:] over rows of n units of type V (u32x4 = 16 bytes on the vector path; u32 / u16 = one element on the scalar path).
+// grid (chunks, rows), both strided.  An index outside [0, rows_src) never forms an address: that row of dst is filled with `nan` (the NaN bit pattern of the
+// element type, replicated over V).
+template <typename V>
+__global__ __launch_bounds__(256) void gather_rows_kernel(const V* __restrict__ src, int rows_src, const int64_t* __restrict__ index, int rows_out, int64_t n,
+                                                          V nan, V* __restrict__ dst) {
+    for (int r = blockIdx.y; r < rows_out; r += gridDim.y) {
+        const int64_t i = index[r];
+        const bool ok = i >= 0 && i < (int64_t)rows_src;
+        const V* s = src + (ok ? i : 0) * n;
+        V* d = dst + (int64_t)r * n;
+        for (int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; v < n; v += (int64_t)gridDim.x * blockDim.x) d[v] = ok ? s[v] : nan;
+    }
+}
+
+template <typename V>
+void launch_gather_rows(const void* src, int rows_src, const int64_t* index, int rows_out, int64_t n, V nan, void* dst, hipStream_t s) {
+    int gy = rows_out < 65535 ? rows_out : 65535;
+    int64_t gx = (n + 255) / 256;
+    // memory-bound: the capped grid of solver.hip's launch_step (~8 blocks per CU overall), the rest grid-strided
+    int64_t cap = (2048 + gy - 1) / gy; if (cap < 1) cap = 1;
+    if (gx > cap) gx = cap; if (gx < 1) gx = 1;
+    hipLaunchKernelGGL(gather_rows_kernel<V>, dim3((unsigned)gx, (unsigned)gy), dim3(256), 0, s, (const V*)src, rows_src, index, rows_out, n, nan, (V*)dst);
+}
+
 }  // namespace
 
 extern "C" {
@@ -338,6 +364,11 @@ size_t cs_psnr_workspace_bytes(int batch) { return (size_t)(batch > 0 ? batch : 
 
 int cs_image_psnr(const void* pred, const void* target, int B, int64_t elems, int dtype, float clamp_hi, float* out, void* workspace,
                   size_t workspace_bytes, void* stream) {
+    return cs_image_psnr_bcast(pred, target, B, elems, dtype, clamp_hi, out, workspace, workspace_bytes, stream, elems);
+}
+
+int cs_image_psnr_bcast(const void* pred, const void* target, int B, int64_t elems, int dtype, float clamp_hi, float* out, void* workspace,
+                        size_t workspace_bytes, void* stream, int64_t target_stride) {
     if (B < 0 || elems < 0) CS_FAIL(CS_E_ARG, "negative size");
     if (B == 0) return CS_OK;
     if (elems == 0) CS_FAIL(CS_E_SHAPE, "psnr of empty images");
@@ -346,11 +377,39 @@ int cs_image_psnr(const void* pred, const void* target, int B, int64_t elems, in
     if (dtype != CS_F16 && dtype != CS_F32) CS_FAIL(CS_E_UNSUPPORTED, "psnr: dtype must be f16 or f32");
     if (((uintptr_t)pred | (uintptr_t)target) & 15 || (elems * (dtype == CS_F16 ? 2 : 4)) % 16)
         CS_FAIL(CS_E_ARG, "psnr: images must be 16-byte aligned with a 16-byte multiple of bytes per image");
+    if (target_stride != 0 && (target_stride < elems || (target_stride * (dtype == CS_F16 ? 2 : 4)) % 16))
+        CS_FAIL(CS_E_ARG, "psnr: target_stride must be 0 (one shared target) or at least elems, a 16-byte multiple of bytes");
     hipStream_t s = (hipStream_t)stream;
     float* partial = (float*)workspace;
-    if (dtype == CS_F16) hipLaunchKernelGGL(sqdiff_partial_kernel<f16>, dim3(PSNR_SPLITS, B), dim3(256), 0, s, (const f16*)pred, (const f16*)target, (long)elems, partial);
-    else hipLaunchKernelGGL(sqdiff_partial_kernel<float>, dim3(PSNR_SPLITS, B), dim3(256), 0, s, (const float*)pred, (const float*)target, (long)elems, partial);
+    if (dtype == CS_F16)
+        hipLaunchKernelGGL(sqdiff_partial_kernel<f16>, dim3(PSNR_SPLITS, B), dim3(256), 0, s, (const f16*)pred, (const f16*)target, (long)elems, (long)target_stride, partial);
+    else
+        hipLaunchKernelGGL(sqdiff_partial_kernel<float>, dim3(PSNR_SPLITS, B), dim3(256), 0, s, (const float*)pred, (const float*)target, (long)elems, (long)target_stride,
+                           partial);
     hipLaunchKernelGGL(psnr_finalize_kernel, dim3(B), dim3(64), 0, s, partial, PSNR_SPLITS, (long)elems, clamp_hi, out);
+    CS_CHECK_LAUNCH();
+    return CS_OK;
+}
+
+int cs_gather_rows(const void* src, int rows_src, const int64_t* index, int rows_out, int64_t elems, int dtype, void* dst, void* stream) {
+    if (rows_src < 0 || rows_out < 0 || elems < 0) CS_FAIL(CS_E_ARG, "gather_rows: negative size");
+    if (dtype != CS_F32 && dtype != CS_F16 && dtype != CS_BF16) CS_FAIL(CS_E_DTYPE, "gather_rows: dtype must be f32, f16 or bf16, got %d", dtype);
+    if (rows_out == 0 || elems == 0) return CS_OK;
+    if (!src || !index || !dst) CS_FAIL(CS_E_ARG, "gather_rows: null pointer");
+    const int64_t es = dtype == CS_F32 ? 4 : 2, row_bytes = elems * es;
+    const uintptr_t s0 = (uintptr_t)src, s1 = s0 + (uintptr_t)rows_src * (uintptr_t)row_bytes, d0 = (uintptr_t)dst, d1 = d0 + (uintptr_t)rows_out * (uintptr_t)row_bytes;
+    if (s0 < d1 && d0 < s1) CS_FAIL(CS_E_ARG, "gather_rows: dst overlaps src");
+    if (((s0 | d0) & (uintptr_t)(es - 1)) != 0) CS_FAIL(CS_E_ARG, "gather_rows: pointers must be aligned to the element size");
+    const unsigned nan32 = dtype == CS_F32 ? 0x7FC00000u : dtype == CS_F16 ? 0x7E007E00u : 0x7FC07FC0u;
+    hipStream_t s = (hipStream_t)stream;
+    if (row_bytes % 16 == 0 && ((s0 | d0) & 15) == 0) {
+        const u32x4 nan = {nan32, nan32, nan32, nan32};
+        launch_gather_rows<u32x4>(src, rows_src, index, rows_out, row_bytes / 16, nan, dst, s);
+    } else if (es == 4) {
+        launch_gather_rows<unsigned>(src, rows_src, index, rows_out, elems, nan32, dst, s);
+    } else {
+        launch_gather_rows<u16>(src, rows_src, index, rows_out, elems, (u16)(nan32 & 0xFFFFu), dst, s);
+    }
     CS_CHECK_LAUNCH();
     return CS_OK;
 }

@@ -30,9 +30,11 @@ _DT = {torch.float32: 0, torch.float16: 1}
 
 
 def _psnr(pred, target, clamp_hi):
+    """``target``: one row per row of ``pred``, or ONE row shared by all of them (cs_image_psnr_bcast with stride 0)."""
     L.require_cuda(pred, "model_pred")
     L.require_cuda(target, "target")
-    if pred.shape != target.shape:
+    shared = target.shape[0] == 1 and pred.shape[0] != 1 and pred.shape[1:] == target.shape[1:]
+    if pred.shape != target.shape and not shared:
         raise ValueError(f"shape mismatch {tuple(pred.shape)} vs {tuple(target.shape)} (the bilinear-resize branch, "
                          "reward_model.py:492-494, is not on the hot path)")
     if pred.dtype != target.dtype:
@@ -47,18 +49,23 @@ def _psnr(pred, target, clamp_hi):
     elems = pred[0].numel()
     lib = L.lib()
     ws = torch.empty(int(lib.cs_psnr_workspace_bytes(B)), dtype=torch.uint8, device=pred.device)
+    if shared:
+        L.check(lib.cs_image_psnr_bcast(L.ptr(pred), L.ptr(target), B, elems, _DT[pred.dtype], float(clamp_hi), L.ptr(out), L.ptr(ws), ws.numel(),
+                                        L.stream_ptr(pred.device), 0))
+        return out
     L.check(lib.cs_image_psnr(L.ptr(pred), L.ptr(target), B, elems, _DT[pred.dtype], float(clamp_hi), L.ptr(out), L.ptr(ws), ws.numel(),
                               L.stream_ptr(pred.device)))
     return out
 
 
 def calculate_image_psnr_reward(reward_model_processor, model_pred, target, device=None):
-    """edit_ppo/reward_model.py:484-509: [B,3,H,W] in [0,1] x2 -> PSNR [B,1] clamped to [0, 100]."""
+    """edit_ppo/reward_model.py:484-509: [B,3,H,W] in [0,1] x2 -> PSNR [B,1] clamped to [0, 100].  ``target`` may be [1,3,H,W]: one image shared
+    by every prediction, read in place."""
     return _psnr(model_pred, target, 100.0)
 
 
 def depth_psnr_tail(pred_depth, target_depth):
-    """edit_ppo/reward_model.py:404-422: PSNR of normalised depth maps [B,H,W], clamp(min=0) only -> [B,1]."""
+    """edit_ppo/reward_model.py:404-422: PSNR of normalised depth maps [B,H,W] ([1,H,W] target: shared), clamp(min=0) only -> [B,1]."""
     return _psnr(pred_depth, target_depth, 0.0)
 
 
@@ -106,20 +113,22 @@ def ppo_loss(curr_probs, old_probs, entropy, advantages, clip_range=0.2, entropy
 
 def collect_rollout(text_encoder, noise_scheduler, unet, vae, noise, text, tokenizer, target_latents, cfg=3.0, num_inference_steps=8,
                     reward_type="image_psnr", reward_model=None, reward_model_processor=None, decode_batch_size=8,
-                    prompt_embeds=None, negative_prompt_embeds=None, identical_inputs=False):
+                    prompt_embeds=None, negative_prompt_embeds=None, identical_inputs=False, group_rows=False, share_target=False):
     """train_ppo.py:352-403 for one batch: rollout, decode pred and teacher latents, reward, advantages, and the
-    records flattened to [B (n-1), ...].  Returns a dict(conds, actions, probs, masks, advantages, rewards, model_pred).
+    records flattened to [B (n-1), ...].  Returns a dict(conds, actions, probs, masks, advantages, rewards, model_pred, forward_rows).
     ``identical_inputs=True``: the B rows are copies of one (prompt, noise, teacher latent) sample (``repeat_random_sample``):
     the rollout shares the denoiser calls whose inputs cannot differ yet, and the teacher image is decoded once (and, for the "dino"
-    and "clip" rewards, encoded once)."""
+    and "clip" rewards, encoded once).  ``share_target=True`` (with ``identical_inputs``): every reward type gets the one teacher image as
+    [1,3,H,W] -- the reward network sees it once, not once per row.  ``group_rows=True``: ``denoise_diffusion(group_rows=True)``."""
     n = num_inference_steps
+    stats = {}
     model_pred, conds, probs, actions, masks, _ = denoise_diffusion(
         text_encoder, noise_scheduler, unet, noise, text, tokenizer, cfg=float(cfg), num_inference_steps=n,
-        prompt_embeds=prompt_embeds, negative_prompt_embeds=negative_prompt_embeds, identical_inputs=identical_inputs)
+        prompt_embeds=prompt_embeds, negative_prompt_embeds=negative_prompt_embeds, identical_inputs=identical_inputs, group_rows=group_rows, stats=stats)
     model_pred_decoded = decode_latents(vae, model_pred, batch_size=decode_batch_size)
     if identical_inputs and target_latents.shape[0] > 1:
         target_decoded = decode_latents(vae, target_latents[:1], batch_size=1)
-        if reward_type not in ("dino", "clip"):               # calculate_dino_reward / calculate_clip_reward take one shared target as [1,3,H,W]
+        if reward_type not in ("dino", "clip") and not share_target:               # calculate_dino_reward / calculate_clip_reward take one shared target as [1,3,H,W]
             target_decoded = target_decoded.expand(target_latents.shape[0], -1, -1, -1).contiguous()
     else:
         target_decoded = decode_latents(vae, target_latents, batch_size=decode_batch_size)
@@ -129,7 +138,8 @@ def collect_rollout(text_encoder, noise_scheduler, unet, vae, noise, text, token
     conds = {k: flat(v) for k, v in conds.items()}
     actions, probs, masks = (t.reshape(B * (n - 1), -1) for t in (actions, probs, masks))
     advantages = compute_advantages(rewards, masks, n)
-    return dict(conds=conds, actions=actions, probs=probs, masks=masks, advantages=advantages, rewards=rewards, model_pred=model_pred)
+    return dict(conds=conds, actions=actions, probs=probs, masks=masks, advantages=advantages, rewards=rewards, model_pred=model_pred,
+                forward_rows=stats["forward_rows"])
 
 
 class PolicyTrainer:
@@ -212,6 +222,20 @@ class PolicyTrainer:
             o += n
         return loss, self._out[1].clone()
 
+    # -- optimiser state (not part of the reference's model.ckpt; the SD training driver keeps it next to it) ----
+    def state_dict(self):
+        """the Adam moments (packed, state-dict order of the parameters) and the step count, on the CPU"""
+        return {"exp_avg": self.exp_avg.detach().cpu().clone(), "exp_avg_sq": self.exp_avg_sq.detach().cpu().clone(), "step_count": int(self.step_count)}
+
+    def load_state_dict(self, state):
+        for k in ("exp_avg", "exp_avg_sq"):
+            if tuple(state[k].shape) != tuple(self.grads.shape):
+                raise ValueError(f"{k}: {tuple(state[k].shape)} values for a policy of {self.grads.numel()} parameters")
+        self.exp_avg.copy_(state["exp_avg"].to(self.exp_avg.device, torch.float32))
+        self.exp_avg_sq.copy_(state["exp_avg_sq"].to(self.exp_avg_sq.device, torch.float32))
+        self.step_count = int(state["step_count"])
+        return self
+
     # -- checkpoint format of the reference (train_ppo.py:174-186) ---------------------------------------------
     def save_checkpoint(self, output_dir, global_step):
         import os
@@ -231,11 +255,12 @@ class PolicyTrainer:
 
 def train_iteration(trainer, text_encoder, noise_scheduler, unet, vae, batch, tokenizer, cfg=3.0, num_inference_steps=None, ppo_epochs=4,
                     reward_type="image_psnr", dist=None, prompt_embeds=None, negative_prompt_embeds=None, rng=None, share_identical=True,
-                    reward_model=None, reward_model_processor=None):
+                    reward_model=None, reward_model_processor=None, group_rows=False, share_target=False):
     """One iteration of the training loop body (train_ppo.py:322-437): ``repeat_random_sample`` -> random step count in [2, 15]
     (:345) -> rollout, decode, reward, advantages (``collect_rollout``) -> ``ppo_epochs`` optimisation steps on the collected
-    batch.  ``batch`` = (text list, noise [B,4,64,64], teacher latents [B,4,64,64]) already on the GPU.
-    Returns dict(loss, norm, reward, num_inference_steps)."""
+    batch.  ``batch`` = (text list, noise [B,4,64,64], teacher latents [B,4,64,64]) already on the GPU.  ``group_rows`` / ``share_target``: those of
+    ``collect_rollout``; both build on ``share_identical``.
+    Returns dict(loss, norm, reward, num_inference_steps, forward_rows)."""
     import random
     from .ppo_data import repeat_random_sample
     rng = rng or random
@@ -249,8 +274,9 @@ def train_iteration(trainer, text_encoder, noise_scheduler, unet, vae, batch, to
     # the B rows are copies of one sample by construction (data_processing.py:65-83): share what cannot differ
     roll = collect_rollout(text_encoder, noise_scheduler, unet, vae, noise, text, tokenizer, tch, cfg=cfg, num_inference_steps=n,
                            reward_type=reward_type, reward_model=reward_model, reward_model_processor=reward_model_processor,
-                           prompt_embeds=prompt_embeds, negative_prompt_embeds=negative_prompt_embeds, identical_inputs=share_identical)
+                           prompt_embeds=prompt_embeds, negative_prompt_embeds=negative_prompt_embeds, identical_inputs=share_identical,
+                           group_rows=group_rows, share_target=share_target)
     loss = norm = None
     for _ in range(ppo_epochs):
         loss, norm = trainer.step(roll["conds"], roll["actions"], roll["probs"], roll["advantages"], dist=dist)
-    return dict(loss=loss, norm=norm, reward=roll["rewards"].mean(), num_inference_steps=n)
+    return dict(loss=loss, norm=norm, reward=roll["rewards"].mean(), num_inference_steps=n, forward_rows=roll["forward_rows"])

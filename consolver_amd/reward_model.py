@@ -633,9 +633,7 @@ def calculate_depth_reward(reward_model, reward_model_processor, model_pred, tar
         raise NotImplementedError("reward_type 'depth' needs a HipDepthAnythingModel (load_depth_reward(device, config)); the eager transformers path is "
                                   "not implemented")
     pred_maps, target_maps = _paired_image_pass(reward_model, reward_model_processor, model_pred, target, reward_model.normalized_depth)
-    if target_maps.shape[0] != pred_maps.shape[0]:
-        target_maps = target_maps.expand(pred_maps.shape[0], -1, -1)
-    from .ppo import depth_psnr_tail
+    from .ppo import depth_psnr_tail            # a one-row target map is read in place by every row (cs_image_psnr_bcast)
     return depth_psnr_tail(pred_maps, target_maps)
 
 

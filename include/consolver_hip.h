@@ -443,6 +443,16 @@ int cs_vae_encode(CsVae* v, const void* images, int batch, float out_scale, floa
 size_t cs_psnr_workspace_bytes(int batch);
 int cs_image_psnr(const void* pred, const void* target, int B, int64_t elems, int dtype, float clamp_hi,
                   float* out, void* workspace, size_t workspace_bytes, void* stream);
+/* cs_image_psnr with target row b at target + b * target_stride elements: target_stride = 0 is ONE target image shared by all B
+ * predictions (the trainer's B copies of one teacher image), target_stride = elems is cs_image_psnr.  The same two kernels. */
+int cs_image_psnr_bcast(const void* pred, const void* target, int B, int64_t elems, int dtype, float clamp_hi,
+                        float* out, void* workspace, size_t workspace_bytes, void* stream, int64_t target_stride);
+/* dst[r][:] = src[index[r]][:] for r < rows_out, rows of `elems` elements of dtype CS_F32 | CS_F16 | CS_BF16 (the grouped rollout: the
+ * representative latents of each group of equal rows, and a group's denoiser output handed to each of its rows).  16-byte vectors when
+ * elems * element size is a multiple of 16 and both pointers are 16-byte aligned, one element per lane otherwise.  dst must not overlap
+ * src (CS_E_ARG).  An index outside [0, rows_src) is never turned into an address: that row of dst is filled with NaN.
+ * rows_out == 0 or elems == 0: no-op.  Argument errors are negative codes before any launch. */
+int cs_gather_rows(const void* src, int rows_src, const int64_t* index, int rows_out, int64_t elems, int dtype, void* dst, void* stream);
 /* advantages[(b, j), a] = (r[b] - mean(r)) / (std_unbiased(r) + 1e-8) * 10 * masks[(b, j), a],
  * j over the recorded steps (n - 1) (train_ppo.py:376-390).  All fp32. */
 int cs_ppo_advantages(const float* rewards, int B, int recorded_steps, int A, const float* masks,
