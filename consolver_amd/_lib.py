@@ -142,6 +142,7 @@ SYMBOLS = {
     "cs_dpm_multistep_step": (C.c_int, [C.POINTER(CsDpmStepArgs), C.c_void_p]),
     "cs_unipc_step": (C.c_int, [C.POINTER(CsUnipcStepArgs), C.c_void_p]),
     "cs_fm_general_step": (C.c_int, [C.POINTER(CsFmStepArgs), C.c_void_p]),
+    "cs_true_cfg_combine": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_int, C.c_int64, C.c_void_p]),
     "cs_psnr_workspace_bytes": (C.c_size_t, [C.c_int]),
     "cs_image_psnr": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_size_t,
                                 C.c_void_p]),
@@ -221,6 +222,8 @@ SYMBOLS = {
     "cs_flux_get_output_dtype": (C.c_int, [C.c_void_p]),
     "cs_flux_forward_joint": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "cs_flux_forward_joint_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     # include/consolver_hip_ops.h
     "cs_op_gemm2_x2": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_long, C.c_int,
                                  C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),

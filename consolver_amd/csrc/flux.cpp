@@ -179,9 +179,13 @@ struct FRun {
 // (`noise_pred[:, :latents.size(1)]`, edit_ppo/denoise_diffusion.py:145).
 int flux_forward(CsFlux* f, bool dry, const void* hidden, int B, int I, const void* enc, int T, const float* pooled, const float* timestep,
                  const float* guidance, const float* rcos, const float* rsin, void* out, char* ws, size_t ws_bytes, hipStream_t s,
-                 const void* hidden2 = nullptr, int I2 = 0) {
+                 const void* hidden2 = nullptr, int I2 = 0, int lat_rows = 0) {
     const CsFluxConfig& c = f->cfg; const int D = f->D, S = T + I, H = c.num_heads, dh = c.head_dim;
     const int I1 = I - I2;                    // rows of `hidden` per sample = output rows per sample
+    // lat_rows (cs_flux_forward_joint_rows): `hidden` / `hidden2` hold lat_rows < B samples and sample b reads b % lat_rows -- the embedder's A row map with a
+    // zero segment stride walks the lat_rows * I1 (I2) source rows again for every group, so no other launch knows about it
+    const bool bcast = lat_rows > 0 && lat_rows < B;
+    const int as1 = bcast ? lat_rows * I1 : 0, as2 = bcast ? lat_rows * I2 : 0;
     f->arena.reset(dry ? (char*)256 : ws, ws_bytes, dry); f->dry_flops = 0;
     FRun Rn{f, s, dry}; Rn.dt = c.dtype;
     const size_t e = 2;
@@ -247,10 +251,10 @@ int flux_forward(CsFlux* f, bool dry, const void* hidden, int B, int I, const vo
     if (split) { ires = img; cres = ctx; }
     void* const ilo = split ? (void*)img_lo : nullptr; void* const clo = split ? (void*)ctx_lo : nullptr;
     if (I2 > 0)
-        Rn.gemm_pair(FRun::with_lo(FRun::gargs(f->x_emb, hidden, c.in_channels, B * I1, img, D, 0, 0, ires, nullptr, 0, 0, 0, 0, 0, I1, I, 0), ilo),
-                     FRun::with_lo(FRun::gargs(f->x_emb, hidden2, c.in_channels, B * I2, img, D, 0, 0, ires, nullptr, 0, 0, 0, 0, 0, I2, I, I1), ilo));
+        Rn.gemm_pair(FRun::with_lo(FRun::gargs(f->x_emb, hidden, c.in_channels, B * I1, img, D, 0, 0, ires, nullptr, 0, 0, as1, 0, 0, I1, I, 0), ilo),
+                     FRun::with_lo(FRun::gargs(f->x_emb, hidden2, c.in_channels, B * I2, img, D, 0, 0, ires, nullptr, 0, 0, as2, 0, 0, I2, I, I1), ilo));
     else
-        Rn.gemm(f->x_emb, hidden, c.in_channels, B * I, img, D, 0, 0, ires, nullptr, 0, 0, 0, 0, 0, 0, 0, 0, ilo);
+        Rn.gemm(f->x_emb, hidden, c.in_channels, B * I, img, D, 0, 0, ires, nullptr, 0, 0, as1, 0, 0, 0, 0, 0, ilo);
     Rn.gemm(f->c_emb, enc, c.joint_attention_dim, B * T, ctx, D, 0, 0, cres, nullptr, 0, 0, 0, 0, 0, 0, 0, 0, clo);
 
     // ---- double-stream blocks -----------------------------------------------------------------------------------
@@ -474,9 +478,17 @@ int cs_flux_get_output_dtype(const CsFlux* f) { return f ? (f->out_f32 ? CS_F32 
 int cs_flux_forward_joint(CsFlux* f, const void* latents, int lat_len, const void* image_latents, int image_len, int batch,
                           const void* encoder_hidden_states, int txt_len, const float* pooled_f32, const float* timestep, const float* guidance,
                           const float* rope_cos, const float* rope_sin, void* out, void* workspace, size_t workspace_bytes, void* stream) {
+    return cs_flux_forward_joint_rows(f, latents, lat_len, image_latents, image_len, batch, batch, encoder_hidden_states, txt_len, pooled_f32, timestep,
+                                      guidance, rope_cos, rope_sin, out, workspace, workspace_bytes, stream);
+}
+
+int cs_flux_forward_joint_rows(CsFlux* f, const void* latents, int lat_len, const void* image_latents, int image_len, int latent_rows, int batch,
+                               const void* encoder_hidden_states, int txt_len, const float* pooled_f32, const float* timestep, const float* guidance,
+                               const float* rope_cos, const float* rope_sin, void* out, void* workspace, size_t workspace_bytes, void* stream) {
     if (!f) CS_FAIL(CS_E_ARG, "flux is NULL");
     if (!f->manifest.finalized) CS_FAIL(CS_E_STATE, "cs_flux_finalize has not been called");
     if (batch <= 0) return batch < 0 ? CS_E_SHAPE : CS_OK;
+    if (latent_rows <= 0 || batch % latent_rows) CS_FAIL(CS_E_SHAPE, "flux: batch %d is not a positive multiple of latent_rows %d", batch, latent_rows);
     if (!latents || !encoder_hidden_states || !pooled_f32 || !timestep || !rope_cos || !rope_sin || !out || !workspace) CS_FAIL(CS_E_ARG, "null pointer");
     if (f->out_f32 && f->residual != CS_RESIDUAL_F16X2) CS_FAIL(CS_E_STATE, "flux: an fp32 output (cs_flux_set_output_dtype) is the split stream's (CS_RESIDUAL_F16X2)");
     if (f->cfg.guidance_embeds && !guidance) CS_FAIL(CS_E_ARG, "guidance is required (guidance_embeds)");
@@ -485,7 +497,7 @@ int cs_flux_forward_joint(CsFlux* f, const void* latents, int lat_len, const voi
     const TuneSet k = tune_snapshot();
     TuneScope scope(&k);
     return flux_forward(f, false, latents, batch, lat_len + image_len, encoder_hidden_states, txt_len, pooled_f32, timestep, guidance, rope_cos,
-                        rope_sin, out, (char*)workspace, workspace_bytes, (hipStream_t)stream, image_len > 0 ? image_latents : nullptr, image_len);
+                        rope_sin, out, (char*)workspace, workspace_bytes, (hipStream_t)stream, image_len > 0 ? image_latents : nullptr, image_len, latent_rows);
 }
 
 }  // extern "C"

@@ -7,6 +7,7 @@
 //   cs_dpm_multistep_step : CFG combine + model-output conversion + Multistep DPM-Solver update (orders 1, 2)
 //   cs_unipc_step : CFG combine + x0 conversion + UniPC corrector of the previous update + predictor (bh1 / bh2, orders 1, 2)
 //   cs_fm_general_step : the flow-matching baselines' update (Euler / Heun / dpm-solver / multistep, edit_ppo/scheduler_fm.py:405-482)
+//   cs_true_cfg_combine : true classifier-free guidance of the Kontext edit, neg + scale * (pos - neg) (edit_ppo/pipeline.py:1115)
 //   cs_factor_probs   : FactorNetPPO.forward_ (factor_net_ppo.py:137-157)
 //   cs_cosine_features: compute_cosine_similarity (factor_net_ppo.py:108-130)
 //   cs_sample_actions / cs_gather_actions / cs_action_probs / cs_step_masks / cs_stack_history
@@ -630,6 +631,88 @@ int launch_fm_step(const CsFmStepArgs* a, void* stream) {
     return CS_OK;
 }
 
+// ---------------------------------------------------------------- true classifier-free guidance (edit_ppo/pipeline.py:1115)
+// out = cast_out(neg + scale * (pos - neg)): the value rounded ONCE to the output dtype (the rule of the CFG line of lms_step_kernel), not the reference's
+// three 16-bit ops.  The three fp32 operations are carried with their rounding errors (two-sum for the difference and the sum, an fma for the product's
+// error), so what is rounded at the end is the exact value to ~2^-45: where 4 pos and 3 neg cancel, the plain fp32 expression is off by several units of an
+// fp32 -- or of a subnormal fp16 -- result.  Memory-bound: the ~20 flops per element are free.
+__device__ __forceinline__ float true_cfg_one(float p, float n, float s) {
+    const float d = p - n, db = d - p, de = (p - (d - db)) + (-n - db);          // d + de = p - n
+    const float m = s * d, me = __builtin_fmaf(s, d, -m);                        // m + me = s * d
+    const float r = n + m, rb = r - n, re = (n - (r - rb)) + (m - rb);           // r + re = n + m
+    const float c = re + (me + s * de);
+    return fabsf(c) < INFINITY ? r + c : r;                                      // (inf / NaN operands: the plain expression's result)
+}
+
+struct CfgParams { const void* pos; const void* neg; void* out; float scale; int64_t n; int in_vec; };
+
+// V elements per lane: 8 with a 16-bit output (one 16-byte store; fp32 inputs as two 16-byte loads each), 4 for fp32 -> fp32.
+// in_vec == 0 (fp32 inputs of a mixed pair that are only 4-byte aligned): element loads.  Every lane reads its elements before it writes them and the
+// vector body and the tail cover disjoint ranges, so out may be pos or neg when the element sizes are equal.
+template <typename TI, typename TO>
+__global__ __launch_bounds__(256) void true_cfg_kernel(CfgParams p) {
+    constexpr int V = Io<TO>::VEC;
+    const int64_t nvec = p.n / V;
+    for (int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; v < nvec; v += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t i = v * V;
+        float a[V], b[V], o[V];
+        if constexpr (Io<TI>::VEC == V) {
+            Io<TI>::load(p.pos, i, a); Io<TI>::load(p.neg, i, b);
+        } else if (p.in_vec) {   // block-uniform
+            float t[4];
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                Io<float>::load(p.pos, i + 4 * h, t);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) a[4 * h + j] = t[j];
+                Io<float>::load(p.neg, i + 4 * h, t);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) b[4 * h + j] = t[j];
+            }
+        } else {
+#pragma unroll
+            for (int j = 0; j < V; ++j) { a[j] = Io<TI>::load1(p.pos, i + j); b[j] = Io<TI>::load1(p.neg, i + j); }
+        }
+#pragma unroll
+        for (int j = 0; j < V; ++j) o[j] = true_cfg_one(a[j], b[j], p.scale);
+        Io<TO>::store(p.out, i, o);
+    }
+    // scalar tail (n % V != 0): handled by the first block
+    if (blockIdx.x == 0)
+        for (int64_t i = nvec * V + threadIdx.x; i < p.n; i += blockDim.x)
+            Io<TO>::store1(p.out, i, true_cfg_one(Io<TI>::load1(p.pos, i), Io<TI>::load1(p.neg, i), p.scale));
+}
+
+int launch_true_cfg(const void* pos, const void* neg, int in_dtype, float scale, void* out, int out_dtype, int64_t n, void* stream) {
+    if (n < 0) CS_FAIL(CS_E_SHAPE, "negative length");
+    const bool pair_ok = (in_dtype == CS_F32 && (out_dtype == CS_F32 || out_dtype == CS_F16 || out_dtype == CS_BF16)) ||
+                         ((in_dtype == CS_F16 || in_dtype == CS_BF16) && out_dtype == in_dtype);
+    if (!pair_ok) CS_FAIL(CS_E_DTYPE, "unsupported in/out dtype pair (%d,%d)", in_dtype, out_dtype);
+    if (n == 0) return CS_OK;
+    if (!pos || !neg || !out) CS_FAIL(CS_E_ARG, "pos, neg and out are required");
+    const bool mixed = in_dtype == CS_F32 && out_dtype != CS_F32;
+    // one 16-byte load / store per lane and tensor; the fp32 side of a mixed pair needs its element's 4 bytes only (launch_fm_step's rule)
+    if ((((uintptr_t)pos | (uintptr_t)neg) & (mixed ? 3 : 15)) || ((uintptr_t)out & 15))
+        CS_FAIL(CS_E_ARG, "pos, neg and out must be 16-byte aligned (fp32 inputs beside a 16-bit output: 4-byte)");
+    if (mixed && (out == pos || out == neg)) CS_FAIL(CS_E_ARG, "out may alias pos or neg only when the element sizes are equal");
+    CfgParams p{pos, neg, out, scale, n, (((uintptr_t)pos | (uintptr_t)neg) & 15) == 0};
+    const int vec = out_dtype == CS_F32 ? 4 : 8;
+    // the same capped grid as launch_fm_step
+    int64_t gx = (n / vec + 255) / 256;
+    if (gx > 2048) gx = 2048; if (gx < 1) gx = 1;
+    dim3 grid((unsigned)gx), block(256);
+    hipStream_t s = (hipStream_t)stream;
+#define LAUNCH(TI, TO) hipLaunchKernelGGL((true_cfg_kernel<TI, TO>), grid, block, 0, s, p)
+    if (in_dtype == CS_F16) LAUNCH(f16, f16);
+    else if (in_dtype == CS_BF16) LAUNCH(bf16_tag, bf16_tag);
+    else if (out_dtype == CS_F32) LAUNCH(float, float);
+    else if (out_dtype == CS_F16) LAUNCH(float, f16);
+    else LAUNCH(float, bf16_tag);
+#undef LAUNCH
+    CS_CHECK_LAUNCH();
+    return CS_OK;
+}
+
 // ---------------------------------------------------------------- policy MLP
 // one workgroup per DISTINCT conditioning row; weights (<= ~1 MB) stay in L2.  When one row is
 // broadcast to all B samples (x_row_stride == 0, no cosine features: every sampling step), a single
@@ -853,6 +936,9 @@ int cs_lms_euler_step(const CsStepArgs* args, void* stream) { return launch_step
 int cs_dpm_multistep_step(const CsDpmStepArgs* args, void* stream) { return launch_dpm_step(args, stream); }
 int cs_unipc_step(const CsUnipcStepArgs* args, void* stream) { return launch_unipc_step(args, stream); }
 int cs_fm_general_step(const CsFmStepArgs* args, void* stream) { return launch_fm_step(args, stream); }
+int cs_true_cfg_combine(const void* pos, const void* neg, int in_dtype, float scale, void* out, int out_dtype, int64_t n, void* stream) {
+    return launch_true_cfg(pos, neg, in_dtype, scale, out, out_dtype, n, stream);
+}
 
 int cs_factor_probs(const CsFactorNet* n, const float* x, int x_row_stride, const float* cos_feat, int B, float* probs, void* stream) {
     if (!n) CS_FAIL(CS_E_ARG, "net is NULL");

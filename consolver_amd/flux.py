@@ -70,6 +70,7 @@ def rope_tables(ids, axes_dims, theta=10000.0):
 
 class HipFluxTransformer2DModel:
     is_consolver_hip = True
+    broadcasts_latent_rows = True        # __call__ takes R latent rows beside G * R text rows (cs_flux_forward_joint_rows)
 
     RESIDUAL_MODES = {"plain": 0, "bf16": 0, "f16": 0, "split": 1, "bf16x2": 1, "f16x2": 1}
 
@@ -173,21 +174,28 @@ class HipFluxTransformer2DModel:
         ``torch.cat``) and the result holds the rows of ``hidden_states`` only ([B, I, 64], i.e. the reference's
         ``noise_pred[:, :latents.size(1)]`` without the slice copy); ``img_ids`` cover I + I2 tokens.
         ``out_dtype=torch.float32`` (split stream only; cs_flux_set_output_dtype): the prediction as the unrounded sum of the output head's two planes instead of
-        their hi plane in the model dtype."""
+        their hi plane in the model dtype.
+        Row broadcast (true classifier-free guidance: [prompt | negative prompt] rows of the same latents): ``hidden_states`` / ``image_latents`` may hold R rows
+        beside ``encoder_hidden_states`` / ``pooled_projections`` of G * R rows; batch row b reads latent row b % R and the result is [G * R, I, 64], bit-identical
+        to the call on ``hidden_states.repeat(G, 1, 1)``.  A row count that is not a multiple of R raises ValueError."""
         if not self._finalized:
             raise RuntimeError("weights not loaded")
         L.require_cuda(hidden_states, "hidden_states")
         hs = hidden_states.to(self.dtype).contiguous()
         enc = L.require_cuda(encoder_hidden_states, "encoder_hidden_states").to(self.dtype).contiguous()
-        B, I, _ = hs.shape
-        T = enc.shape[1]
+        R, I, _ = hs.shape
+        B, T = enc.shape[0], enc.shape[1]
+        if R <= 0 or B % R:
+            raise ValueError(f"encoder_hidden_states has {B} rows, not a multiple of the {R} rows of hidden_states")
         il, I2 = None, 0
         if image_latents is not None:
             il = L.require_cuda(image_latents, "image_latents").to(self.dtype).contiguous()
-            if il.shape[0] != B or il.shape[2] != hs.shape[2]:
-                raise ValueError("image_latents must be [B, I2, in_channels]")
+            if il.shape[0] != R or il.shape[2] != hs.shape[2]:
+                raise ValueError("image_latents must be [B, I2, in_channels] with the rows of hidden_states")
             I2 = il.shape[1]
         pooled = L.require_cuda(pooled_projections, "pooled_projections").to(torch.float32).contiguous()
+        if pooled.shape[0] != B:
+            raise ValueError(f"pooled_projections has {pooled.shape[0]} rows, encoder_hidden_states {B}")
         t = timestep.to(device=hs.device, dtype=torch.float32).reshape(-1) if torch.is_tensor(timestep) else \
             torch.full((B,), float(timestep), dtype=torch.float32, device=hs.device)
         if t.numel() == 1:
@@ -199,6 +207,10 @@ class HipFluxTransformer2DModel:
             g = guidance.to(device=hs.device, dtype=torch.float32).reshape(-1)
             if g.numel() == 1:
                 g = g.expand(B).contiguous()
+        if t.numel() != B or (g is not None and g.numel() != B):
+            raise ValueError(f"timestep and guidance must hold 1 or {B} values (one per row of encoder_hidden_states)")
+        # (an `expand`ed scalar has B elements behind ONE address: the kernels read B consecutive floats)
+        t, g = t.contiguous(), (g.contiguous() if g is not None else None)
         cos, sin = self._rope_dev(txt_ids, img_ids)
         if cos.shape[0] != T + I + I2:
             raise ValueError(f"ids cover {cos.shape[0]} tokens, expected {T + I + I2}")
@@ -218,16 +230,32 @@ class HipFluxTransformer2DModel:
             out = torch.empty(B, I, self.config["in_channels"], dtype=odt, device=hs.device)
         elif out.dtype != odt or tuple(out.shape) != (B, I, self.config["in_channels"]) or not out.is_contiguous():
             raise ValueError(f"out must be a contiguous {odt} tensor of shape {(B, I, self.config['in_channels'])}")
-        if il is None:
+        if il is None and R == B:
             L.check(L.lib().cs_flux_forward(self._h, L.ptr(hs), B, I, L.ptr(enc), T, L.ptr(pooled), L.ptr(t), L.ptr(g), L.ptr(cos),
                                             L.ptr(sin), L.ptr(out), L.ptr(self._ws), self._ws.numel(), L.stream_ptr(hs.device)))
         else:
-            L.check(L.lib().cs_flux_forward_joint(self._h, L.ptr(hs), I, L.ptr(il), I2, B, L.ptr(enc), T, L.ptr(pooled), L.ptr(t),
-                                                  L.ptr(g), L.ptr(cos), L.ptr(sin), L.ptr(out), L.ptr(self._ws), self._ws.numel(),
-                                                  L.stream_ptr(hs.device)))
+            L.check(L.lib().cs_flux_forward_joint_rows(self._h, L.ptr(hs), I, L.ptr(il), I2, R, B, L.ptr(enc), T, L.ptr(pooled), L.ptr(t),
+                                                       L.ptr(g), L.ptr(cos), L.ptr(sin), L.ptr(out), L.ptr(self._ws), self._ws.numel(),
+                                                       L.stream_ptr(hs.device)))
         if return_dict:
             return {"sample": out}
         return (out,)
+
+
+def true_cfg_combine(pos, neg, scale, out_dtype=None, out=None):
+    """``neg + scale * (pos - neg)`` rounded once to ``out_dtype`` (cs_true_cfg_combine; edit_ppo/pipeline.py:1115): pos / neg fp32 with any of
+    fp32 / fp16 / bf16 out, or a 16-bit dtype in and the same out (the default).  ``out`` may be ``pos`` or ``neg`` when the dtypes are equal."""
+    L.require_cuda(pos, "pos"); L.require_cuda(neg, "neg")
+    if pos.shape != neg.shape or pos.dtype != neg.dtype:
+        raise ValueError(f"pos {tuple(pos.shape)} {pos.dtype} and neg {tuple(neg.shape)} {neg.dtype} differ")
+    pos, neg = pos.contiguous(), neg.contiguous()
+    if out is None:
+        out = torch.empty(pos.shape, dtype=out_dtype or pos.dtype, device=pos.device)
+    elif out.shape != pos.shape or not out.is_contiguous() or (out_dtype is not None and out.dtype != out_dtype):
+        raise ValueError("out must be a contiguous tensor of the inputs' shape and of out_dtype")
+    L.check(L.lib().cs_true_cfg_combine(L.ptr(pos), L.ptr(neg), L.dtype_code(pos.dtype), float(scale), L.ptr(out), L.dtype_code(out.dtype),
+                                        pos.numel(), L.stream_ptr(pos.device)))
+    return out
 
 
 class FluxKontextSamplingEngine:
@@ -240,13 +268,39 @@ class FluxKontextSamplingEngine:
 
     @torch.no_grad()
     def generate(self, latents, image_latents, prompt_embeds, pooled_prompt_embeds, latent_hw, image_hw=None,
-                 num_inference_steps=8, record=False):
+                 num_inference_steps=8, record=False, negative_prompt_embeds=None, negative_pooled_prompt_embeds=None, true_cfg_scale=1.0,
+                 true_cfg_dtype=None):
         """latents / image_latents: packed [B, L, 64]; latent_hw = (H/2, W/2) of the packed grid.
         record=True additionally returns the PPO trajectory records of edit_ppo/denoise_diffusion.py:152-172
-        (conds{x, epsilon}, probs, actions, masks; steps i > 0 only)."""
+        (conds{x, epsilon}, probs, actions, masks; steps i > 0 only).
+
+        True classifier-free guidance (edit_ppo/pipeline.py:937-940, 1100-1115) runs when ``true_cfg_scale > 1`` AND both negative tensors are given;
+        otherwise the loop is the unguided one, forward rows included.  Per step: the prompt and the negative-prompt prediction -- one forward of 2 B text
+        rows over the B latent rows on a transformer that ``broadcasts_latent_rows``, two forwards on any other callable -- then
+        ``v = neg + true_cfg_scale * (pos - neg)`` rounded once to the latents' dtype (cs_true_cfg_combine), then the unchanged ``scheduler.step``;
+        the recorded ``epsilon`` history holds the combined v.  ``true_cfg_dtype``: dtype of the two predictions entering the combine, ``torch.float32``
+        (the DiT head's unrounded value; HIP model on the split stream only, else ValueError) or the latents' dtype; None = fp32 where available."""
         dev = latents.device
         B, Lq, _ = latents.shape
         sch = self.scheduler
+        tr = self.transformer
+        do_true_cfg = float(true_cfg_scale) > 1.0 and negative_prompt_embeds is not None and negative_pooled_prompt_embeds is not None
+        if do_true_cfg:
+            f32_ok = bool(getattr(tr, "is_consolver_hip", False)) and getattr(tr, "residual", None) == "split"
+            if true_cfg_dtype is None:
+                true_cfg_dtype = torch.float32 if f32_ok else latents.dtype
+            if true_cfg_dtype not in (torch.float32, latents.dtype):
+                raise ValueError(f"true_cfg_dtype must be torch.float32 or the latents' dtype {latents.dtype}, got {true_cfg_dtype}")
+            if true_cfg_dtype == torch.float32 and latents.dtype != torch.float32 and not f32_ok:
+                raise ValueError("true_cfg_dtype=torch.float32 needs a transformer with an fp32 output: HipFluxTransformer2DModel on the split stream")
+            if negative_prompt_embeds.shape[0] != B or negative_pooled_prompt_embeds.shape[0] != B:
+                raise ValueError(f"negative_prompt_embeds / negative_pooled_prompt_embeds must have the {B} rows of the latents")
+            okw = {"out_dtype": torch.float32} if true_cfg_dtype == torch.float32 and latents.dtype != torch.float32 else {}
+            # one forward for both branches: the text rows [prompt | negative] over the SAME latent rows (needs equal text lengths)
+            one_forward = bool(getattr(tr, "broadcasts_latent_rows", False)) and negative_prompt_embeds.shape[1:] == prompt_embeds.shape[1:]
+            if one_forward:
+                enc2 = torch.cat([prompt_embeds, negative_prompt_embeds.to(prompt_embeds.dtype)], 0)
+                pooled2 = torch.cat([pooled_prompt_embeds, negative_pooled_prompt_embeds.to(pooled_prompt_embeds.dtype)], 0)
         sigmas = np.linspace(1.0, 1 / num_inference_steps, num_inference_steps)
         mu = calculate_shift(Lq, sch.config.get("base_image_seq_len", 256), sch.config.get("max_image_seq_len", 4096),
                              sch.config.get("base_shift", 0.5), sch.config.get("max_shift", 1.15))
@@ -257,6 +311,9 @@ class FluxKontextSamplingEngine:
             ids = np.concatenate([ids, prepare_latent_image_ids(*(image_hw or latent_hw), first=1.0)], 0)
         txt_ids = np.zeros((prompt_embeds.shape[1], 3), np.float32)
         guidance = torch.full([B], self.guidance_scale, device=dev, dtype=torch.float32)
+        if do_true_cfg:
+            neg_txt_ids = txt_ids if negative_prompt_embeds.shape[1] == prompt_embeds.shape[1] else np.zeros((negative_prompt_embeds.shape[1], 3), np.float32)
+            guidance2 = torch.full([2 * B], self.guidance_scale, device=dev, dtype=torch.float32)
         # timestep / 1000 in the model dtype like the reference (`t.expand(B).to(dtype)` then `/ 1000`, pipeline.py:1084-1089)
         sig = (sch.timesteps.to(latents.dtype) / 1000).to(torch.float32)
         x = latents
@@ -272,8 +329,21 @@ class FluxKontextSamplingEngine:
         try:
             for i, t in enumerate(sch.timesteps):
                 # [latents | image_latents] is read in place by the embedder; v holds the latent rows only
-                v = self.transformer(x, sig[i:i + 1].expand(B), guidance=guidance, pooled_projections=pooled_prompt_embeds,
-                                     encoder_hidden_states=prompt_embeds, txt_ids=txt_ids, img_ids=ids, image_latents=image_latents)[0]
+                if not do_true_cfg:
+                    v = self.transformer(x, sig[i:i + 1].expand(B), guidance=guidance, pooled_projections=pooled_prompt_embeds,
+                                         encoder_hidden_states=prompt_embeds, txt_ids=txt_ids, img_ids=ids, image_latents=image_latents)[0]
+                else:
+                    if one_forward:
+                        both = tr(x, sig[i:i + 1].expand(2 * B), guidance=guidance2, pooled_projections=pooled2, encoder_hidden_states=enc2,
+                                  txt_ids=txt_ids, img_ids=ids, image_latents=image_latents, **okw)[0]
+                        pos, neg = both[:B], both[B:]
+                    else:
+                        pos = tr(x, sig[i:i + 1].expand(B), guidance=guidance, pooled_projections=pooled_prompt_embeds,
+                                 encoder_hidden_states=prompt_embeds, txt_ids=txt_ids, img_ids=ids, image_latents=image_latents, **okw)[0]
+                        neg = tr(x, sig[i:i + 1].expand(B), guidance=guidance, pooled_projections=negative_pooled_prompt_embeds,
+                                 encoder_hidden_states=negative_prompt_embeds, txt_ids=neg_txt_ids, img_ids=ids, image_latents=image_latents, **okw)[0]
+                    # (a fresh tensor per step: the scheduler's history keeps a reference to its model output)
+                    v = true_cfg_combine(pos, neg, true_cfg_scale, out_dtype=x.dtype)
                 stepped = sch.step(v, t, x, return_dict=False)
                 x = stepped[0]
                 if record and i > 0:

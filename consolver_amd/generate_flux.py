@@ -8,6 +8,10 @@ Per entry (edit_ppo/pipeline.py:613-623, 1009-1150): reference image -> VAE enco
 image latents; seeded noise -> packed latents; 8-step FMPPOScheduler loop around the DiT; unpack -> VAE decoder -> pixels.
 The text side (T5-XXL + CLIP embeddings of the instruction) needs third-party weights and tokenizers: it is read from an
 embedding cache (``save_instruction_cache``): ``{key}.prompt_embeds`` [512, 4096] and ``{key}.pooled`` [768] in one safetensors file.
+
+True classifier-free guidance (edit_ppo/pipeline.py:1100-1115): ``--true_cfg_scale S`` (> 1) with ``--negative-embeds FILE`` (one negative
+prompt's ``prompt_embeds`` [T, D] and ``pooled`` [768] shared by every entry, ``save_negative_embeds``) runs the negative-prompt branch in every
+step, with every ``--solver``.
 """
 import json
 import os
@@ -69,6 +73,20 @@ def save_instruction_cache(path, embeds):
     save_file(t, path, metadata={"format": "consolver_amd.instruction_cache.v1"})
 
 
+def save_negative_embeds(path, prompt_embeds, pooled):
+    """the one negative prompt of a driver run (``--negative-embeds``): prompt_embeds [T, D] and pooled [768]"""
+    from safetensors.torch import save_file
+    save_file({"prompt_embeds": prompt_embeds.detach().to("cpu", torch.bfloat16).contiguous(),
+               "pooled": pooled.detach().to("cpu", torch.bfloat16).contiguous()}, path, metadata={"format": "consolver_amd.negative_embeds.v1"})
+
+
+def load_negative_embeds(path, device):
+    """-> (negative_prompt_embeds [1, T, D], negative_pooled_prompt_embeds [1, 768]) on ``device``"""
+    from safetensors import safe_open
+    with safe_open(path, framework="pt", device="cpu") as f:
+        return f.get_tensor("prompt_embeds").to(device)[None], f.get_tensor("pooled").to(device)[None]
+
+
 def load_instruction_embeds(cache, key, device):
     return cache.get_tensor(f"{key}.prompt_embeds").to(device)[None], cache.get_tensor(f"{key}.pooled").to(device)[None]
 
@@ -81,8 +99,9 @@ def preprocess_image(path, size):
     return (x * 2 - 1)[None]
 
 
-def process_instruction(entry, engine, vae, cache, image_dir, output_dir, device, num_inference_steps=8, seed=0):
-    """generate_ours.py:50-104 for one entry; returns the edited-image path (or None when the reference image is missing)."""
+def process_instruction(entry, engine, vae, cache, image_dir, output_dir, device, num_inference_steps=8, seed=0, negative=None, true_cfg_scale=1.0):
+    """generate_ours.py:50-104 for one entry; returns the edited-image path (or None when the reference image is missing).
+    ``negative``: (negative_prompt_embeds [1, T, D], negative_pooled_prompt_embeds [1, 768]) for true CFG at ``true_cfg_scale`` > 1."""
     from PIL import Image
     key, category, file_name, instruction = entry["key"], entry["category"], entry["file_name"], entry["instruction"]
     src = os.path.join(image_dir, os.path.basename(file_name))
@@ -100,7 +119,8 @@ def process_instruction(entry, engine, vae, cache, image_dir, output_dir, device
     noise = torch.randn(1, vae.config.latent_channels, S, S, generator=gen).to(device)
     latents = pack_latents(noise).to(torch.bfloat16)
     pe, pooled = load_instruction_embeds(cache, key, device)
-    out = engine.generate(latents, image_latents, pe, pooled, latent_hw=(S // 2, S // 2), num_inference_steps=num_inference_steps)
+    cfg_kw = {} if negative is None else dict(negative_prompt_embeds=negative[0], negative_pooled_prompt_embeds=negative[1], true_cfg_scale=true_cfg_scale)
+    out = engine.generate(latents, image_latents, pe, pooled, latent_hw=(S // 2, S // 2), num_inference_steps=num_inference_steps, **cfg_kw)
     img = flux_decode_latents(vae, out.to(torch.float16), height=8 * S, width=8 * S)[0]
     arr = (img.float().clamp(0, 1).permute(1, 2, 0) * 255.0).round().to(torch.uint8).cpu().numpy()
     dst = ensure_unique_path(os.path.join(sub, "edited_image.jpg"))
@@ -108,13 +128,14 @@ def process_instruction(entry, engine, vae, cache, image_dir, output_dir, device
     return dst
 
 
-def worker(entries, engine, vae, cache_path, image_dir, output_dir, device, num_inference_steps=8):
+def worker(entries, engine, vae, cache_path, image_dir, output_dir, device, num_inference_steps=8, negative=None, true_cfg_scale=1.0):
     """generate_ours.py:107-148 with the models already built for this process."""
     from safetensors import safe_open
     done = 0
     with safe_open(cache_path, framework="pt", device="cpu") as cache:
         for entry in entries:
-            done += process_instruction(entry, engine, vae, cache, image_dir, output_dir, device, num_inference_steps) is not None
+            done += process_instruction(entry, engine, vae, cache, image_dir, output_dir, device, num_inference_steps,
+                                        negative=negative, true_cfg_scale=true_cfg_scale) is not None
     return done
 
 
@@ -182,13 +203,9 @@ def load_models(args, ap, dev, transformer=None, vae=None):
     return transformer, vae
 
 
-def main(argv=None, *, transformer=None, vae=None):
-    """``python -m consolver_amd.generate_flux``: generate_ours.py / generate_pretrain.py as one command, one process per GPU
-    (``launch``).  ``transformer`` / ``vae``: already loaded HIP handles to run on instead of building them from the arguments."""
+def parse_args(argv=None):
+    """-> (parser, args) of ``python -m consolver_amd.generate_flux``; argument conflicts are parser errors (SystemExit)"""
     import argparse
-    import tempfile
-    import time
-    from .flux import FluxKontextSamplingEngine
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--out", required=True)
     ap.add_argument("--jsonl"), ap.add_argument("--image-dir"), ap.add_argument("--instruction-cache")
@@ -198,11 +215,26 @@ def main(argv=None, *, transformer=None, vae=None):
     ap.add_argument("--guidance", type=float, default=2.5)
     ap.add_argument("--solver", default="consistencysolver", choices=FLUX_SOLVERS,
                     help="the learned solver (default) or a comparison method of generate_pretrain.py (scheduler type); those have no policy")
+    ap.add_argument("--true_cfg_scale", type=float, default=1.0,
+                    help="> 1: true classifier-free guidance, a second DiT branch on the negative prompt in every step (needs --negative-embeds or --synthetic)")
+    ap.add_argument("--negative-embeds", help="safetensors file with the negative prompt's prompt_embeds [T, D] and pooled [768] (save_negative_embeds)")
     args = ap.parse_args(argv)
     if args.solver != "consistencysolver" and args.policy:
         ap.error(f"--policy belongs to the learned solver; --solver {args.solver} has no policy")
     if not args.synthetic and not (args.jsonl and args.image_dir and args.instruction_cache):
         ap.error("pass --jsonl, --image-dir and --instruction-cache, or --synthetic N")
+    if args.true_cfg_scale > 1.0 and not args.synthetic and not args.negative_embeds:
+        ap.error("--true_cfg_scale > 1 needs the negative prompt's embeddings: pass --negative-embeds FILE")
+    return ap, args
+
+
+def main(argv=None, *, transformer=None, vae=None):
+    """``python -m consolver_amd.generate_flux``: generate_ours.py / generate_pretrain.py as one command, one process per GPU
+    (``launch``).  ``transformer`` / ``vae``: already loaded HIP handles to run on instead of building them from the arguments."""
+    import tempfile
+    import time
+    from .flux import FluxKontextSamplingEngine
+    ap, args = parse_args(argv)
     rank, world, local, dist = launch.init_distributed()
     torch.cuda.set_device(local)
     dev = torch.device("cuda", local)
@@ -219,10 +251,19 @@ def main(argv=None, *, transformer=None, vae=None):
                                                       transformer.config["pooled_projection_dim"], 8 * vae.config.sample_size)
         else:
             data, image_dir, cache = load_jsonl(args.jsonl), args.image_dir, args.instruction_cache
+        negative = None
+        if args.true_cfg_scale > 1.0:
+            if args.negative_embeds:
+                negative = load_negative_embeds(args.negative_embeds, dev)
+            else:       # --synthetic: one seeded negative embedding of the synthetic instructions' shape
+                g = torch.Generator().manual_seed(2002)
+                negative = (torch.randn(1, 64, transformer.config["joint_attention_dim"], generator=g).to(dev, torch.bfloat16),
+                            torch.randn(1, transformer.config["pooled_projection_dim"], generator=g).to(dev, torch.bfloat16))
         if dist is not None:
             dist.barrier()
         t0 = time.perf_counter()
-        n = worker(shard_for_rank(data, world, rank), eng, vae, cache, image_dir, args.out, dev, num_inference_steps=args.steps)
+        n = worker(shard_for_rank(data, world, rank), eng, vae, cache, image_dir, args.out, dev, num_inference_steps=args.steps,
+                   negative=negative, true_cfg_scale=args.true_cfg_scale)
         torch.cuda.synchronize()
     secs = launch.reduce_max_seconds(dist, time.perf_counter() - t0, device=dev)
     report = launch.gather_report(dist, n, 0.0, device=dev)
@@ -231,10 +272,10 @@ def main(argv=None, *, transformer=None, vae=None):
         print(f"{total} edits in {secs:.2f} s = {total / secs:.2f} edits/s on {world} GPU(s); per rank: {[c for c, _ in report]}")
     if dist is not None:
         dist.destroy_process_group()
-    return {"edits": n, "seconds": secs, "solver": args.solver, "steps": args.steps}
+    return {"edits": n, "seconds": secs, "solver": args.solver, "steps": args.steps, "true_cfg_scale": args.true_cfg_scale if negative is not None else 1.0}
 
 
-__all__ = ["sanitize_folder_name", "ensure_unique_path", "load_jsonl", "chunk_entries", "shard_for_rank", "save_instruction_cache",
+__all__ = ["sanitize_folder_name", "ensure_unique_path", "load_jsonl", "chunk_entries", "shard_for_rank", "save_instruction_cache", "save_negative_embeds", "load_negative_embeds", "parse_args",
            "process_instruction", "worker", "launch", "FLUX_SOLVERS", "make_scheduler", "main"]
 
 

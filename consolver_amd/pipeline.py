@@ -86,7 +86,12 @@ class FluxKontextEditPipeline:
     ``pipe(image=ref_image, prompt=instruction, num_inference_steps=8, guidance_scale=2.5, generator=torch.manual_seed(0)).images[0]``
     on the HIP components: T5 + CLIP text encoders -> VAE encoder of the reference image -> FMPPOScheduler loop around the DiT ->
     VAE decoder.  Token ids (``input_ids_t5`` / ``input_ids_clip``) or precomputed ``prompt_embeds`` / ``pooled_prompt_embeds`` replace
-    ``prompt`` when the tokenizers' asset files are not at hand."""
+    ``prompt`` when the tokenizers' asset files are not at hand.
+
+    True classifier-free guidance (edit_ppo/pipeline.py:751, 937-969, 1100-1115): ``negative_prompt`` (or ``negative_input_ids_t5`` /
+    ``negative_input_ids_clip``, or ``negative_prompt_embeds`` / ``negative_pooled_prompt_embeds``) together with ``true_cfg_scale > 1`` runs a
+    second DiT branch on the negative prompt and steps on ``neg + true_cfg_scale * (pos - neg)``; ``true_cfg_scale > 1`` without any negative
+    input runs unguided, like the reference."""
 
     def __init__(self, transformer, scheduler, vae, text_encoder=None, text_encoder_2=None, tokenizer=None, tokenizer_2=None, guidance_scale=2.5):
         from .flux import FluxKontextSamplingEngine
@@ -178,7 +183,9 @@ class FluxKontextEditPipeline:
 
     @torch.no_grad()
     def __call__(self, image=None, prompt=None, num_inference_steps=28, guidance_scale=None, generator=None, prompt_embeds=None,
-                 pooled_prompt_embeds=None, input_ids_t5=None, input_ids_clip=None, output_type="pil", return_dict=True, **_ignored):
+                 pooled_prompt_embeds=None, input_ids_t5=None, input_ids_clip=None, output_type="pil", return_dict=True,
+                 negative_prompt=None, negative_prompt_embeds=None, negative_pooled_prompt_embeds=None, true_cfg_scale=1.0,
+                 negative_input_ids_t5=None, negative_input_ids_clip=None, true_cfg_dtype=None, **_ignored):
         from .flux import pack_latents
         from .vae import encode_image_latents, flux_decode_latents
         dev, S = self.vae.device, self.vae.config.sample_size
@@ -187,6 +194,27 @@ class FluxKontextEditPipeline:
         if prompt_embeds is None or pooled_prompt_embeds is None:
             prompt_embeds, pooled_prompt_embeds, _ = self.encode_prompt(prompt, input_ids_t5=input_ids_t5, input_ids_clip=input_ids_clip)
         B = prompt_embeds.shape[0]
+        # edit_ppo/pipeline.py:937-969: the negative prompt is encoded exactly like the prompt, and only when guidance will use it
+        has_negative = negative_prompt is not None or (negative_input_ids_t5 is not None and negative_input_ids_clip is not None) or \
+            (negative_prompt_embeds is not None and negative_pooled_prompt_embeds is not None)
+        do_true_cfg = float(true_cfg_scale) > 1.0 and has_negative
+        if negative_prompt is not None and (self.tokenizer is None or self.tokenizer_2 is None) and \
+                (negative_input_ids_t5 is None or negative_input_ids_clip is None) and \
+                (negative_prompt_embeds is None or negative_pooled_prompt_embeds is None):      # whatever the scale: a string that cannot be encoded is an error
+            raise RuntimeError("a negative text prompt needs both tokenizers; without them pass negative token ids or negative_prompt_embeds / "
+                               "negative_pooled_prompt_embeds")
+        if do_true_cfg:
+            if negative_prompt_embeds is None or negative_pooled_prompt_embeds is None:
+                negative_prompt_embeds, negative_pooled_prompt_embeds, _ = self.encode_prompt(
+                    negative_prompt, input_ids_t5=negative_input_ids_t5, input_ids_clip=negative_input_ids_clip)
+            if negative_prompt_embeds.shape[0] == 1 and B > 1:
+                negative_prompt_embeds = negative_prompt_embeds.expand(B, -1, -1)
+                negative_pooled_prompt_embeds = negative_pooled_prompt_embeds.expand(B, -1)
+            cfg_kw = dict(negative_prompt_embeds=negative_prompt_embeds.to(dev, torch.bfloat16).contiguous(),
+                          negative_pooled_prompt_embeds=negative_pooled_prompt_embeds.to(dev, torch.bfloat16).contiguous(),
+                          true_cfg_scale=float(true_cfg_scale), true_cfg_dtype=true_cfg_dtype)
+        else:
+            cfg_kw = {}
         image_latents = None
         if image is not None:
             if not isinstance(image, torch.Tensor):                               # PIL image -> [1, 3, 8S, 8S] in [-1, 1]
@@ -201,7 +229,8 @@ class FluxKontextEditPipeline:
         noise = torch.randn(B, self.vae.config.latent_channels, S, S, generator=generator,
                             device=generator.device if generator is not None else dev).to(dev)
         out = self._engine.generate(pack_latents(noise).to(torch.bfloat16), image_latents, prompt_embeds.to(dev, torch.bfloat16),
-                                    pooled_prompt_embeds.to(dev, torch.bfloat16), latent_hw=(S // 2, S // 2), num_inference_steps=num_inference_steps)
+                                    pooled_prompt_embeds.to(dev, torch.bfloat16), latent_hw=(S // 2, S // 2), num_inference_steps=num_inference_steps,
+                                    **cfg_kw)
         if output_type == "latent":
             images = out
         else:

@@ -239,6 +239,17 @@ typedef struct CsFmStepArgs {
 
 int cs_fm_general_step(const CsFmStepArgs* args, void* stream);
 
+/* True classifier-free guidance of the Kontext edit (edit_ppo/pipeline.py:1100-1115), between the two DiT forwards and an unchanged scheduler step:
+ *     out[i] = round_to_out_dtype(neg[i] + scale * (pos[i] - neg[i]))
+ * evaluated in fp32 with the operations' rounding errors carried along and rounded ONCE (to nearest even): the exact value's rounding, not the
+ * reference's three 16-bit ops.  Dtype pairs: the same 16-bit type in and out, or CS_F32 in with CS_F16 / CS_BF16 / CS_F32 out (the DiT's fp32
+ * head output, cs_flux_set_output_dtype); anything else is CS_E_DTYPE.  pos and neg are typically the two halves of one [2 R, L, 64] forward output.
+ * n < 0: CS_E_SHAPE.  n == 0: no-op whatever the pointers.  A NULL pointer, or one that is not 16-byte aligned (fp32 inputs beside a 16-bit
+ * output: 4-byte), is CS_E_ARG.  out may be pos or neg (exactly, not a shifted overlap) ONLY when input and output elements have the same size;
+ * with fp32 in and 16 bits out that is CS_E_ARG.  All codes are returned before any launch. */
+int cs_true_cfg_combine(const void* pos, const void* neg, int in_dtype /* CS_F32 | CS_F16 | CS_BF16 */, float scale,
+                        void* out, int out_dtype /* CS_F16 | CS_BF16 | CS_F32 */, int64_t n, void* stream);
+
 /* ------------------------------------------------------------------------
  * SD1.5 UNet2DConditionModel forward (denoiser).  See DESIGN.md for the
  * activation layout (NHWC fp16) and the kernels behind it.
@@ -376,6 +387,15 @@ int cs_flux_forward_joint(CsFlux* f, const void* latents, int lat_len, const voi
                           const void* encoder_hidden_states, int txt_len, const float* pooled_f32, const float* timestep,
                           const float* guidance, const float* rope_cos, const float* rope_sin, void* out, void* workspace,
                           size_t workspace_bytes, void* stream);
+/* cs_flux_forward_joint with the latent rows shared between groups of the batch (true classifier-free guidance: [prompt | negative prompt] rows
+ * of the SAME latents): latents [latent_rows, lat_len, C] and image_latents [latent_rows, image_len, C], everything else -- encoder_hidden_states,
+ * pooled_f32, timestep, guidance, out, the workspace size -- `batch` rows, batch a positive multiple of latent_rows (else CS_E_SHAPE).  Row b of the
+ * batch reads latent row b % latent_rows: only the x_embedder reads these buffers, through its row map, so the result equals the call on the
+ * repeated tensors bit for bit.  latent_rows == batch is cs_flux_forward_joint. */
+int cs_flux_forward_joint_rows(CsFlux* f, const void* latents, int lat_len, const void* image_latents, int image_len, int latent_rows, int batch,
+                               const void* encoder_hidden_states, int txt_len, const float* pooled_f32, const float* timestep,
+                               const float* guidance, const float* rope_cos, const float* rope_sin, void* out, void* workspace,
+                               size_t workspace_bytes, void* stream);
 
 /* Storage of the DiT's hidden-state (residual) stream between kernels, as for the UNet (CS_RESIDUAL_* above): CS_RESIDUAL_F16X2 (default) keeps the image / text /
  * joint hidden states as two planes of the model dtype (value = hi + lo): the 57 + 38 gated-residual epilogues add in fp32 and write both planes, the adaLN
