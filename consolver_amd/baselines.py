@@ -16,7 +16,7 @@ import torch
 
 from . import _lib as L
 from .scheduling_fmppo import FMPPOScheduler
-from .scheduling_ppo import PPOScheduler, SolverOutput
+from .scheduling_ppo import PPOScheduler, SolverOutput, result_tensor, step_inputs
 
 
 class DDIMBaselineScheduler(PPOScheduler):
@@ -30,15 +30,7 @@ class DDIMBaselineScheduler(PPOScheduler):
     def step(self, model_output, timestep, sample, return_dict=True, *, eps_uncond=None, guidance_scale=1.0, out=None, out_lp=None, **_ignored):
         if self.num_inference_steps is None:
             raise ValueError("Number of inference steps is 'None'. Call 'set_timesteps' first.")
-        L.require_cuda(model_output, "model_output")
-        L.require_cuda(sample, "sample")
-        model_output, sample = model_output.contiguous(), sample.contiguous()
-        # same dtype rule as PPOScheduler.step: an fp32 sample next to a 16-bit model output stays fp32 through the update (CsStepArgs::x_is_f32, the
-        # engine's default solver state); any other mismatch is cast to the model output's dtype
-        if sample.dtype != model_output.dtype and sample.dtype != torch.float32:
-            sample = sample.to(model_output.dtype)
-        if self.prev_sample_dtype is not None and sample.dtype != self.prev_sample_dtype:
-            sample = sample.to(self.prev_sample_dtype)
+        model_output, sample = step_inputs(model_output, sample, self.prev_sample_dtype)      # (PPOScheduler.step's dtype rule)
         dev, B = model_output.device, model_output.shape[0]
         t = self._resolve_timestep(timestep)
         prev_t = t - self.config.num_train_timesteps // self.num_inference_steps
@@ -47,9 +39,7 @@ class DDIMBaselineScheduler(PPOScheduler):
         self.ets = [model_output]                   # history of one: eps_eff = eps_t
         if self._zero_actions is None or self._zero_actions.shape[0] < B or self._zero_actions.device != dev:
             self._zero_actions = torch.zeros(max(B, 1), 1, dtype=torch.float32, device=dev)
-        prev = out if out is not None else torch.empty_like(sample)
-        if prev.dtype != sample.dtype:
-            raise ValueError(f"step(out=...) must have the sample's dtype {sample.dtype}, got {prev.dtype}")
+        prev = result_tensor(out, sample)
         eps_out = torch.empty_like(model_output) if eps_uncond is not None else None     # the kernel writes the combined eps
         a = L.CsStepArgs()
         self._fill_step_args(a, sample, model_output, eps_uncond, guidance_scale, self._zero_actions, prev, eps_out, sample.dtype, out_lp)
@@ -72,12 +62,7 @@ class FlowMatchEulerBaselineScheduler(FMPPOScheduler):
             raise ValueError("Number of inference steps is 'None'. Call 'set_timesteps' first.")
         if self._step_index is None:
             self._init_step_index(timestep)
-        L.require_cuda(model_output, "model_output")
-        L.require_cuda(sample, "sample")
-        model_output = model_output.contiguous()
-        sample = sample.contiguous()
-        if sample.dtype != model_output.dtype and sample.dtype != torch.float32:        # (an fp32 sample is consumed as fp32: scheduler_fm.py upcasts it, FMPPOScheduler.step does the same)
-            sample = sample.to(model_output.dtype)
+        model_output, sample = step_inputs(model_output, sample)        # (an fp32 sample is consumed as fp32: scheduler_fm.py upcasts it, FMPPOScheduler.step does the same)
         dev, B = model_output.device, model_output.shape[0]
         i = self._step_index
         dt = np.float32(self._sigmas[i + 1] - self._sigmas[i])

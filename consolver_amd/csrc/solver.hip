@@ -16,100 +16,122 @@
 // -ffp-contract=off so that a*b+c is two roundings like torch's separate ops);
 // half/bfloat I/O is converted on load and rounded once on store.
 #include "common.h"
+#include <type_traits>
 
 namespace {
 
+// ---------------------------------------------------------------- element I/O
+// A dtype's element, its 16-byte vector width and its conversions; round(v) is the image of an fp32 value in the dtype.
 template <typename T> struct Io;
 template <> struct Io<float> {
     static constexpr int VEC = 4;
-    typedef f32x4 vec_t;
-    __device__ static vec_t load_raw(const void* p, int64_t i) { return *reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(p) + i); }
-    __device__ static void unpack(vec_t v, float* o) { o[0] = v[0]; o[1] = v[1]; o[2] = v[2]; o[3] = v[3]; }
-    __device__ static void load(const void* p, int64_t i, float (&o)[4]) {
-        f32x4 v = *reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(p) + i);
-        o[0] = v[0]; o[1] = v[1]; o[2] = v[2]; o[3] = v[3];
-    }
-    __device__ static void store(void* p, int64_t i, const float (&o)[4]) {
-        f32x4 v = {o[0], o[1], o[2], o[3]};
-        *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(p) + i) = v;
-    }
-    __device__ static float load1(const void* p, int64_t i) { return reinterpret_cast<const float*>(p)[i]; }
-    __device__ static void store1(void* p, int64_t i, float v) { reinterpret_cast<float*>(p)[i] = v; }
+    typedef float elem_t;
+    __device__ static float to_f32(float v) { return v; }
+    __device__ static float from_f32(float v) { return v; }
     __device__ static float round(float v) { return v; }
 };
 template <> struct Io<f16> {
     static constexpr int VEC = 8;
-    typedef f16x8 vec_t;
-    __device__ static vec_t load_raw(const void* p, int64_t i) { return *reinterpret_cast<const f16x8*>(reinterpret_cast<const f16*>(p) + i); }
-    __device__ static void unpack(vec_t v, float* o) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) o[j] = (float)v[j];
-    }
-    __device__ static void load(const void* p, int64_t i, float (&o)[8]) {
-        f16x8 v = *reinterpret_cast<const f16x8*>(reinterpret_cast<const f16*>(p) + i);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) o[j] = (float)v[j];
-    }
-    __device__ static void store(void* p, int64_t i, const float (&o)[8]) {
-        f16x8 v;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] = (f16)o[j];
-        *reinterpret_cast<f16x8*>(reinterpret_cast<f16*>(p) + i) = v;
-    }
-    __device__ static float load1(const void* p, int64_t i) { return (float)reinterpret_cast<const f16*>(p)[i]; }
-    __device__ static void store1(void* p, int64_t i, float v) { reinterpret_cast<f16*>(p)[i] = (f16)v; }
+    typedef f16 elem_t;
+    __device__ static float to_f32(f16 v) { return (float)v; }
+    __device__ static f16 from_f32(float v) { return (f16)v; }
     __device__ static float round(float v) { return (float)(f16)v; }
 };
 struct bf16_tag {};
 template <> struct Io<bf16_tag> {
     static constexpr int VEC = 8;
-    typedef u32x4 vec_t;
-    __device__ static vec_t load_raw(const void* p, int64_t i) { return *reinterpret_cast<const u32x4*>(reinterpret_cast<const u16*>(p) + i); }
-    __device__ static void unpack(vec_t v, float* o) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) { o[2 * j] = __uint_as_float(v[j] << 16); o[2 * j + 1] = __uint_as_float(v[j] & 0xffff0000u); }
-    }
-    __device__ static void load(const void* p, int64_t i, float (&o)[8]) {
-        u32x4 v = *reinterpret_cast<const u32x4*>(reinterpret_cast<const u16*>(p) + i);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) { o[2 * j] = __uint_as_float(v[j] << 16); o[2 * j + 1] = __uint_as_float(v[j] & 0xffff0000u); }
-    }
-    __device__ static void store(void* p, int64_t i, const float (&o)[8]) {
-        u32x4 v;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) v[j] = (unsigned)f32_to_bf16(o[2 * j]) | ((unsigned)f32_to_bf16(o[2 * j + 1]) << 16);
-        *reinterpret_cast<u32x4*>(reinterpret_cast<u16*>(p) + i) = v;
-    }
-    __device__ static float load1(const void* p, int64_t i) { return bf16_to_f32(reinterpret_cast<const u16*>(p)[i]); }
-    __device__ static void store1(void* p, int64_t i, float v) { reinterpret_cast<u16*>(p)[i] = f32_to_bf16(v); }
+    typedef u16 elem_t;
+    __device__ static float to_f32(u16 v) { return bf16_to_f32(v); }
+    __device__ static u16 from_f32(float v) { return f32_to_bf16(v); }
     __device__ static float round(float v) { return bf16_to_f32(f32_to_bf16(v)); }
 };
 
-// the low-precision copy of a result vector (CsStepArgs::x_out_lp): V = 4 or 8 values as fp16 (lp_bf16 == 0) or bf16, one 8- / 16-byte store
-template <int V>
-__device__ __forceinline__ void store_lp(void* p, int64_t i, const float (&o)[V], int lp_bf16) {
-    unsigned w[V / 2];
+template <typename E, int N> using Vec = E __attribute__((ext_vector_type(N)));
+
+// W consecutive elements of dtype T as they lie in memory: one element (W == 1, the tail), else 16-byte vectors -- two of them for 8 values of an
+// fp32 state beside 8-wide 16-bit model outputs, and a single 8-byte one for 4 16-bit values (the low-precision copy of a 4-wide fp32 result).
+// load and unpack are separate so that a step issues every load before it converts the first value: one round trip to memory per iteration.
+template <typename T, int W>
+struct Raw {
+    typedef typename Io<T>::elem_t E;
+    static constexpr int L = W < Io<T>::VEC ? W : Io<T>::VEC, N = W / L;
+    static_assert(W == 1 || W == 4 || W == 8, "one element, or the vector width of a 32-bit / 16-bit dtype");
+    typedef Vec<E, L> vec_t;
+    vec_t r[N];
+    __device__ __forceinline__ void load(const void* p, int64_t i) {
+        const vec_t* q = reinterpret_cast<const vec_t*>(reinterpret_cast<const E*>(p) + i);
 #pragma unroll
-    for (int j = 0; j < V / 2; ++j) {
-        if (lp_bf16) w[j] = (unsigned)f32_to_bf16(o[2 * j]) | ((unsigned)f32_to_bf16(o[2 * j + 1]) << 16);
-        else { union { f16 h[2]; unsigned u; } c; c.h[0] = (f16)o[2 * j]; c.h[1] = (f16)o[2 * j + 1]; w[j] = c.u; }
+        for (int k = 0; k < N; ++k) r[k] = q[k];
     }
-    if constexpr (V == 8) *reinterpret_cast<u32x4*>(reinterpret_cast<u16*>(p) + i) = u32x4{w[0], w[1], w[2], w[3]};
-    else { typedef unsigned u32x2v __attribute__((ext_vector_type(2))); *reinterpret_cast<u32x2v*>(reinterpret_cast<u16*>(p) + i) = u32x2v{w[0], w[1]}; }
+    __device__ __forceinline__ float get(int j) const { return Io<T>::to_f32(r[j / L][j % L]); }
+    __device__ __forceinline__ void unpack(float (&o)[W]) const {
+#pragma unroll
+        for (int k = 0; k < N; ++k)
+#pragma unroll
+            for (int j = 0; j < L; ++j) o[k * L + j] = Io<T>::to_f32(r[k][j]);
+    }
+};
+// ... and the way back: each value rounded once to T, the same vectors stored
+template <typename T, int W>
+__device__ __forceinline__ void store(void* p, int64_t i, const float (&o)[W]) {
+    typedef Raw<T, W> R;
+    typename R::vec_t* q = reinterpret_cast<typename R::vec_t*>(reinterpret_cast<typename R::E*>(p) + i);
+#pragma unroll
+    for (int k = 0; k < R::N; ++k) {
+        typename R::vec_t v;
+#pragma unroll
+        for (int j = 0; j < R::L; ++j) v[j] = Io<T>::from_f32(o[k * R::L + j]);
+        q[k] = v;
+    }
 }
-__device__ __forceinline__ void store_lp1(void* p, int64_t i, float v, int lp_bf16) {
-    if (lp_bf16) reinterpret_cast<u16*>(p)[i] = f32_to_bf16(v); else reinterpret_cast<f16*>(p)[i] = (f16)v;
+// the low-precision copy of a result (x_out_lp of the args structs) as fp16 (lp_bf16 == 0) or bf16: the 16-bit view of an fp32 state, what
+// `x.to(model dtype)` would round the stored result to
+template <int W>
+__device__ __forceinline__ void store_lp(void* p, int64_t i, const float (&o)[W], int lp_bf16) {
+    if (lp_bf16) store<bf16_tag, W>(p, i, o); else store<f16, W>(p, i, o);
 }
 
+// classifier-free guidance on the model output: e := u + g (e - u), rounded to the model dtype like torch's 16-bit ops
+template <typename TI, int W>
+__device__ __forceinline__ void cfg_combine(float (&e)[W], const float (&u)[W], float g) {
+#pragma unroll
+    for (int j = 0; j < W; ++j) e[j] = Io<TI>::round(u[j] + g * (e[j] - u[j]));
+}
+// the "converted model output" (x0 / eps prediction) of the dpm and unipc steps: e := conv_x x + conv_e e, rounded to the model dtype like the combined eps
+template <typename TI, int W>
+__device__ __forceinline__ void convert_output(float (&e)[W], const float (&x)[W], float conv_x, float conv_e) {
+#pragma unroll
+    for (int j = 0; j < W; ++j) e[j] = Io<TI>::round(conv_x * x[j] + conv_e * e[j]);
+}
+
+// ---------------------------------------------------------------- the streaming skeleton
+// Every update kernel is this one: grid (gx, nb) walks nb ranges of n elements, a grid-stride body of F::V elements per lane and the n % F::V
+// elements of the tail, which block x = 0 of each range handles.  F is the solver: its Params, its per-range set-up F(p, range), its vector width V
+// and one step<W>(p, i) that loads (raw, every tensor before the first conversion), combines, updates and stores W elements at i.  The tail is
+// step<1>, so body and tail are the same code.  The per-sample kernels (lms, dpm) run it with nb = B, n = elems; the others have no per-sample
+// coefficient and run one flat range nb = 1, n = B * elems, where the vector body stays 16-byte aligned whatever elems is.
+// TI is the model outputs' dtype (eps, history, converted outputs), TX the sample's and TO the result's: each TI, or fp32 beside 16-bit model
+// outputs (scheduler_fmppo.py:354 upcasts the sample, not the model output).
+template <typename F>
+__global__ __launch_bounds__(256) void stream_kernel(typename F::Params p, int64_t n) {
+    const F f(p, blockIdx.y);
+    const int64_t base = (int64_t)blockIdx.y * n, nvec = n / F::V;
+    // the tail is fewer than V elements, one per thread; it comes first so that nothing of it is live across the body's loop (with the tail as a
+    // loop after the body the fp32 lms kernel runs out of SGPRs and loses a wave per SIMD)
+    const int64_t t = nvec * F::V + threadIdx.x;
+    if (blockIdx.x == 0 && t < n) f.template step<1>(p, base + t);
+    for (int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; v < nvec; v += (int64_t)gridDim.x * blockDim.x)
+        f.template step<F::V>(p, base + v * F::V);
+}
+
+// ---------------------------------------------------------------- linear multistep + DDIM / Euler
 struct StepParams {
     const void* x; const void* ec; const void* eu; float g;
     const void* hist[CS_MAX_ORDER];
     int m, order, scaler;
     const float* actions; int astride;
-    int64_t elems;
     void* x_out; void* eps_out;
     float sat, s1mat, sap, s1map; int vpred; float dt;
-    int x_f32;   // x is fp32 although eps / history are TI (scheduler_fmppo.py:354 upcasts the sample, not the model output)
     void* x_lp;  // optional 16-bit copy of an fp32 result (CsStepArgs::x_out_lp)
     int lp_bf16; // ... as bf16 (else fp16)
 };
@@ -136,8 +158,10 @@ __device__ __forceinline__ void make_coeffs(const StepParams& p, int b, float (&
     sc1 = (p.scaler >= 2) ? a[p.order] + 1.0f : 1.0f;
 }
 
-template <typename TI, typename TO, bool EULER, bool OUT_X_TI>
-__device__ __forceinline__ float solve_one(const StepParams& p, float x, float e0, const float* h, const float (&c)[CS_MAX_ORDER], float sc0, float sc1) {
+// h[k].get(j) is element j of history entry k: loaded, and converted and read here, for k < m - 1 only
+template <typename TI, bool EULER, int W>
+__device__ __forceinline__ float solve_one(const StepParams& p, float x, float e0, const Raw<TI, W> (&h)[CS_MAX_ORDER - 1], int j, const float (&c)[CS_MAX_ORDER],
+                                           float sc0, float sc1) {
     float eff;
     if (p.m == 1) {
         eff = e0;
@@ -145,7 +169,7 @@ __device__ __forceinline__ float solve_one(const StepParams& p, float x, float e
         eff = c[0] * e0;
 #pragma unroll
         for (int k = 1; k < CS_MAX_ORDER; ++k)
-            if (k < p.m) eff = eff + c[k] * h[k - 1];
+            if (k < p.m) eff = eff + c[k] * h[k - 1].get(j);
     }
     if (p.scaler >= 1) eff = eff * sc0;
     if (p.scaler >= 2) x = x * sc1;
@@ -162,112 +186,35 @@ __device__ __forceinline__ float solve_one(const StepParams& p, float x, float e
     return p.sap * x0 + p.s1map * eff;
 }
 
-template <typename TI, typename TO, bool EULER>
-__global__ __launch_bounds__(256) void lms_step_kernel(StepParams p) {
-    constexpr int V = Io<TI>::VEC;
-    const int b = blockIdx.y;
+template <typename TI, typename TX, typename TO, bool EULER>
+struct LmsStep {
+    typedef StepParams Params;
+    static constexpr int V = Io<TI>::VEC;
     float c[CS_MAX_ORDER], sc0, sc1;
-    make_coeffs(p, b, c, sc0, sc1);
-    const int64_t base = (int64_t)b * p.elems;
-    const int64_t nvec = p.elems / V;
-    for (int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; v < nvec; v += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t i = base + v * V;
-        float x[V], e[V], u[V], h[CS_MAX_ORDER - 1][V], o[V];
-        if (p.x_f32) {   // block-uniform
-#pragma unroll
-            for (int j = 0; j < V; ++j) x[j] = reinterpret_cast<const float*>(p.x)[i + j];
-        } else {
-            Io<TI>::load(p.x, i, x);
-        }
-        Io<TI>::load(p.ec, i, e);
-        if (p.eu) {
-            Io<TI>::load(p.eu, i, u);
-#pragma unroll
-            for (int j = 0; j < V; ++j) e[j] = Io<TI>::round(u[j] + p.g * (e[j] - u[j]));
-        }
+    __device__ __forceinline__ LmsStep(const StepParams& p, int b) { make_coeffs(p, b, c, sc0, sc1); }
+    template <int W>
+    __device__ __forceinline__ void step(const StepParams& p, int64_t i) const {
+        Raw<TX, W> rx;
+        Raw<TI, W> re, ru, rh[CS_MAX_ORDER - 1];
+        rx.load(p.x, i);
+        re.load(p.ec, i);
+        if (p.eu) ru.load(p.eu, i);                          // (every branch on p is block-uniform; a tensor that is not loaded is not read either)
+        float x[W], e[W], u[W], o[W];
+        rx.unpack(x); re.unpack(e);
+        if (p.eu) { ru.unpack(u); cfg_combine<TI>(e, u, p.g); }
+        // the history is loaded after the combine: two trips to memory per iteration, not one as in the other steps.  It is the order this update
+        // has always had, and the one its HBM-bound figure is known to hold with: at 2.3 GB (fp32, 4096 x 16384, m = 4, CFG, 16-bit copy) 4 of 8
+        // processes ran 3 - 10 % below 5.85 TB/s with every load issued first, 2 of 20 with this order, on a machine where the figure drifts
 #pragma unroll
         for (int k = 0; k < CS_MAX_ORDER - 1; ++k)
-            if (k < p.m - 1) Io<TI>::load(p.hist[k], i, h[k]);
-        if (p.eps_out) Io<TI>::store(p.eps_out, i, e);
+            if (k < p.m - 1) rh[k].load(p.hist[k], i);
+        if (p.eps_out) store<TI, W>(p.eps_out, i, e);
 #pragma unroll
-        for (int j = 0; j < V; ++j) {
-            float hh[CS_MAX_ORDER - 1];
-#pragma unroll
-            for (int k = 0; k < CS_MAX_ORDER - 1; ++k) hh[k] = (k < p.m - 1) ? h[k][j] : 0.f;
-            o[j] = solve_one<TI, TO, EULER, false>(p, x[j], e[j], hh, c, sc0, sc1);
-        }
-        if constexpr (Io<TO>::VEC == V) {
-            Io<TO>::store(p.x_out, i, o);
-        } else {
-#pragma unroll
-            for (int j = 0; j < V; ++j) Io<TO>::store1(p.x_out, i + j, o[j]);
-        }
-        if (p.x_lp) store_lp<V>(p.x_lp, i, o, p.lp_bf16);        // (block-uniform) the 16-bit view of an fp32 state: what `x.to(model dtype)` would round the stored result to
+        for (int j = 0; j < W; ++j) o[j] = solve_one<TI, EULER>(p, x[j], e[j], rh, j, c, sc0, sc1);
+        store<TO, W>(p.x_out, i, o);
+        if (p.x_lp) store_lp<W>(p.x_lp, i, o, p.lp_bf16);
     }
-    // scalar tail (elems % V != 0): handled by the last block of each sample
-    if (blockIdx.x == 0) {
-        for (int64_t t = nvec * V + threadIdx.x; t < p.elems; t += blockDim.x) {
-            const int64_t i = base + t;
-            float x = p.x_f32 ? reinterpret_cast<const float*>(p.x)[i] : Io<TI>::load1(p.x, i), e = Io<TI>::load1(p.ec, i);
-            if (p.eu) { float u = Io<TI>::load1(p.eu, i); e = Io<TI>::round(u + p.g * (e - u)); }
-            float hh[CS_MAX_ORDER - 1];
-#pragma unroll
-            for (int k = 0; k < CS_MAX_ORDER - 1; ++k) hh[k] = (k < p.m - 1) ? Io<TI>::load1(p.hist[k], i) : 0.f;
-            if (p.eps_out) Io<TI>::store1(p.eps_out, i, e);
-            const float r = solve_one<TI, TO, EULER, false>(p, x, e, hh, c, sc0, sc1);
-            Io<TO>::store1(p.x_out, i, r);
-            if (p.x_lp) store_lp1(p.x_lp, i, r, p.lp_bf16);
-        }
-    }
-}
-
-template <bool EULER>
-int launch_step(const CsStepArgs* a, void* stream) {
-    if (!a) CS_FAIL(CS_E_ARG, "args is NULL");
-    if (a->B < 0 || a->elems < 0) CS_FAIL(CS_E_SHAPE, "negative shape");
-    const bool empty = (a->B == 0 || a->elems == 0);
-    if (!empty && (!a->x || !a->eps_text || !a->x_out)) CS_FAIL(CS_E_ARG, "x, eps_text and x_out are required");
-    if (a->order_dim < 1 || a->order_dim > CS_MAX_ORDER) CS_FAIL(CS_E_ARG, "order_dim %d out of range [1,%d]", a->order_dim, CS_MAX_ORDER);
-    if (a->scaler_dim < 0 || a->scaler_dim > 2) CS_FAIL(CS_E_UNSUPPORTED, "scaler_dim %d > 2 is not implemented (scheduler_ppo.py:280)", a->scaler_dim);
-    if (a->m < 1 || a->m > a->order_dim) CS_FAIL(CS_E_ARG, "history length m=%d not in [1, order_dim=%d]", a->m, a->order_dim);
-    if (empty) return CS_OK;
-    if ((a->m > 1 || a->scaler_dim > 0) && !a->actions) CS_FAIL(CS_E_ARG, "actions required when m > 1 or scaler_dim > 0");
-    if (a->actions && a->actions_stride < a->order_dim + a->scaler_dim - 1) CS_FAIL(CS_E_SHAPE, "actions_stride %d < order+scaler-1", a->actions_stride);
-    if (a->eps_uncond && !a->eps_out) CS_FAIL(CS_E_ARG, "eps_out is required with CFG (the combined eps is the history entry)");
-    for (int k = 0; k < a->m - 1; ++k)
-        if (!a->hist[k]) CS_FAIL(CS_E_ARG, "hist[%d] is NULL but m=%d", k, a->m);
-    StepParams p;
-    p.x = a->x; p.ec = a->eps_text; p.eu = a->eps_uncond; p.g = a->guidance;
-    for (int k = 0; k < CS_MAX_ORDER; ++k) p.hist[k] = a->hist[k];
-    p.m = a->m; p.order = a->order_dim; p.scaler = a->scaler_dim;
-    p.actions = a->actions; p.astride = a->actions_stride; p.elems = a->elems;
-    p.x_out = a->x_out; p.eps_out = a->eps_out;
-    p.sat = a->sqrt_at; p.s1mat = a->sqrt_1mat; p.sap = a->sqrt_ap; p.s1map = a->sqrt_1map;
-    p.vpred = a->v_prediction; p.dt = a->dt;
-    p.x_f32 = (a->x_is_f32 != 0 && a->io_dtype != CS_F32);
-    p.x_lp = a->x_out_lp; p.lp_bf16 = a->lp_dtype == CS_BF16;
-    if (a->x_out_lp && (a->out_dtype != CS_F32 || (a->lp_dtype != CS_F16 && a->lp_dtype != CS_BF16)))
-        CS_FAIL(CS_E_ARG, "x_out_lp is the 16-bit copy (lp_dtype CS_F16 or CS_BF16) of an fp32 result (out_dtype CS_F32)");
-    const int vec = (a->io_dtype == CS_F32) ? 4 : 8;
-    int64_t nvec = a->elems / vec;
-    int gx = (int)((nvec + 255) / 256);
-    // memory-bound: cap the grid at ~8 blocks per CU overall and grid-stride the rest
-    int cap = (2048 + a->B - 1) / a->B; if (cap < 1) cap = 1;
-    if (gx > cap) gx = cap; if (gx < 1) gx = 1;
-    dim3 grid(gx, a->B), block(256);
-    hipStream_t s = (hipStream_t)stream;
-#define LAUNCH(TI, TO) hipLaunchKernelGGL((lms_step_kernel<TI, TO, EULER>), grid, block, 0, s, p)
-    const int io = a->io_dtype, od = a->out_dtype;
-    if (io == CS_F32 && od == CS_F32) LAUNCH(float, float);
-    else if (io == CS_F16 && od == CS_F16) LAUNCH(f16, f16);
-    else if (io == CS_F16 && od == CS_F32) LAUNCH(f16, float);
-    else if (io == CS_BF16 && od == CS_BF16) LAUNCH(bf16_tag, bf16_tag);
-    else if (io == CS_BF16 && od == CS_F32) LAUNCH(bf16_tag, float);
-    else CS_FAIL(CS_E_DTYPE, "unsupported io/out dtype pair (%d,%d)", io, od);
-#undef LAUNCH
-    CS_CHECK_LAUNCH();
-    return CS_OK;
-}
+};
 
 // ---------------------------------------------------------------- Multistep DPM-Solver
 // Every variant (dpmsolver / dpmsolver++, epsilon / v prediction, first / second order, midpoint / heun) is the same linear update per
@@ -276,10 +223,8 @@ int launch_step(const CsStepArgs* a, void* stream) {
 struct DpmParams {
     const void* x; const void* ec; const void* eu; float g;
     const void* m1;
-    int64_t elems;
     void* x_out; void* m_out;
     float conv_x, conv_e, cx, c0, c1;
-    int x_f32;   // as StepParams::x_f32
     void* x_lp;  // as StepParams::x_lp
     int lp_bf16;
 };
@@ -290,113 +235,40 @@ __device__ __forceinline__ float dpm_one(const DpmParams& p, float x, float m0, 
     return r;
 }
 
-template <typename TI, typename TO>
-__global__ __launch_bounds__(256) void dpm_step_kernel(DpmParams p) {
-    constexpr int V = Io<TI>::VEC;
-    const int b = blockIdx.y;
-    const int64_t base = (int64_t)b * p.elems;
-    const int64_t nvec = p.elems / V;
-    for (int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; v < nvec; v += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t i = base + v * V;
-        float x[V], e[V], u[V], h[V], o[V];
-        if (p.x_f32) {   // block-uniform
+template <typename TI, typename TX, typename TO>
+struct DpmStep {
+    typedef DpmParams Params;
+    static constexpr int V = Io<TI>::VEC;
+    __device__ __forceinline__ DpmStep(const DpmParams&, int) {}
+    template <int W>
+    __device__ __forceinline__ void step(const DpmParams& p, int64_t i) const {
+        Raw<TX, W> rx;
+        Raw<TI, W> re, ru, r1;
+        rx.load(p.x, i);
+        re.load(p.ec, i);
+        if (p.eu) ru.load(p.eu, i);
+        if (p.m1) r1.load(p.m1, i);                          // (dpm_one reads m1 under the same condition)
+        float x[W], e[W], u[W], h[W], o[W];
+        rx.unpack(x); re.unpack(e);
+        if (p.eu) { ru.unpack(u); cfg_combine<TI>(e, u, p.g); }
+        if (p.m1) r1.unpack(h);
+        convert_output<TI>(e, x, p.conv_x, p.conv_e);
+        if (p.m_out) store<TI, W>(p.m_out, i, e);
 #pragma unroll
-            for (int j = 0; j < V; ++j) x[j] = reinterpret_cast<const float*>(p.x)[i + j];
-        } else {
-            Io<TI>::load(p.x, i, x);
-        }
-        Io<TI>::load(p.ec, i, e);
-        if (p.eu) {
-            Io<TI>::load(p.eu, i, u);
-#pragma unroll
-            for (int j = 0; j < V; ++j) e[j] = Io<TI>::round(u[j] + p.g * (e[j] - u[j]));
-        }
-#pragma unroll
-        for (int j = 0; j < V; ++j) e[j] = Io<TI>::round(p.conv_x * x[j] + p.conv_e * e[j]);
-        if (p.m1) {
-            Io<TI>::load(p.m1, i, h);
-        } else {
-#pragma unroll
-            for (int j = 0; j < V; ++j) h[j] = 0.f;
-        }
-        if (p.m_out) Io<TI>::store(p.m_out, i, e);
-#pragma unroll
-        for (int j = 0; j < V; ++j) o[j] = dpm_one(p, x[j], e[j], h[j]);
-        if constexpr (Io<TO>::VEC == V) {
-            Io<TO>::store(p.x_out, i, o);
-        } else {
-#pragma unroll
-            for (int j = 0; j < V; ++j) Io<TO>::store1(p.x_out, i + j, o[j]);
-        }
-        if (p.x_lp) store_lp<V>(p.x_lp, i, o, p.lp_bf16);
+        for (int j = 0; j < W; ++j) o[j] = dpm_one(p, x[j], e[j], h[j]);
+        store<TO, W>(p.x_out, i, o);
+        if (p.x_lp) store_lp<W>(p.x_lp, i, o, p.lp_bf16);
     }
-    // scalar tail (elems % V != 0): handled by the first block of each sample
-    if (blockIdx.x == 0) {
-        for (int64_t t = nvec * V + threadIdx.x; t < p.elems; t += blockDim.x) {
-            const int64_t i = base + t;
-            const float x = p.x_f32 ? reinterpret_cast<const float*>(p.x)[i] : Io<TI>::load1(p.x, i);
-            float e = Io<TI>::load1(p.ec, i);
-            if (p.eu) { float u = Io<TI>::load1(p.eu, i); e = Io<TI>::round(u + p.g * (e - u)); }
-            e = Io<TI>::round(p.conv_x * x + p.conv_e * e);
-            const float h = p.m1 ? Io<TI>::load1(p.m1, i) : 0.f;
-            if (p.m_out) Io<TI>::store1(p.m_out, i, e);
-            const float r = dpm_one(p, x, e, h);
-            Io<TO>::store1(p.x_out, i, r);
-            if (p.x_lp) store_lp1(p.x_lp, i, r, p.lp_bf16);
-        }
-    }
-}
-
-int launch_dpm_step(const CsDpmStepArgs* a, void* stream) {
-    if (!a) CS_FAIL(CS_E_ARG, "args is NULL");
-    if (a->B < 0 || a->elems < 0) CS_FAIL(CS_E_SHAPE, "negative shape");
-    const bool empty = (a->B == 0 || a->elems == 0);
-    if (!empty && (!a->x || !a->eps_text || !a->x_out)) CS_FAIL(CS_E_ARG, "x, eps_text and x_out are required");
-    if (a->x_out_lp && (a->out_dtype != CS_F32 || (a->lp_dtype != CS_F16 && a->lp_dtype != CS_BF16)))
-        CS_FAIL(CS_E_ARG, "x_out_lp is the 16-bit copy (lp_dtype CS_F16 or CS_BF16) of an fp32 result (out_dtype CS_F32)");
-    const int io = a->io_dtype, od = a->out_dtype;
-    const bool pair_ok = (io == CS_F32 && od == CS_F32) || (io == CS_F16 && (od == CS_F16 || od == CS_F32)) || (io == CS_BF16 && (od == CS_BF16 || od == CS_F32));
-    if (!pair_ok) CS_FAIL(CS_E_DTYPE, "unsupported io/out dtype pair (%d,%d)", io, od);
-    if (a->x_is_f32 && io != CS_F32 && od != CS_F32) CS_FAIL(CS_E_DTYPE, "an fp32 sample gives an fp32 result (out_dtype %d)", od);
-    if (empty) return CS_OK;
-    const bool identity = (a->conv_x == 0.f && a->conv_e == 1.f);
-    if ((a->eps_uncond || !identity) && !a->m_out)
-        CS_FAIL(CS_E_ARG, "m_out is required with CFG or a model-output conversion (the converted output is the history entry)");
-    DpmParams p;
-    p.x = a->x; p.ec = a->eps_text; p.eu = a->eps_uncond; p.g = a->guidance;
-    p.m1 = a->m_prev; p.elems = a->elems;
-    p.x_out = a->x_out; p.m_out = a->m_out;
-    p.conv_x = a->conv_x; p.conv_e = a->conv_e; p.cx = a->cx; p.c0 = a->c0; p.c1 = a->c1;
-    p.x_f32 = (a->x_is_f32 != 0 && io != CS_F32);
-    p.x_lp = a->x_out_lp; p.lp_bf16 = a->lp_dtype == CS_BF16;
-    const int vec = (io == CS_F32) ? 4 : 8;
-    int64_t nvec = a->elems / vec;
-    int gx = (int)((nvec + 255) / 256);
-    // the same capped grid as launch_step: ~8 blocks per CU overall, grid-stride the rest
-    int cap = (2048 + a->B - 1) / a->B; if (cap < 1) cap = 1;
-    if (gx > cap) gx = cap; if (gx < 1) gx = 1;
-    dim3 grid(gx, a->B), block(256);
-    hipStream_t s = (hipStream_t)stream;
-#define LAUNCH(TI, TO) hipLaunchKernelGGL((dpm_step_kernel<TI, TO>), grid, block, 0, s, p)
-    if (io == CS_F32) LAUNCH(float, float);
-    else if (io == CS_F16 && od == CS_F16) LAUNCH(f16, f16);
-    else if (io == CS_F16) LAUNCH(f16, float);
-    else if (od == CS_BF16) LAUNCH(bf16_tag, bf16_tag);
-    else LAUNCH(bf16_tag, float);
-#undef LAUNCH
-    CS_CHECK_LAUNCH();
-    return CS_OK;
-}
+};
 
 // ---------------------------------------------------------------- UniPC (bh1 / bh2, orders 1 and 2, x0 prediction)
 // One step of UniPC is the corrector of the PREVIOUS update (it needs this step's model output) followed by this step's predictor.  Both are
 // linear in the same tensors, so the step is one pass: the variant lives in nine host scalars (scheduling_unipc.py).  x is the predicted sample
 // (the previous predictor's output), x_last the previous step's corrected sample, m0 / m1 the converted outputs of the two previous steps.
-// As in fm_step_kernel there is no per-sample coefficient: the batch is one flat range and the vector body stays 16-byte aligned whatever elems is.
+// The state (x, x_last, x_c, x_next) has the result's dtype TO: launch_unipc_step checks it.
 struct UnipcParams {
     const void* x; const void* ec; const void* eu; float g;
     const void* x_last; const void* m0; const void* m1;
-    int64_t total;   // B * elems
     void* x_out; void* m_out; void* x_last_out;
     float conv_x, conv_e, a_x, a_0, a_1, a_n, p_x, p_0, p_1;
     int corr;    // apply the corrector (else x_c = x)
@@ -413,93 +285,209 @@ __device__ __forceinline__ void unipc_one(const UnipcParams& p, float x, float x
     xn = p.p_x * xc + p.p_0 * mn + p.p_1 * m0;
 }
 
-// V values of the state (x, x_last, x_c, x_next): the io vector, or two fp32 vectors beside 16-bit model outputs
-template <typename TS, int V>
-struct StateRaw {
-    static constexpr int N = V / Io<TS>::VEC;
-    static_assert(N == 1 || (V == 8 && Io<TS>::VEC == 4), "an fp32 state beside 8-wide 16-bit vectors");
-    typename Io<TS>::vec_t r[N];
-    __device__ void load(const void* p, int64_t i) {
+template <typename TI, typename TO>
+struct UnipcStep {
+    typedef UnipcParams Params;
+    static constexpr int V = Io<TI>::VEC;
+    __device__ __forceinline__ UnipcStep(const UnipcParams&, int) {}
+    template <int W>
+    __device__ __forceinline__ void step(const UnipcParams& p, int64_t i) const {
+        Raw<TO, W> rx, rxl = {};
+        Raw<TI, W> re, ru, r0 = {}, r1 = {};                 // (unipc_one takes a history value that is not read as zero)
+        rx.load(p.x, i);
+        re.load(p.ec, i);
+        if (p.eu) ru.load(p.eu, i);
+        if (p.corr) rxl.load(p.x_last, i);
+        if (p.m0) r0.load(p.m0, i);
+        if (p.m1) r1.load(p.m1, i);
+        float x[W], xl[W], e[W], u[W], h0[W], h1[W], oc[W], on[W];
+        rx.unpack(x); rxl.unpack(xl); re.unpack(e); r0.unpack(h0); r1.unpack(h1);
+        if (p.eu) { ru.unpack(u); cfg_combine<TI>(e, u, p.g); }
+        convert_output<TI>(e, x, p.conv_x, p.conv_e);
 #pragma unroll
-        for (int k = 0; k < N; ++k) r[k] = Io<TS>::load_raw(p, i + k * Io<TS>::VEC);
-    }
-    __device__ void unpack(float (&o)[V]) const {
-#pragma unroll
-        for (int k = 0; k < N; ++k) Io<TS>::unpack(r[k], o + k * Io<TS>::VEC);
+        for (int j = 0; j < W; ++j) unipc_one<TO>(p, x[j], xl[j], e[j], h0[j], h1[j], oc[j], on[j]);
+        store<TI, W>(p.m_out, i, e);
+        if (p.x_last_out) store<TO, W>(p.x_last_out, i, oc);
+        store<TO, W>(p.x_out, i, on);
+        if (p.x_lp) store_lp<W>(p.x_lp, i, on, p.lp_bf16);
     }
 };
-template <typename TS, int V>
-__device__ __forceinline__ void store_state(void* p, int64_t i, const float (&o)[V]) {
-    if constexpr (Io<TS>::VEC == V) {
-        Io<TS>::store(p, i, o);
-    } else {
-        const float a[4] = {o[0], o[1], o[2], o[3]}, b[4] = {o[4], o[5], o[6], o[7]};
-        Io<TS>::store(p, i, a); Io<TS>::store(p, i + 4, b);
-    }
+
+// ---------------------------------------------------------------- flow-matching baselines (edit_ppo/scheduler_fm.py:405-482)
+// Every branch of the Euler / Heun / dpm-solver / multistep step is x' = cast_out(x_base + c * w) with w = v2 or v1 + v2; which base, whether
+// v1 is read and the scalar c are decided on the host (scheduling_fm.py).  c is a 0-d fp32 tensor in the reference, so with a 16-bit model
+// output `v1 + v2` and `c * w` are 16-bit ops (c cast to the model dtype, each result rounded to it) before the fp32 add -- the m == 1 form
+// of solve_one.
+struct FmParams { const void* x; const void* v2; const void* v1; float c; void* x_out; };
+
+template <typename TI>
+__device__ __forceinline__ float fm_one(const FmParams& p, float x, float v2, float v1) {
+    const float w = p.v1 ? Io<TI>::round(v1 + v2) : v2;
+    return x + Io<TI>::round(Io<TI>::round(p.c) * w);
 }
 
-template <typename TI, typename TO>
-__global__ __launch_bounds__(256) void unipc_step_kernel(UnipcParams p) {
-    constexpr int V = Io<TI>::VEC;
-    const int64_t nvec = p.total / V;
-    for (int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; v < nvec; v += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t i = v * V;
-        // every load is issued, as raw vectors, before the first value is converted (the branches are block-uniform): one round trip to memory per iteration
-        StateRaw<TO, V> rx, rxl = {};                 // (the state has the result's dtype: launch_unipc_step checks it)
-        typename Io<TI>::vec_t re, ru = {}, r0 = {}, r1 = {};
+template <typename TI, typename TX, typename TO>
+struct FmStep {
+    typedef FmParams Params;
+    static constexpr int V = Io<TI>::VEC;
+    __device__ __forceinline__ FmStep(const FmParams&, int) {}
+    template <int W>
+    __device__ __forceinline__ void step(const FmParams& p, int64_t i) const {
+        Raw<TX, W> rx;
+        Raw<TI, W> r2, r1;
         rx.load(p.x, i);
-        re = Io<TI>::load_raw(p.ec, i);
-        if (p.eu) ru = Io<TI>::load_raw(p.eu, i);
-        if (p.corr) rxl.load(p.x_last, i);
-        if (p.m0) r0 = Io<TI>::load_raw(p.m0, i);
-        if (p.m1) r1 = Io<TI>::load_raw(p.m1, i);
-        float x[V], xl[V], e[V], u[V], h0[V], h1[V], oc[V], on[V];
-        rx.unpack(x); rxl.unpack(xl);
-        Io<TI>::unpack(re, e); Io<TI>::unpack(ru, u); Io<TI>::unpack(r0, h0); Io<TI>::unpack(r1, h1);
-        if (p.eu) {
+        r2.load(p.v2, i);
+        if (p.v1) r1.load(p.v1, i);                          // (fm_one reads v1 under the same condition)
+        float x[W], e[W], h[W], o[W];
+        rx.unpack(x); r2.unpack(e);
+        if (p.v1) r1.unpack(h);
 #pragma unroll
-            for (int j = 0; j < V; ++j) e[j] = Io<TI>::round(u[j] + p.g * (e[j] - u[j]));
-        }
-#pragma unroll
-        for (int j = 0; j < V; ++j) {
-            e[j] = Io<TI>::round(p.conv_x * x[j] + p.conv_e * e[j]);
-            unipc_one<TO>(p, x[j], xl[j], e[j], h0[j], h1[j], oc[j], on[j]);
-        }
-        Io<TI>::store(p.m_out, i, e);
-        if (p.x_last_out) store_state<TO, V>(p.x_last_out, i, oc);
-        store_state<TO, V>(p.x_out, i, on);
-        if (p.x_lp) store_lp<V>(p.x_lp, i, on, p.lp_bf16);
+        for (int j = 0; j < W; ++j) o[j] = fm_one<TI>(p, x[j], e[j], h[j]);
+        store<TO, W>(p.x_out, i, o);
     }
-    // scalar tail (total % V != 0): handled by the first block
-    if (blockIdx.x == 0) {
-        for (int64_t i = nvec * V + threadIdx.x; i < p.total; i += blockDim.x) {
-            const float x = Io<TO>::load1(p.x, i);
-            const float xl = p.corr ? Io<TO>::load1(p.x_last, i) : 0.f;
-            float e = Io<TI>::load1(p.ec, i);
-            if (p.eu) { float u = Io<TI>::load1(p.eu, i); e = Io<TI>::round(u + p.g * (e - u)); }
-            e = Io<TI>::round(p.conv_x * x + p.conv_e * e);
-            const float h0 = p.m0 ? Io<TI>::load1(p.m0, i) : 0.f;
-            const float h1 = p.m1 ? Io<TI>::load1(p.m1, i) : 0.f;
-            Io<TI>::store1(p.m_out, i, e);
-            float xc, xn;
-            unipc_one<TO>(p, x, xl, e, h0, h1, xc, xn);
-            if (p.x_last_out) Io<TO>::store1(p.x_last_out, i, xc);
-            Io<TO>::store1(p.x_out, i, xn);
-            if (p.x_lp) store_lp1(p.x_lp, i, xn, p.lp_bf16);
-        }
-    }
+};
+
+// ---------------------------------------------------------------- true classifier-free guidance (edit_ppo/pipeline.py:1115)
+// out = cast_out(neg + scale * (pos - neg)): the value rounded ONCE to the output dtype (the rule of cfg_combine), not the reference's
+// three 16-bit ops.  The three fp32 operations are carried with their rounding errors (two-sum for the difference and the sum, an fma for the product's
+// error), so what is rounded at the end is the exact value to ~2^-45: where 4 pos and 3 neg cancel, the plain fp32 expression is off by several units of an
+// fp32 -- or of a subnormal fp16 -- result.  Memory-bound: the ~20 flops per element are free.
+__device__ __forceinline__ float true_cfg_one(float p, float n, float s) {
+    const float d = p - n, db = d - p, de = (p - (d - db)) + (-n - db);          // d + de = p - n
+    const float m = s * d, me = __builtin_fmaf(s, d, -m);                        // m + me = s * d
+    const float r = n + m, rb = r - n, re = (n - (r - rb)) + (m - rb);           // r + re = n + m
+    const float c = re + (me + s * de);
+    return fabsf(c) < INFINITY ? r + c : r;                                      // (inf / NaN operands: the plain expression's result)
 }
 
-int launch_unipc_step(const CsUnipcStepArgs* a, void* stream) {
+struct CfgParams { const void* pos; const void* neg; void* out; float scale; };
+
+// V elements per lane: 8 with a 16-bit output (one 16-byte store; fp32 inputs as two 16-byte loads each), 4 for fp32 -> fp32.  Every lane reads its
+// elements before it writes them and the vector body and the tail cover disjoint ranges, so out may be pos or neg when the element sizes are equal.
+template <typename TX, typename TO>
+struct TrueCfg {
+    typedef CfgParams Params;
+    static constexpr int V = Io<TO>::VEC;
+    __device__ __forceinline__ TrueCfg(const CfgParams&, int) {}
+    template <int W>
+    __device__ __forceinline__ void step(const CfgParams& p, int64_t i) const {
+        Raw<TX, W> ra, rb;
+        ra.load(p.pos, i);
+        rb.load(p.neg, i);
+        float a[W], b[W], o[W];
+        ra.unpack(a); rb.unpack(b);
+#pragma unroll
+        for (int j = 0; j < W; ++j) o[j] = true_cfg_one(a[j], b[j], p.scale);
+        store<TO, W>(p.out, i, o);
+    }
+};
+
+// ---------------------------------------------------------------- launchers
+template <typename T> struct Tag { typedef T type; };
+#define TYPE_OF(tag) typename decltype(tag)::type
+
+// the one dtype ladder: f(Tag<T>{}) for a dtype code
+template <typename F>
+int with_dtype(int code, F&& f) {
+    if (code == CS_F32) return f(Tag<float>{});
+    if (code == CS_F16) return f(Tag<f16>{});
+    if (code == CS_BF16) return f(Tag<bf16_tag>{});
+    CS_FAIL(CS_E_DTYPE, "bad dtype %d", code);
+}
+// f(TI, TX, TO) of an update: the sample and the result have the model outputs' dtype io, or are fp32 beside 16-bit model outputs
+template <typename F>
+int with_step_dtypes(int io, bool x_f32, bool out_f32, F&& f) {
+    return with_dtype(io, [&](auto ti) {
+        const Tag<float> f32;
+        if (x_f32) return out_f32 ? f(ti, f32, f32) : f(ti, f32, ti);
+        return out_f32 ? f(ti, ti, f32) : f(ti, ti, ti);
+    });
+}
+
+// what every update entry point refuses in the same words.  *empty: nothing to launch -- the entry point returns CS_OK for it once its own
+// shape-independent checks have passed.
+template <typename A>
+int refuse_common(const A* a, bool* empty) {
     if (!a) CS_FAIL(CS_E_ARG, "args is NULL");
     if (a->B < 0 || a->elems < 0) CS_FAIL(CS_E_SHAPE, "negative shape");
-    const bool empty = (a->B == 0 || a->elems == 0);
-    if (!empty && (!a->x || !a->eps_text || !a->x_out || !a->m_out)) CS_FAIL(CS_E_ARG, "x, eps_text, x_out and m_out are required");
-    if (a->x_out_lp && (a->out_dtype != CS_F32 || (a->lp_dtype != CS_F16 && a->lp_dtype != CS_BF16)))
-        CS_FAIL(CS_E_ARG, "x_out_lp is the 16-bit copy (lp_dtype CS_F16 or CS_BF16) of an fp32 result (out_dtype CS_F32)");
+    if constexpr (!std::is_same<A, CsFmStepArgs>::value)      // (the fm step writes no 16-bit copy)
+        if (a->x_out_lp && (a->out_dtype != CS_F32 || (a->lp_dtype != CS_F16 && a->lp_dtype != CS_BF16)))
+            CS_FAIL(CS_E_ARG, "x_out_lp is the 16-bit copy (lp_dtype CS_F16 or CS_BF16) of an fp32 result (out_dtype CS_F32)");
     const int io = a->io_dtype, od = a->out_dtype;
     const bool pair_ok = (io == CS_F32 && od == CS_F32) || (io == CS_F16 && (od == CS_F16 || od == CS_F32)) || (io == CS_BF16 && (od == CS_BF16 || od == CS_F32));
     if (!pair_ok) CS_FAIL(CS_E_DTYPE, "unsupported io/out dtype pair (%d,%d)", io, od);
+    *empty = (a->B == 0 || a->elems == 0);
+    return CS_OK;
+}
+// x_is_f32 of the args structs: an fp32 sample beside 16-bit model outputs
+template <typename A>
+bool x_f32(const A* a) { return a->x_is_f32 != 0 && a->io_dtype != CS_F32; }
+
+// memory-bound: cap the grid at ~8 blocks per CU overall (2048 blocks over the nb ranges) and grid-stride the rest
+template <typename F>
+int launch_stream(const typename F::Params& p, int nb, int64_t n, void* stream) {
+    int64_t gx = (n / F::V + 255) / 256;
+    int cap = (2048 + nb - 1) / nb; if (cap < 1) cap = 1;
+    if (gx > cap) gx = cap; if (gx < 1) gx = 1;
+    hipLaunchKernelGGL(stream_kernel<F>, dim3((unsigned)gx, nb), dim3(256), 0, (hipStream_t)stream, p, n);
+    CS_CHECK_LAUNCH();
+    return CS_OK;
+}
+
+template <bool EULER>
+int launch_step(const CsStepArgs* a, void* stream) {
+    bool empty;
+    if (int rc = refuse_common(a, &empty)) return rc;
+    if (!empty && (!a->x || !a->eps_text || !a->x_out)) CS_FAIL(CS_E_ARG, "x, eps_text and x_out are required");
+    if (a->order_dim < 1 || a->order_dim > CS_MAX_ORDER) CS_FAIL(CS_E_ARG, "order_dim %d out of range [1,%d]", a->order_dim, CS_MAX_ORDER);
+    if (a->scaler_dim < 0 || a->scaler_dim > 2) CS_FAIL(CS_E_UNSUPPORTED, "scaler_dim %d > 2 is not implemented (scheduler_ppo.py:280)", a->scaler_dim);
+    if (a->m < 1 || a->m > a->order_dim) CS_FAIL(CS_E_ARG, "history length m=%d not in [1, order_dim=%d]", a->m, a->order_dim);
+    if (empty) return CS_OK;
+    if ((a->m > 1 || a->scaler_dim > 0) && !a->actions) CS_FAIL(CS_E_ARG, "actions required when m > 1 or scaler_dim > 0");
+    if (a->actions && a->actions_stride < a->order_dim + a->scaler_dim - 1) CS_FAIL(CS_E_SHAPE, "actions_stride %d < order+scaler-1", a->actions_stride);
+    if (a->eps_uncond && !a->eps_out) CS_FAIL(CS_E_ARG, "eps_out is required with CFG (the combined eps is the history entry)");
+    for (int k = 0; k < a->m - 1; ++k)
+        if (!a->hist[k]) CS_FAIL(CS_E_ARG, "hist[%d] is NULL but m=%d", k, a->m);
+    StepParams p;
+    p.x = a->x; p.ec = a->eps_text; p.eu = a->eps_uncond; p.g = a->guidance;
+    for (int k = 0; k < CS_MAX_ORDER; ++k) p.hist[k] = a->hist[k];
+    p.m = a->m; p.order = a->order_dim; p.scaler = a->scaler_dim;
+    p.actions = a->actions; p.astride = a->actions_stride;
+    p.x_out = a->x_out; p.eps_out = a->eps_out;
+    p.sat = a->sqrt_at; p.s1mat = a->sqrt_1mat; p.sap = a->sqrt_ap; p.s1map = a->sqrt_1map;
+    p.vpred = a->v_prediction; p.dt = a->dt;
+    p.x_lp = a->x_out_lp; p.lp_bf16 = a->lp_dtype == CS_BF16;
+    return with_step_dtypes(a->io_dtype, x_f32(a), a->out_dtype == CS_F32, [&](auto ti, auto tx, auto to) {
+        return launch_stream<LmsStep<TYPE_OF(ti), TYPE_OF(tx), TYPE_OF(to), EULER>>(p, a->B, a->elems, stream);
+    });
+}
+
+int launch_dpm_step(const CsDpmStepArgs* a, void* stream) {
+    bool empty;
+    if (int rc = refuse_common(a, &empty)) return rc;
+    if (!empty && (!a->x || !a->eps_text || !a->x_out)) CS_FAIL(CS_E_ARG, "x, eps_text and x_out are required");
+    if (x_f32(a) && a->out_dtype != CS_F32) CS_FAIL(CS_E_DTYPE, "an fp32 sample gives an fp32 result (out_dtype %d)", a->out_dtype);
+    if (empty) return CS_OK;
+    const bool identity = (a->conv_x == 0.f && a->conv_e == 1.f);
+    if ((a->eps_uncond || !identity) && !a->m_out)
+        CS_FAIL(CS_E_ARG, "m_out is required with CFG or a model-output conversion (the converted output is the history entry)");
+    DpmParams p;
+    p.x = a->x; p.ec = a->eps_text; p.eu = a->eps_uncond; p.g = a->guidance;
+    p.m1 = a->m_prev;
+    p.x_out = a->x_out; p.m_out = a->m_out;
+    p.conv_x = a->conv_x; p.conv_e = a->conv_e; p.cx = a->cx; p.c0 = a->c0; p.c1 = a->c1;
+    p.x_lp = a->x_out_lp; p.lp_bf16 = a->lp_dtype == CS_BF16;
+    // per sample like launch_step, so a ragged b * elems is accepted and no alignment is checked
+    return with_step_dtypes(a->io_dtype, x_f32(a), a->out_dtype == CS_F32, [&](auto ti, auto tx, auto to) {
+        return launch_stream<DpmStep<TYPE_OF(ti), TYPE_OF(tx), TYPE_OF(to)>>(p, a->B, a->elems, stream);
+    });
+}
+
+int launch_unipc_step(const CsUnipcStepArgs* a, void* stream) {
+    bool empty;
+    if (int rc = refuse_common(a, &empty)) return rc;
+    if (!empty && (!a->x || !a->eps_text || !a->x_out || !a->m_out)) CS_FAIL(CS_E_ARG, "x, eps_text, x_out and m_out are required");
+    const int io = a->io_dtype, od = a->out_dtype;
     if (a->x_is_f32 && io == CS_F32) CS_FAIL(CS_E_DTYPE, "x_is_f32 marks an fp32 sample beside 16-bit model outputs (io_dtype %d is fp32 already)", io);
     // x_c has the sample's dtype (it is the next step's x_last), so the result dtype is the sample's
     if ((a->x_is_f32 != 0) != (io != CS_F32 && od == CS_F32)) CS_FAIL(CS_E_DTYPE, "out_dtype %d is not the sample's dtype (x_is_f32 = %d, io_dtype %d)", od, a->x_is_f32, io);
@@ -514,7 +502,6 @@ int launch_unipc_step(const CsUnipcStepArgs* a, void* stream) {
     // a history tensor is read only where a coefficient uses it
     p.m0 = ((p.corr && a->a_0 != 0.f) || a->p_1 != 0.f) ? a->m_prev0 : nullptr;
     p.m1 = (p.corr && a->a_1 != 0.f) ? a->m_prev1 : nullptr;
-    p.total = (int64_t)a->B * a->elems;
     p.x_out = a->x_out; p.m_out = a->m_out; p.x_last_out = a->x_last_out;
     p.conv_x = a->conv_x; p.conv_e = a->conv_e;
     p.a_x = a->a_x; p.a_0 = a->a_0; p.a_1 = a->a_1; p.a_n = a->a_n; p.p_x = a->p_x; p.p_0 = a->p_0; p.p_1 = a->p_1;
@@ -523,164 +510,25 @@ int launch_unipc_step(const CsUnipcStepArgs* a, void* stream) {
     if ((((uintptr_t)a->eps_text | (uintptr_t)a->eps_uncond | (uintptr_t)p.m0 | (uintptr_t)p.m1 | (uintptr_t)a->m_out | (uintptr_t)a->x | (uintptr_t)p.x_last |
           (uintptr_t)a->x_out | (uintptr_t)a->x_last_out) & 15) || ((uintptr_t)a->x_out_lp & (a->x_is_f32 ? 15 : 7)))
         CS_FAIL(CS_E_ARG, "x, x_last, eps_*, m_prev*, m_out, x_out, x_last_out and x_out_lp must be 16-byte aligned");
-    const int vec = (io == CS_F32) ? 4 : 8;
-    int64_t nvec = p.total / vec;
-    // the same capped grid as launch_step: ~8 blocks per CU overall, grid-stride the rest
-    int64_t gx = (nvec + 255) / 256;
-    if (gx > 2048) gx = 2048; if (gx < 1) gx = 1;
-    dim3 grid((unsigned)gx), block(256);
-    hipStream_t s = (hipStream_t)stream;
-#define LAUNCH(TI, TO) hipLaunchKernelGGL((unipc_step_kernel<TI, TO>), grid, block, 0, s, p)
-    if (io == CS_F32) LAUNCH(float, float);
-    else if (io == CS_F16 && od == CS_F16) LAUNCH(f16, f16);
-    else if (io == CS_F16) LAUNCH(f16, float);
-    else if (od == CS_BF16) LAUNCH(bf16_tag, bf16_tag);
-    else LAUNCH(bf16_tag, float);
-#undef LAUNCH
-    CS_CHECK_LAUNCH();
-    return CS_OK;
-}
-
-// ---------------------------------------------------------------- flow-matching baselines (edit_ppo/scheduler_fm.py:405-482)
-// Every branch of the Euler / Heun / dpm-solver / multistep step is x' = cast_out(x_base + c * w) with w = v2 or v1 + v2; which base, whether
-// v1 is read and the scalar c are decided on the host (scheduling_fm.py).  c is a 0-d fp32 tensor in the reference, so with a 16-bit model
-// output `v1 + v2` and `c * w` are 16-bit ops (c cast to the model dtype, each result rounded to it) before the fp32 add -- the m == 1 form
-// of solve_one.
-struct FmParams {
-    const void* x; const void* v2; const void* v1; float c;
-    int64_t total;   // B * elems: no per-sample coefficient, so the batch is one flat range and the vector body stays 16-byte aligned whatever elems is
-    void* x_out;
-    int x_f32;   // as StepParams::x_f32
-};
-
-template <typename TI>
-__device__ __forceinline__ float fm_one(const FmParams& p, float x, float v2, float v1) {
-    const float w = p.v1 ? Io<TI>::round(v1 + v2) : v2;
-    return x + Io<TI>::round(Io<TI>::round(p.c) * w);
-}
-
-template <typename TI, typename TO>
-__global__ __launch_bounds__(256) void fm_step_kernel(FmParams p) {
-    constexpr int V = Io<TI>::VEC;
-    const int64_t nvec = p.total / V;
-    for (int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; v < nvec; v += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t i = v * V;
-        float x[V], e[V], h[V], o[V];
-        if (p.x_f32) {   // block-uniform
-#pragma unroll
-            for (int j = 0; j < V; ++j) x[j] = reinterpret_cast<const float*>(p.x)[i + j];
-        } else {
-            Io<TI>::load(p.x, i, x);
-        }
-        Io<TI>::load(p.v2, i, e);
-        if (p.v1) {
-            Io<TI>::load(p.v1, i, h);
-        } else {
-#pragma unroll
-            for (int j = 0; j < V; ++j) h[j] = 0.f;
-        }
-#pragma unroll
-        for (int j = 0; j < V; ++j) o[j] = fm_one<TI>(p, x[j], e[j], h[j]);
-        if constexpr (Io<TO>::VEC == V) {
-            Io<TO>::store(p.x_out, i, o);
-        } else {
-#pragma unroll
-            for (int j = 0; j < V; ++j) Io<TO>::store1(p.x_out, i + j, o[j]);
-        }
-    }
-    // scalar tail (total % V != 0): handled by the first block
-    if (blockIdx.x == 0) {
-        for (int64_t i = nvec * V + threadIdx.x; i < p.total; i += blockDim.x) {
-            const float x = p.x_f32 ? reinterpret_cast<const float*>(p.x)[i] : Io<TI>::load1(p.x, i);
-            const float h = p.v1 ? Io<TI>::load1(p.v1, i) : 0.f;
-            Io<TO>::store1(p.x_out, i, fm_one<TI>(p, x, Io<TI>::load1(p.v2, i), h));
-        }
-    }
+    return with_step_dtypes(io, false, od == CS_F32, [&](auto ti, auto, auto to) {      // (the sample's dtype is the result's: checked above)
+        return launch_stream<UnipcStep<TYPE_OF(ti), TYPE_OF(to)>>(p, 1, (int64_t)a->B * a->elems, stream);
+    });
 }
 
 int launch_fm_step(const CsFmStepArgs* a, void* stream) {
-    if (!a) CS_FAIL(CS_E_ARG, "args is NULL");
-    if (a->B < 0 || a->elems < 0) CS_FAIL(CS_E_SHAPE, "negative shape");
-    const bool empty = (a->B == 0 || a->elems == 0);
+    bool empty;
+    if (int rc = refuse_common(a, &empty)) return rc;
     if (!empty && (!a->x_base || !a->v2 || !a->x_out)) CS_FAIL(CS_E_ARG, "x_base, v2 and x_out are required");
-    const int io = a->io_dtype, od = a->out_dtype;
-    const bool pair_ok = (io == CS_F32 && od == CS_F32) || (io == CS_F16 && (od == CS_F16 || od == CS_F32)) || (io == CS_BF16 && (od == CS_BF16 || od == CS_F32));
-    if (!pair_ok) CS_FAIL(CS_E_DTYPE, "unsupported io/out dtype pair (%d,%d)", io, od);
     if (empty) return CS_OK;
-    FmParams p;
-    p.x = a->x_base; p.v2 = a->v2; p.v1 = a->v1; p.c = a->c; p.total = (int64_t)a->B * a->elems; p.x_out = a->x_out;
-    p.x_f32 = (a->x_is_f32 != 0 && io != CS_F32);
-    // one 16-byte load / store per lane and tensor (4 bytes per element of an fp32 base next to 16-bit outputs)
-    if ((((uintptr_t)a->v2 | (uintptr_t)a->v1) & 15) || ((uintptr_t)a->x_base & (p.x_f32 ? 3 : 15)) || ((uintptr_t)a->x_out & (io != CS_F32 && od == CS_F32 ? 3 : 15)))
+    const int io = a->io_dtype, od = a->out_dtype;
+    const FmParams p{a->x_base, a->v2, a->v1, a->c, a->x_out};
+    // 16-byte loads / stores on the model outputs; an fp32 base or result beside them needs its element's 4 bytes only (the hardware splits a
+    // 16-byte access that is not aligned, as it does for the samples of a ragged per-sample launch)
+    if ((((uintptr_t)a->v2 | (uintptr_t)a->v1) & 15) || ((uintptr_t)a->x_base & (x_f32(a) ? 3 : 15)) || ((uintptr_t)a->x_out & (io != CS_F32 && od == CS_F32 ? 3 : 15)))
         CS_FAIL(CS_E_ARG, "x_base, v1, v2 and x_out must be 16-byte aligned");
-    const int vec = (io == CS_F32) ? 4 : 8;
-    int64_t nvec = p.total / vec;
-    // the same capped grid as launch_step: ~8 blocks per CU overall, grid-stride the rest
-    int64_t gx = (nvec + 255) / 256;
-    if (gx > 2048) gx = 2048; if (gx < 1) gx = 1;
-    dim3 grid((unsigned)gx), block(256);
-    hipStream_t s = (hipStream_t)stream;
-#define LAUNCH(TI, TO) hipLaunchKernelGGL((fm_step_kernel<TI, TO>), grid, block, 0, s, p)
-    if (io == CS_F32) LAUNCH(float, float);
-    else if (io == CS_F16 && od == CS_F16) LAUNCH(f16, f16);
-    else if (io == CS_F16) LAUNCH(f16, float);
-    else if (od == CS_BF16) LAUNCH(bf16_tag, bf16_tag);
-    else LAUNCH(bf16_tag, float);
-#undef LAUNCH
-    CS_CHECK_LAUNCH();
-    return CS_OK;
-}
-
-// ---------------------------------------------------------------- true classifier-free guidance (edit_ppo/pipeline.py:1115)
-// out = cast_out(neg + scale * (pos - neg)): the value rounded ONCE to the output dtype (the rule of the CFG line of lms_step_kernel), not the reference's
-// three 16-bit ops.  The three fp32 operations are carried with their rounding errors (two-sum for the difference and the sum, an fma for the product's
-// error), so what is rounded at the end is the exact value to ~2^-45: where 4 pos and 3 neg cancel, the plain fp32 expression is off by several units of an
-// fp32 -- or of a subnormal fp16 -- result.  Memory-bound: the ~20 flops per element are free.
-__device__ __forceinline__ float true_cfg_one(float p, float n, float s) {
-    const float d = p - n, db = d - p, de = (p - (d - db)) + (-n - db);          // d + de = p - n
-    const float m = s * d, me = __builtin_fmaf(s, d, -m);                        // m + me = s * d
-    const float r = n + m, rb = r - n, re = (n - (r - rb)) + (m - rb);           // r + re = n + m
-    const float c = re + (me + s * de);
-    return fabsf(c) < INFINITY ? r + c : r;                                      // (inf / NaN operands: the plain expression's result)
-}
-
-struct CfgParams { const void* pos; const void* neg; void* out; float scale; int64_t n; int in_vec; };
-
-// V elements per lane: 8 with a 16-bit output (one 16-byte store; fp32 inputs as two 16-byte loads each), 4 for fp32 -> fp32.
-// in_vec == 0 (fp32 inputs of a mixed pair that are only 4-byte aligned): element loads.  Every lane reads its elements before it writes them and the
-// vector body and the tail cover disjoint ranges, so out may be pos or neg when the element sizes are equal.
-template <typename TI, typename TO>
-__global__ __launch_bounds__(256) void true_cfg_kernel(CfgParams p) {
-    constexpr int V = Io<TO>::VEC;
-    const int64_t nvec = p.n / V;
-    for (int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; v < nvec; v += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t i = v * V;
-        float a[V], b[V], o[V];
-        if constexpr (Io<TI>::VEC == V) {
-            Io<TI>::load(p.pos, i, a); Io<TI>::load(p.neg, i, b);
-        } else if (p.in_vec) {   // block-uniform
-            float t[4];
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                Io<float>::load(p.pos, i + 4 * h, t);
-#pragma unroll
-                for (int j = 0; j < 4; ++j) a[4 * h + j] = t[j];
-                Io<float>::load(p.neg, i + 4 * h, t);
-#pragma unroll
-                for (int j = 0; j < 4; ++j) b[4 * h + j] = t[j];
-            }
-        } else {
-#pragma unroll
-            for (int j = 0; j < V; ++j) { a[j] = Io<TI>::load1(p.pos, i + j); b[j] = Io<TI>::load1(p.neg, i + j); }
-        }
-#pragma unroll
-        for (int j = 0; j < V; ++j) o[j] = true_cfg_one(a[j], b[j], p.scale);
-        Io<TO>::store(p.out, i, o);
-    }
-    // scalar tail (n % V != 0): handled by the first block
-    if (blockIdx.x == 0)
-        for (int64_t i = nvec * V + threadIdx.x; i < p.n; i += blockDim.x)
-            Io<TO>::store1(p.out, i, true_cfg_one(Io<TI>::load1(p.pos, i), Io<TI>::load1(p.neg, i), p.scale));
+    return with_step_dtypes(io, x_f32(a), od == CS_F32, [&](auto ti, auto tx, auto to) {
+        return launch_stream<FmStep<TYPE_OF(ti), TYPE_OF(tx), TYPE_OF(to)>>(p, 1, (int64_t)a->B * a->elems, stream);
+    });
 }
 
 int launch_true_cfg(const void* pos, const void* neg, int in_dtype, float scale, void* out, int out_dtype, int64_t n, void* stream) {
@@ -695,22 +543,11 @@ int launch_true_cfg(const void* pos, const void* neg, int in_dtype, float scale,
     if ((((uintptr_t)pos | (uintptr_t)neg) & (mixed ? 3 : 15)) || ((uintptr_t)out & 15))
         CS_FAIL(CS_E_ARG, "pos, neg and out must be 16-byte aligned (fp32 inputs beside a 16-bit output: 4-byte)");
     if (mixed && (out == pos || out == neg)) CS_FAIL(CS_E_ARG, "out may alias pos or neg only when the element sizes are equal");
-    CfgParams p{pos, neg, out, scale, n, (((uintptr_t)pos | (uintptr_t)neg) & 15) == 0};
-    const int vec = out_dtype == CS_F32 ? 4 : 8;
-    // the same capped grid as launch_fm_step
-    int64_t gx = (n / vec + 255) / 256;
-    if (gx > 2048) gx = 2048; if (gx < 1) gx = 1;
-    dim3 grid((unsigned)gx), block(256);
-    hipStream_t s = (hipStream_t)stream;
-#define LAUNCH(TI, TO) hipLaunchKernelGGL((true_cfg_kernel<TI, TO>), grid, block, 0, s, p)
-    if (in_dtype == CS_F16) LAUNCH(f16, f16);
-    else if (in_dtype == CS_BF16) LAUNCH(bf16_tag, bf16_tag);
-    else if (out_dtype == CS_F32) LAUNCH(float, float);
-    else if (out_dtype == CS_F16) LAUNCH(float, f16);
-    else LAUNCH(float, bf16_tag);
-#undef LAUNCH
-    CS_CHECK_LAUNCH();
-    return CS_OK;
+    const CfgParams p{pos, neg, out, scale};
+    return with_dtype(out_dtype, [&](auto to) {
+        if (in_dtype == CS_F32) return launch_stream<TrueCfg<float, TYPE_OF(to)>>(p, 1, n, stream);
+        return launch_stream<TrueCfg<TYPE_OF(to), TYPE_OF(to)>>(p, 1, n, stream);
+    });
 }
 
 // ---------------------------------------------------------------- policy MLP
@@ -803,8 +640,29 @@ __global__ __launch_bounds__(1024) void factor_probs_kernel(CsFactorNet n, const
 struct HistPtrs { const void* p[CS_MAX_ORDER]; };
 
 // CFG form (eu != null): hist[0] is the TEXT branch and the newest history entry is the combined eps u + g (c - u), rounded to
-// the model dtype exactly as lms_step_kernel rounds it; it is formed on the fly and the blocks of feature 1 also write it to
+// the model dtype exactly as the update kernels round it (cfg_combine); it is formed on the fly and the blocks of feature 1 also write it to
 // eps_out (every launch has them, whatever m is), so the update kernel that follows takes it as an already combined eps.
+// W elements at t of a thread's three partial sums; hi == nullptr: feature i is not formed (i >= m), only the combined eps is written
+template <typename T, int W>
+__device__ __forceinline__ void cosine_acc(const void* h0, const void* hi, const void* eu, float g, void* eps_out, int64_t t, float& dot, float& na, float& nb) {
+    Raw<T, W> rc, ru, ra;
+    rc.load(h0, t);
+    if (eu) ru.load(eu, t);
+    if (hi) ra.load(hi, t);
+    float a[W], c[W], u[W];
+    rc.unpack(c);
+    if (eu) {
+        ru.unpack(u);
+        cfg_combine<T>(c, u, g);
+        if (eps_out) store<T, W>(eps_out, t, c);
+    }
+    if (hi) {
+        ra.unpack(a);
+#pragma unroll
+        for (int j = 0; j < W; ++j) { dot += a[j] * c[j]; na += a[j] * a[j]; nb += c[j] * c[j]; }
+    }
+}
+
 template <typename T>
 __global__ __launch_bounds__(256) void cosine_kernel(HistPtrs h, int m, int order, int64_t elems, float* out, const void* eu, float g, void* eps_out) {
     // grid (order-1, B): cos(hist[i], hist[0]), i = blockIdx.x + 1
@@ -815,31 +673,10 @@ __global__ __launch_bounds__(256) void cosine_kernel(HistPtrs h, int m, int orde
     if (i < m || writer) {
         constexpr int V = Io<T>::VEC;
         const int64_t base = (int64_t)b * elems, nvec = elems / V;
-        for (int64_t v = threadIdx.x; v < nvec; v += blockDim.x) {
-            float a[V], c[V];
-            Io<T>::load(h.p[0], base + v * V, c);
-            if (eu) {
-                float u[V];
-                Io<T>::load(eu, base + v * V, u);
-#pragma unroll
-                for (int j = 0; j < V; ++j) c[j] = Io<T>::round(u[j] + g * (c[j] - u[j]));
-                if (writer) Io<T>::store(eps_out, base + v * V, c);
-            }
-            if (i < m) {
-                Io<T>::load(h.p[i], base + v * V, a);
-#pragma unroll
-                for (int j = 0; j < V; ++j) { dot += a[j] * c[j]; na += a[j] * a[j]; nb += c[j] * c[j]; }
-            }
-        }
-        for (int64_t t = nvec * V + threadIdx.x; t < elems; t += blockDim.x) {
-            float c = Io<T>::load1(h.p[0], base + t);
-            if (eu) {
-                const float u = Io<T>::load1(eu, base + t);
-                c = Io<T>::round(u + g * (c - u));
-                if (writer) Io<T>::store1(eps_out, base + t, c);
-            }
-            if (i < m) { const float a = Io<T>::load1(h.p[i], base + t); dot += a * c; na += a * a; nb += c * c; }
-        }
+        const void* hi = i < m ? h.p[i] : nullptr;
+        void* eo = writer ? eps_out : nullptr;
+        for (int64_t v = threadIdx.x; v < nvec; v += blockDim.x) cosine_acc<T, V>(h.p[0], hi, eu, g, eo, base + v * V, dot, na, nb);
+        for (int64_t t = nvec * V + threadIdx.x; t < elems; t += blockDim.x) cosine_acc<T, 1>(h.p[0], hi, eu, g, eo, base + t, dot, na, nb);
     }
     dot = wave_sum(dot); na = wave_sum(na); nb = wave_sum(nb);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -906,6 +743,16 @@ __global__ void masks_kernel(int B, int A, int m, int order, float* masks) {
     masks[t] = (a >= m - 1 && a < order - 1) ? 0.f : 1.f;
 }
 
+// W elements of plane k of the stacked history: a copy of hist[k], zeros where src == nullptr (k >= m)
+template <typename T, int W>
+__device__ __forceinline__ void stack_copy(const void* src, int64_t s, void* out, int64_t d) {
+    Raw<T, W> r = {};
+    if (src) r.load(src, s);
+    float a[W];
+    r.unpack(a);
+    store<T, W>(out, d, a);
+}
+
 template <typename T>
 __global__ __launch_bounds__(256) void stack_kernel(HistPtrs h, int m, int order, int64_t elems, void* out) {
     // grid (chunks, order, B)
@@ -913,18 +760,11 @@ __global__ __launch_bounds__(256) void stack_kernel(HistPtrs h, int m, int order
     constexpr int V = Io<T>::VEC;
     const int64_t nvec = elems / V;
     const int64_t src = (int64_t)b * elems, dst = ((int64_t)b * order + k) * elems;
-    for (int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; v < nvec; v += (int64_t)gridDim.x * blockDim.x) {
-        float a[V];
-        if (k < m) Io<T>::load(h.p[k], src + v * V, a);
-        else {
-#pragma unroll
-            for (int j = 0; j < V; ++j) a[j] = 0.f;
-        }
-        Io<T>::store(out, dst + v * V, a);
-    }
+    const void* hk = k < m ? h.p[k] : nullptr;
+    for (int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; v < nvec; v += (int64_t)gridDim.x * blockDim.x)
+        stack_copy<T, V>(hk, src + v * V, out, dst + v * V);
     if (blockIdx.x == 0)
-        for (int64_t t = nvec * V + threadIdx.x; t < elems; t += blockDim.x)
-            Io<T>::store1(out, dst + t, k < m ? Io<T>::load1(h.p[k], src + t) : 0.f);
+        for (int64_t t = nvec * V + threadIdx.x; t < elems; t += blockDim.x) stack_copy<T, 1>(hk, src + t, out, dst + t);
 }
 
 }  // namespace
@@ -975,12 +815,11 @@ int cs_cosine_features_cfg(const void* const* hist, int m, int order, int B, int
     for (int k = 0; k < m; ++k) if (!h.p[k]) CS_FAIL(CS_E_ARG, "hist[%d] is NULL", k);
     dim3 grid(order - 1, B), block(256);
     hipStream_t s = (hipStream_t)stream;
-    if (dtype == CS_F32) hipLaunchKernelGGL(cosine_kernel<float>, grid, block, 0, s, h, m, order, elems, out, eps_uncond, guidance, eps_out);
-    else if (dtype == CS_F16) hipLaunchKernelGGL(cosine_kernel<f16>, grid, block, 0, s, h, m, order, elems, out, eps_uncond, guidance, eps_out);
-    else if (dtype == CS_BF16) hipLaunchKernelGGL(cosine_kernel<bf16_tag>, grid, block, 0, s, h, m, order, elems, out, eps_uncond, guidance, eps_out);
-    else CS_FAIL(CS_E_DTYPE, "bad dtype %d", dtype);
-    CS_CHECK_LAUNCH();
-    return CS_OK;
+    return with_dtype(dtype, [&](auto t) -> int {
+        hipLaunchKernelGGL(cosine_kernel<TYPE_OF(t)>, grid, block, 0, s, h, m, order, elems, out, eps_uncond, guidance, eps_out);
+        CS_CHECK_LAUNCH();
+        return CS_OK;
+    });
 }
 
 int cs_cosine_features(const void* const* hist, int m, int order, int B, int64_t elems, int dtype, float* out, void* stream) {
@@ -1041,12 +880,11 @@ int cs_stack_history(const void* const* hist, int m, int order, int B, int64_t e
     int gx = (int)((elems / vec + 255) / 256); if (gx < 1) gx = 1; if (gx > 64) gx = 64;
     dim3 grid(gx, order, B), block(256);
     hipStream_t s = (hipStream_t)stream;
-    if (dtype == CS_F32) hipLaunchKernelGGL(stack_kernel<float>, grid, block, 0, s, h, m, order, elems, out);
-    else if (dtype == CS_F16) hipLaunchKernelGGL(stack_kernel<f16>, grid, block, 0, s, h, m, order, elems, out);
-    else if (dtype == CS_BF16) hipLaunchKernelGGL(stack_kernel<bf16_tag>, grid, block, 0, s, h, m, order, elems, out);
-    else CS_FAIL(CS_E_DTYPE, "bad dtype %d", dtype);
-    CS_CHECK_LAUNCH();
-    return CS_OK;
+    return with_dtype(dtype, [&](auto t) -> int {
+        hipLaunchKernelGGL(stack_kernel<TYPE_OF(t)>, grid, block, 0, s, h, m, order, elems, out);
+        CS_CHECK_LAUNCH();
+        return CS_OK;
+    });
 }
 
 }  // extern "C"

@@ -24,7 +24,7 @@ import torch
 from . import _lib as L
 from . import tables
 from ._scheduler_base import ConfigMixin, KARRAS_COMPATIBLES, SchedulerMixin, register_to_config
-from .scheduling_ppo import SolverOutput
+from .scheduling_ppo import SolverOutput, fill_cfg, fill_io, result_tensor, step_inputs
 
 # what the two reference call sites resolve to on SD1.5's scheduler_config.json (from memory, see the module docstring)
 SD15_MULTISTEP_DPM_KWARGS = dict(beta_start=0.00085, beta_end=0.012, beta_schedule="scaled_linear", steps_offset=1,
@@ -110,6 +110,34 @@ class SigmaGridMixin:
         if len(idx) == 0:
             raise ValueError(f"timestep {int(timestep)} is not on the grid of set_timesteps({self.num_inference_steps})")
         return int(idx[1 if len(idx) > 1 else 0])
+
+    def _begin_step(self, model_output, timestep, sample):
+        """what ``step`` checks and normalises before it plans the update: -> (model_output, sample, step index), ``DDIMBaselineScheduler.step``'s
+        dtype rules"""
+        if self.num_inference_steps is None:
+            raise ValueError("Number of inference steps is 'None'. Call 'set_timesteps' first.")
+        model_output, sample = step_inputs(model_output, sample, self.prev_sample_dtype)
+        if sample.shape != model_output.shape:
+            raise ValueError(f"sample {tuple(sample.shape)} and model_output {tuple(model_output.shape)} differ in shape")
+        if self._step_index is None:
+            self._step_index = self._init_step_index(timestep)
+        i = self._step_index
+        if i >= self.num_inference_steps:
+            raise ValueError(f"step {i} is past the {self.num_inference_steps} steps of set_timesteps")
+        return model_output, sample, i
+
+    @staticmethod
+    def _checked_eps_uncond(eps_uncond, model_output):
+        if eps_uncond is not None:
+            eps_uncond = L.require_cuda(eps_uncond, "eps_uncond").contiguous()
+            if eps_uncond.shape != model_output.shape or eps_uncond.dtype != model_output.dtype:
+                raise ValueError("eps_uncond must have the model output's shape and dtype")
+        return eps_uncond
+
+    @staticmethod
+    def _check_eps_out(m, model_output):
+        if m.shape != model_output.shape or m.dtype != model_output.dtype or not m.is_contiguous():
+            raise ValueError("step(eps_out=...) must be contiguous with the model output's shape and dtype")
 
     @staticmethod
     def _alpha_sigma_lambda(sigma):
@@ -205,29 +233,11 @@ class DPMSolverMultistepScheduler(SigmaGridMixin, SchedulerMixin, ConfigMixin):
         """``DDIMBaselineScheduler.step``'s signature and dtype rules.  ``eps_out`` receives the converted model output m0 (the
         history entry: the combined eps for ``dpmsolver``, the x0 prediction for ``dpmsolver++``); the scheduler keeps a
         reference to it for the next step, so a caller that passes its own buffers rotates at least ``solver_order`` of them."""
-        if self.num_inference_steps is None:
-            raise ValueError("Number of inference steps is 'None'. Call 'set_timesteps' first.")
-        L.require_cuda(model_output, "model_output")
-        L.require_cuda(sample, "sample")
-        model_output, sample = model_output.contiguous(), sample.contiguous()
-        if sample.dtype != model_output.dtype and sample.dtype != torch.float32:
-            sample = sample.to(model_output.dtype)
-        if self.prev_sample_dtype is not None and sample.dtype != self.prev_sample_dtype:
-            sample = sample.to(self.prev_sample_dtype)
-        if sample.shape != model_output.shape:
-            raise ValueError(f"sample {tuple(sample.shape)} and model_output {tuple(model_output.shape)} differ in shape")
-        dev, B = model_output.device, model_output.shape[0]
-        if self._step_index is None:
-            self._step_index = self._init_step_index(timestep)
-        i = self._step_index
-        if i >= self.num_inference_steps:
-            raise ValueError(f"step {i} is past the {self.num_inference_steps} steps of set_timesteps")
+        model_output, sample, i = self._begin_step(model_output, timestep, sample)
+        dev = model_output.device
         first = self._first_order(i, self._lower_order_nums)
         conv_x, conv_e, cx, c0, c1 = self.step_scalars(i, first)
-        if eps_uncond is not None:
-            eps_uncond = L.require_cuda(eps_uncond, "eps_uncond").contiguous()
-            if eps_uncond.shape != model_output.shape or eps_uncond.dtype != model_output.dtype:
-                raise ValueError("eps_uncond must have the model output's shape and dtype")
+        eps_uncond = self._checked_eps_uncond(eps_uncond, model_output)
         m_prev = None
         if not first:
             m_prev = self._m[0]
@@ -239,27 +249,14 @@ class DPMSolverMultistepScheduler(SigmaGridMixin, SchedulerMixin, ConfigMixin):
         else:
             m0 = eps_out if eps_out is not None else torch.empty_like(model_output)
         m_out = None if m0 is model_output else m0
-        if m_out is not None and (m_out.shape != model_output.shape or m_out.dtype != model_output.dtype or not m_out.is_contiguous()):
-            raise ValueError("step(eps_out=...) must be contiguous with the model output's shape and dtype")
-        prev = out if out is not None else torch.empty_like(sample)
-        if prev.dtype != sample.dtype:
-            raise ValueError(f"step(out=...) must have the sample's dtype {sample.dtype}, got {prev.dtype}")
-        if prev.shape != sample.shape or not prev.is_contiguous():
-            raise ValueError("step(out=...) must be contiguous with the sample's shape")
+        if m_out is not None:
+            self._check_eps_out(m_out, model_output)
+        prev = result_tensor(out, sample, contiguous_like_sample=True)
         a = L.CsDpmStepArgs()
-        a.x, a.eps_text = sample.data_ptr(), model_output.data_ptr()
-        a.eps_uncond = eps_uncond.data_ptr() if eps_uncond is not None else None
-        a.guidance = float(guidance_scale)
+        fill_cfg(a, sample, model_output, eps_uncond, guidance_scale)
         a.m_prev = m_prev.data_ptr() if m_prev is not None else None
-        a.B, a.elems = B, sample.numel() // max(B, 1)
-        a.io_dtype, a.out_dtype = L.dtype_code(model_output.dtype), L.dtype_code(sample.dtype)
-        a.x_is_f32 = int(sample.dtype == torch.float32 and model_output.dtype != torch.float32)
-        a.x_out = prev.data_ptr()
         a.m_out = m_out.data_ptr() if m_out is not None else None
-        if out_lp is not None:
-            if out_lp.dtype not in (torch.float16, torch.bfloat16) or prev.dtype != torch.float32 or out_lp.shape != prev.shape or not out_lp.is_contiguous():
-                raise ValueError("step(out_lp=...) is the contiguous fp16 / bf16 copy of an fp32 prev_sample of the same shape")
-            a.x_out_lp, a.lp_dtype = out_lp.data_ptr(), L.dtype_code(out_lp.dtype)
+        fill_io(a, sample, model_output, prev, sample.dtype, out_lp)
         a.conv_x, a.conv_e, a.cx, a.c0, a.c1 = float(conv_x), float(conv_e), float(cx), float(c0), float(c1)
         L.check(L.lib().cs_dpm_multistep_step(C.byref(a), L.stream_ptr(dev)))
         self._m = [m0] + self._m[:self.config.solver_order - 1]

@@ -30,7 +30,7 @@ import torch
 from . import _lib as L
 from ._scheduler_base import ConfigMixin, SchedulerMixin, register_to_config
 from .scheduling_fmppo import FlowMatchScheduleMixin
-from .scheduling_ppo import SolverOutput
+from .scheduling_ppo import SolverOutput, fill_io, step_inputs
 
 FM_SOLVER_TYPES = ("euler", "heun", "dpm-solver", "dpm-solver-multistep")
 
@@ -103,11 +103,7 @@ class FlowMatchGeneralDiscreteScheduler(FlowMatchScheduleMixin, SchedulerMixin, 
             raise ValueError("Number of inference steps is 'None'. Call 'set_timesteps' first.")
         if self._step_index is None:
             self._init_step_index(timestep)
-        L.require_cuda(model_output, "model_output")
-        L.require_cuda(sample, "sample")
-        model_output, sample = model_output.contiguous(), sample.contiguous()
-        if sample.dtype != model_output.dtype and sample.dtype != torch.float32:        # (an fp32 sample is consumed as fp32: :401 upcasts it)
-            sample = sample.to(model_output.dtype)
+        model_output, sample = step_inputs(model_output, sample)        # (an fp32 sample is consumed as fp32: :401 upcasts it)
         plan = self.step_plan()
         base = sample if plan.base == "sample" else self.prev_sample
         v1 = self.prev_model_output if plan.use_v1 else None
@@ -117,12 +113,9 @@ class FlowMatchGeneralDiscreteScheduler(FlowMatchScheduleMixin, SchedulerMixin, 
         if prev.dtype != model_output.dtype or prev.shape != model_output.shape or not prev.is_contiguous():
             raise ValueError(f"step(out=...) must be a contiguous {model_output.dtype} tensor of shape {tuple(model_output.shape)}")
         a = L.CsFmStepArgs()
-        a.x_base, a.v2, a.v1, a.x_out = base.data_ptr(), model_output.data_ptr(), v1.data_ptr() if v1 is not None else None, prev.data_ptr()
+        a.x_base, a.v2, a.v1 = base.data_ptr(), model_output.data_ptr(), v1.data_ptr() if v1 is not None else None
         a.c = float(plan.c)
-        a.B = model_output.shape[0]
-        a.elems = model_output.numel() // max(a.B, 1)
-        a.io_dtype = a.out_dtype = L.dtype_code(model_output.dtype)
-        a.x_is_f32 = int(base.dtype == torch.float32 and model_output.dtype != torch.float32)
+        fill_io(a, base, model_output, prev, model_output.dtype)
         L.check(L.lib().cs_fm_general_step(C.byref(a), L.stream_ptr(model_output.device)))
         self.commit_plan(plan, sample, model_output)
         return (prev,) if not return_dict else SolverOutput(prev_sample=prev)

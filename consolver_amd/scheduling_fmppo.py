@@ -21,7 +21,7 @@ from . import _lib as L
 from . import tables
 from .factor_net import FluxFactorNetPPO
 from ._scheduler_base import ConfigMixin, HAVE_DIFFUSERS, SchedulerMixin, register_to_config
-from .scheduling_ppo import HistoryMixin, SolverOutput
+from .scheduling_ppo import HistoryMixin, SolverOutput, step_inputs
 
 # FLUX.1-Kontext-dev's published scheduler/scheduler_config.json: what from_pretrained falls back to offline
 KONTEXT_SCHEDULER_CONFIG = dict(shift=3.0, use_dynamic_shifting=True, base_shift=0.5, max_shift=1.15,
@@ -203,15 +203,9 @@ class FMPPOScheduler(HistoryMixin, FlowMatchScheduleMixin, SchedulerMixin, Confi
             raise NotImplementedError("More than two scale parameters not supported.")
         if self._step_index is None:
             self._init_step_index(timestep)
-        L.require_cuda(model_output, "model_output")
-        L.require_cuda(sample, "sample")
-        model_output = model_output.contiguous()
         # the reference upcasts the SAMPLE to fp32 (scheduler_fmppo.py:354) and rounds only the result (:435-436):
         # an fp32 sample is consumed as fp32 by the kernel; a sample already in the model dtype is exact either way
-        sample = sample.contiguous()
-        x_is_f32 = (sample.dtype == torch.float32 and model_output.dtype != torch.float32)
-        if not x_is_f32 and sample.dtype != model_output.dtype:
-            sample = sample.to(model_output.dtype)
+        model_output, sample = step_inputs(model_output, sample)
         dev = model_output.device
         B = model_output.shape[0]
         self.ets.append(model_output)
@@ -235,8 +229,6 @@ class FMPPOScheduler(HistoryMixin, FlowMatchScheduleMixin, SchedulerMixin, Confi
         a = L.CsStepArgs()
         self._fill_step_args(a, sample, model_output, None, 1.0, actions, prev, None, model_output.dtype)
         a.dt = float(dt)
-        if x_is_f32:
-            a.io_dtype, a.x_is_f32 = L.dtype_code(model_output.dtype), 1
         L.check(L.lib().cs_lms_euler_step(C.byref(a), L.stream_ptr(dev)))
         self._step_index += 1
 

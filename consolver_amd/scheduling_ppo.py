@@ -36,6 +36,55 @@ class SolverOutput(dict):
             raise AttributeError(k) from e
 
 
+def step_inputs(model_output, sample, prev_sample_dtype=None):
+    """(model_output, sample) as every scheduler's ``step`` hands them to its kernel: on the GPU and contiguous.  An fp32 ``sample`` stays fp32 through
+    the update (torch promotion; the reference's latents ARE fp32 from step 2 on when the policy net is fp32; scheduler_fmppo.py:354 and
+    scheduler_fm.py:401 upcast it) -- the native engine keeps its solver state that way: the per-step fp16 rounding of the latents (2.8e-4 relative L2
+    per step, accumulating in quadrature) was what made the 8-step drift grow and the 12-step trajectory miss the 1e-3 gate.  Any
+    other mismatch is cast to the model output's dtype, and a sample keeps its dtype unless ``prev_sample_dtype = torch.float32`` asks for the promotion."""
+    L.require_cuda(model_output, "model_output")
+    L.require_cuda(sample, "sample")
+    model_output, sample = model_output.contiguous(), sample.contiguous()
+    if sample.dtype != model_output.dtype and sample.dtype != torch.float32:
+        sample = sample.to(model_output.dtype)
+    if prev_sample_dtype is not None and sample.dtype != prev_sample_dtype:
+        sample = sample.to(prev_sample_dtype)
+    return model_output, sample
+
+
+def result_tensor(out, sample, contiguous_like_sample=False):
+    """``step(out=...)`` or a new tensor: ``prev_sample`` has the sample's dtype"""
+    prev = out if out is not None else torch.empty_like(sample)
+    if prev.dtype != sample.dtype:
+        raise ValueError(f"step(out=...) must have the sample's dtype {sample.dtype}, got {prev.dtype}")
+    if contiguous_like_sample and (prev.shape != sample.shape or not prev.is_contiguous()):
+        raise ValueError("step(out=...) must be contiguous with the sample's shape")
+    return prev
+
+
+def fill_io(a, sample, model_output, out, out_dtype, out_lp=None):
+    """the fields the args structs of all update kernels share: the shape, the dtype codes, the result and its optional 16-bit copy.
+    io_dtype is the model output's (eps, history, eps_out); an fp32 sample next to a 16-bit model output is passed as such (x_is_f32): the update
+    reads it unrounded, which is what torch's promotion does with an fp32 `sample` (scheduler_ppo.py:306-332, scheduler_fmppo.py:354)."""
+    a.B = sample.shape[0]
+    a.elems = sample.numel() // max(a.B, 1)
+    a.io_dtype, a.out_dtype = L.dtype_code(model_output.dtype), L.dtype_code(out_dtype)
+    a.x_is_f32 = int(sample.dtype == torch.float32 and model_output.dtype != torch.float32)
+    a.x_out = out.data_ptr()
+    if out_lp is not None:
+        # the model-dtype copy of an fp32 prev_sample, written by the same kernel pass (x_out_lp): what the denoiser reads at the next step
+        if out_lp.dtype not in (torch.float16, torch.bfloat16) or out.dtype != torch.float32 or out_lp.shape != out.shape or not out_lp.is_contiguous():
+            raise ValueError("step(out_lp=...) is the contiguous fp16 / bf16 copy of an fp32 prev_sample of the same shape")
+        a.x_out_lp, a.lp_dtype = out_lp.data_ptr(), L.dtype_code(out_lp.dtype)
+
+
+def fill_cfg(a, sample, eps_text, eps_uncond, guidance):
+    """the sample and the one or two branches of the model output (CsStepArgs, CsDpmStepArgs, CsUnipcStepArgs)"""
+    a.x, a.eps_text = sample.data_ptr(), eps_text.data_ptr()
+    a.eps_uncond = eps_uncond.data_ptr() if eps_uncond is not None else None
+    a.guidance = float(guidance)
+
+
 class HistoryMixin:
     """eps history + per-step policy evaluation shared by the SD and FLUX schedulers."""
 
@@ -78,27 +127,14 @@ class HistoryMixin:
         return out
 
     def _fill_step_args(self, a, sample, eps_text, eps_uncond, guidance, actions, out, eps_out, out_dtype, out_lp=None):
-        B = sample.shape[0]
         hist = self.ets[::-1]  # newest first, hist[0] is the eps just pushed
-        a.x, a.eps_text = sample.data_ptr(), eps_text.data_ptr()
-        a.eps_uncond = eps_uncond.data_ptr() if eps_uncond is not None else None
-        a.guidance = float(guidance)
+        fill_cfg(a, sample, eps_text, eps_uncond, guidance)
         for k in range(L.CS_MAX_ORDER):
             a.hist[k] = hist[k + 1].data_ptr() if k + 1 < len(hist) else None
         a.m, a.order_dim, a.scaler_dim = len(hist), self.config.order_dim, self.config.scaler_dim
         a.actions, a.actions_stride = actions.data_ptr(), actions.shape[1]
-        a.B, a.elems = B, sample.numel() // max(B, 1)
-        # io_dtype is the model output's (eps, history, eps_out); an fp32 sample next to a 16-bit model output is passed as such (x_is_f32): the update
-        # reads it unrounded, which is what torch's promotion does with an fp32 `sample` (scheduler_ppo.py:306-332, scheduler_fmppo.py:354)
-        a.io_dtype, a.out_dtype = L.dtype_code(eps_text.dtype), L.dtype_code(out_dtype)
-        a.x_is_f32 = int(sample.dtype == torch.float32 and eps_text.dtype != torch.float32)
-        a.x_out = out.data_ptr()
         a.eps_out = eps_out.data_ptr() if eps_out is not None else None
-        if out_lp is not None:
-            # the model-dtype copy of an fp32 prev_sample, written by the same kernel pass (CsStepArgs::x_out_lp): what the denoiser reads at the next step
-            if out_lp.dtype not in (torch.float16, torch.bfloat16) or out.dtype != torch.float32 or out_lp.shape != out.shape or not out_lp.is_contiguous():
-                raise ValueError("step(out_lp=...) is the contiguous fp16 / bf16 copy of an fp32 prev_sample of the same shape")
-            a.x_out_lp, a.lp_dtype = out_lp.data_ptr(), L.dtype_code(out_lp.dtype)
+        fill_io(a, sample, eps_text, out, out_dtype, out_lp)
 
 
 class PPOScheduler(HistoryMixin, SchedulerMixin, ConfigMixin):
@@ -261,18 +297,7 @@ class PPOScheduler(HistoryMixin, SchedulerMixin, ConfigMixin):
             raise ValueError(f"Unsupported prediction_type: {self.config.prediction_type}")
         if self.config.scaler_dim > 2:
             raise AssertionError("not implemented")     # scheduler_ppo.py:280
-        L.require_cuda(model_output, "model_output")
-        L.require_cuda(sample, "sample")
-        model_output = model_output.contiguous()
-        sample = sample.contiguous()
-        # dtype of the latents: an fp32 `sample` stays fp32 through the update (torch promotion; the reference's latents ARE fp32 from step 2 on when the policy
-        # net is fp32) -- the native engine keeps its solver state that way: the per-step fp16 rounding of the latents (2.8e-4 relative L2 per step,
-        # accumulating in quadrature) was what made the 8-step drift grow and the 12-step trajectory miss the 1e-3 gate.  A 16-bit sample
-        # keeps its dtype unless `prev_sample_dtype = torch.float32` asks for the promotion.
-        if sample.dtype != model_output.dtype and sample.dtype != torch.float32:
-            sample = sample.to(model_output.dtype)
-        if self.prev_sample_dtype is not None and sample.dtype != self.prev_sample_dtype:
-            sample = sample.to(self.prev_sample_dtype)
+        model_output, sample = step_inputs(model_output, sample, self.prev_sample_dtype)
         dev = model_output.device
         t = self._resolve_timestep(timestep)
         prev_t = t - self.config.num_train_timesteps // self.num_inference_steps
@@ -300,9 +325,7 @@ class PPOScheduler(HistoryMixin, SchedulerMixin, ConfigMixin):
             probs3, actions, aprobs, _ = self._policy(cond_row, B, dev)
         masks = self._masks(B, net.action_dims, m, dev)
 
-        prev = out if out is not None else torch.empty_like(sample)
-        if prev.dtype != sample.dtype:
-            raise ValueError(f"step(out=...) must have the sample's dtype {sample.dtype}, got {prev.dtype}")
+        prev = result_tensor(out, sample)
         a = L.CsStepArgs()
         self._fill_step_args(a, sample, model_output, eps_uncond, guidance_scale, actions, prev, eps_out, sample.dtype, out_lp)
         a.sqrt_at, a.sqrt_1mat, a.sqrt_ap, a.sqrt_1map = self._ddim_scalars(t, prev_t)

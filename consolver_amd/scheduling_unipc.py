@@ -24,7 +24,7 @@ import torch
 from . import _lib as L
 from ._scheduler_base import ConfigMixin, KARRAS_COMPATIBLES, SchedulerMixin, register_to_config
 from .scheduling_dpm import SigmaGridMixin
-from .scheduling_ppo import SolverOutput
+from .scheduling_ppo import SolverOutput, fill_cfg, fill_io, result_tensor
 
 # what the reference call site resolves to on SD1.5's scheduler_config.json (from memory, see the module docstring)
 SD15_UNIPC_KWARGS = dict(beta_start=0.00085, beta_end=0.012, beta_schedule="scaled_linear", steps_offset=1)
@@ -154,67 +154,36 @@ class UniPCMultistepScheduler(SigmaGridMixin, SchedulerMixin, ConfigMixin):
         """``DPMSolverMultistepScheduler.step``'s signature and dtype rules.  ``sample`` is the previous call's result (the predicted
         sample).  ``eps_out`` receives the converted model output (the x0 prediction, the history entry); the scheduler keeps references
         to the last ``solver_order`` of them, so a caller that passes its own buffers rotates at least ``history_slots``."""
-        if self.num_inference_steps is None:
-            raise ValueError("Number of inference steps is 'None'. Call 'set_timesteps' first.")
-        L.require_cuda(model_output, "model_output")
-        L.require_cuda(sample, "sample")
-        model_output, sample = model_output.contiguous(), sample.contiguous()
-        if sample.dtype != model_output.dtype and sample.dtype != torch.float32:
-            sample = sample.to(model_output.dtype)
-        if self.prev_sample_dtype is not None and sample.dtype != self.prev_sample_dtype:
-            sample = sample.to(self.prev_sample_dtype)
-        if sample.shape != model_output.shape:
-            raise ValueError(f"sample {tuple(sample.shape)} and model_output {tuple(model_output.shape)} differ in shape")
-        dev, B = model_output.device, model_output.shape[0]
-        if self._step_index is None:
-            self._step_index = self._init_step_index(timestep)
-        i = self._step_index
-        if i >= self.num_inference_steps:
-            raise ValueError(f"step {i} is past the {self.num_inference_steps} steps of set_timesteps")
+        model_output, sample, i = self._begin_step(model_output, timestep, sample)
+        dev = model_output.device
         use_corr = i > 0 and (i - 1) not in self._disable_corrector and self._have_last
         corr_order = self._this_order
         this_order = self._order(i, self._lower_order_nums)
         conv_x, conv_e, (a_x, a_0, a_1, a_n), (p_x, p_0, p_1), use_corr = self.step_scalars(i, corr_order, this_order, use_corr)
-        if eps_uncond is not None:
-            eps_uncond = L.require_cuda(eps_uncond, "eps_uncond").contiguous()
-            if eps_uncond.shape != model_output.shape or eps_uncond.dtype != model_output.dtype:
-                raise ValueError("eps_uncond must have the model output's shape and dtype")
-        need = 2 if (use_corr and a_1 != 0.0) else 1 if ((use_corr and a_0 != 0.0) or p_1 != 0.0) else 0
+        eps_uncond = self._checked_eps_uncond(eps_uncond, model_output)
+        need =2 if (use_corr and a_1 != 0.0) else 1 if ((use_corr and a_0 != 0.0) or p_1 != 0.0) else 0
         if need > len(self._m):
             raise ValueError(f"step {i} reads {need} earlier converted outputs, {len(self._m)} are kept; start a trajectory at the first timestep")
         for m in self._m[:need]:
             if m.shape != model_output.shape or m.dtype != model_output.dtype or m.device != dev:
                 raise ValueError("the model output changed shape, dtype or device since the previous step; call set_timesteps")
         m_new = eps_out if eps_out is not None else torch.empty_like(model_output)
-        if m_new.shape != model_output.shape or m_new.dtype != model_output.dtype or not m_new.is_contiguous():
-            raise ValueError("step(eps_out=...) must be contiguous with the model output's shape and dtype")
+        self._check_eps_out(m_new, model_output)
         if any(m_new.data_ptr() == m.data_ptr() for m in self._m[:need]) and m_new.numel():
             raise ValueError(f"step(eps_out=...) is a converted output this step still reads; rotate at least history_slots = {self.history_slots} buffers")
-        prev = out if out is not None else torch.empty_like(sample)
-        if prev.dtype != sample.dtype:
-            raise ValueError(f"step(out=...) must have the sample's dtype {sample.dtype}, got {prev.dtype}")
-        if prev.shape != sample.shape or not prev.is_contiguous():
-            raise ValueError("step(out=...) must be contiguous with the sample's shape")
+        prev = result_tensor(out, sample, contiguous_like_sample=True)
         if self._last is None or self._last.shape != sample.shape or self._last.dtype != sample.dtype or self._last.device != dev:
             if use_corr:
                 raise ValueError("the sample changed shape, dtype or device since the previous step; call set_timesteps")
             self._last = torch.empty_like(sample)
         a = L.CsUnipcStepArgs()
-        a.x, a.eps_text = sample.data_ptr(), model_output.data_ptr()
-        a.eps_uncond = eps_uncond.data_ptr() if eps_uncond is not None else None
-        a.guidance = float(guidance_scale)
+        fill_cfg(a, sample, model_output, eps_uncond, guidance_scale)
         a.use_corr = int(use_corr)
         a.x_last = self._last.data_ptr() if use_corr else None
         a.m_prev0 = self._m[0].data_ptr() if need >= 1 else None
         a.m_prev1 = self._m[1].data_ptr() if need >= 2 else None
-        a.B, a.elems = B, sample.numel() // max(B, 1)
-        a.io_dtype, a.out_dtype = L.dtype_code(model_output.dtype), L.dtype_code(sample.dtype)
-        a.x_is_f32 = int(sample.dtype == torch.float32 and model_output.dtype != torch.float32)
-        a.x_out, a.m_out, a.x_last_out = prev.data_ptr(), m_new.data_ptr(), self._last.data_ptr()      # (x_last is updated in place)
-        if out_lp is not None:
-            if out_lp.dtype not in (torch.float16, torch.bfloat16) or prev.dtype != torch.float32 or out_lp.shape != prev.shape or not out_lp.is_contiguous():
-                raise ValueError("step(out_lp=...) is the contiguous fp16 / bf16 copy of an fp32 prev_sample of the same shape")
-            a.x_out_lp, a.lp_dtype = out_lp.data_ptr(), L.dtype_code(out_lp.dtype)
+        a.m_out, a.x_last_out = m_new.data_ptr(), self._last.data_ptr()      # (x_last is updated in place)
+        fill_io(a, sample, model_output, prev, sample.dtype, out_lp)
         a.conv_x, a.conv_e = float(conv_x), float(conv_e)
         a.a_x, a.a_0, a.a_1, a.a_n = float(a_x), float(a_0), float(a_1), float(a_n)
         a.p_x, a.p_0, a.p_1 = float(p_x), float(p_0), float(p_1)

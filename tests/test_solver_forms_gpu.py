@@ -3,8 +3,9 @@ unipc, fm) bit for bit against the fp32 replicas of tests/solver_ref.py (`*_exac
 (cosine features, stack, masks, sample / gather, action_probs) against exact replicas or, where they reduce in an order of their own, against float64 with the bounds
 of tests/solver_ref.py (proven on the CPU by tests/test_solver_ref.py).  References, bounds, case lists and inputs all come from tests/solver_ref.py.
 
-Every output is a 16-byte-aligned slice of a NaN-filled buffer with 64 elements of margin on each side; the margins are all NaN after the call.  No base pointer is
-moved off 16-byte alignment: the only misalignment is the one a ragged b * elems gives the per-sample kernels (lms, dpm, cosine, stack).
+Every output is a 16-byte-aligned slice of a NaN-filled buffer with 64 elements of margin on each side; the margins are all NaN after the call.  One test moves
+a base pointer off 16-byte alignment (test_fm_fp32_state_on_a_4_byte_boundary: the fp32 side of fm's mixed pair, one float); otherwise the only misalignment is
+the one a ragged b * elems gives the per-sample kernels (lms, dpm, cosine, stack).
 
 Measured on an MI355X (gfx950; solver.hip built with -O3 -ffp-contract=off):
     Bit-exact against the fp32 replica, every output tensor of every case: lms DDIM and Euler in all 17 (io, out, x_is_f32, lp) forms, the 48 / 24 history forms
@@ -46,24 +47,26 @@ def dev(a, dt="f32"):
 
 
 class Guarded:
-    """a NaN-filled buffer with G elements of margin around n elements of dtype dt (torch dtype or name)"""
+    """a NaN-filled buffer with G elements of margin around n elements of dtype dt (torch dtype or name); off: elements by which the tensor is moved off
+    16-byte alignment"""
 
-    def __init__(self, shape, dt):
+    def __init__(self, shape, dt, off=0):
         self.dt = TD.get(dt, dt)
         n = int(np.prod(shape))
         if self.dt == torch.int64:
-            self.buf = torch.full((n + 2 * G,), -77, dtype=self.dt, device=DEV)
+            self.buf = torch.full((n + 2 * G + off,), -77, dtype=self.dt, device=DEV)
         else:
-            self.buf = torch.full((n + 2 * G,), float("nan"), dtype=self.dt, device=DEV)
-        self.view = self.buf[G:G + n].view(*shape)
-        assert self.view.data_ptr() % 16 == 0
+            self.buf = torch.full((n + 2 * G + off,), float("nan"), dtype=self.dt, device=DEV)
+        self.lo, self.hi = G + off, G + off + n
+        self.view = self.buf[self.lo:self.hi].view(*shape)
+        assert self.view.data_ptr() % 16 == off * self.buf.element_size()
 
     @property
     def ptr(self):
         return self.view.data_ptr()
 
     def margins_intact(self):
-        m = torch.cat([self.buf[:G], self.buf[-G:]])
+        m = torch.cat([self.buf[:self.lo], self.buf[self.hi:]])
         return bool((m == -77).all()) if self.dt == torch.int64 else bool(torch.isnan(m).all())
 
     def untouched(self):
@@ -84,13 +87,18 @@ def build(c):
     k, B, n, io, out = c["kernel"], c["B"], c["elems"], c["io"], c["out"]
     shape = (B, n)
     xdt = "f32" if c["x_is_f32"] else io
-    outs = {"x_out": Guarded(shape, out)}
+    off = c.get("x_off", 0)                     # elements by which x and x_out are moved off 16-byte alignment
+    outs = {"x_out": Guarded(shape, out, off)}
     if c["lp"]:
         outs["x_out_lp"] = Guarded(shape, c["lp"])
     keep = []
 
-    def d(a, dt):
+    def d(a, dt, off=0):
         t = dev(a, dt)
+        if t is not None and off:
+            buf = torch.empty(t.numel() + off, dtype=t.dtype, device=DEV)
+            assert buf.data_ptr() % 16 == 0
+            t = buf[off:].view(t.shape).copy_(t)
         keep.append(t)
         return p(t)
     if k == "lms":
@@ -132,7 +140,7 @@ def build(c):
         fn = L.lib().cs_unipc_step
     else:
         a = L.CsFmStepArgs()
-        a.x_base, a.v2, a.v1, a.c = d(c["x"], xdt), d(c["v2"], io), d(c["v1"], io), c["c"]
+        a.x_base, a.v2, a.v1, a.c = d(c["x"], xdt, off), d(c["v2"], io), d(c["v1"], io), c["c"]
         fn = L.lib().cs_fm_general_step
     a.B, a.elems, a.io_dtype, a.out_dtype, a.x_is_f32, a.x_out = B, n, CODE[io], CODE[out], c["x_is_f32"], p(outs["x_out"])
     if k != "fm":
@@ -240,6 +248,13 @@ def test_fm_dtype_forms(form):
 
 def test_fm_grid_stride():
     run_cases(R.fm_grid_stride_cases())
+
+
+@pytest.mark.parametrize("io", ("f16", "bf16"))
+def test_fm_fp32_state_on_a_4_byte_boundary(io):
+    """the fp32 side of a mixed pair needs 4-byte alignment only: 16-bit v2 / v1, x_is_f32 = 1 and an fp32 result at (3, 269), with x_base and x_out one float
+    past a 16-byte boundary inside their buffers; Euler and Heun form, bit for bit, margins intact"""
+    run_cases([dict(R.make_fm(f"fm-off4-{io}-v{v}", 3, 269, (io, "f32", 1), with_v1=v, which="interior"), x_off=1) for v in (0, 1)])
 
 
 # ----------------------------------------------------------------------------------------------------------------- refusals
