@@ -34,6 +34,7 @@ SOURCES = {
     "clip_vision.cpp": [],
     "dpt_ops.hip": [],
     "depth.cpp": [],
+    "depth_hw.cpp": [],
     "seg_ops.hip": [],
     "segformer.cpp": [],
     "incep_ops.hip": [],

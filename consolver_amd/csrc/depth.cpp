@@ -10,28 +10,12 @@
 //     the token to its k x k output pixels): one GEMM [tokens][D] x [k k C][D]^T through launch_igemm, then the pixel-shuffle store;
 //   * channel counts the kernels cannot take are zero-padded in the weights of the layer that produces them and of the one that consumes them (48 -> 64 for the
 //     narrow conv's 32-channel k step; 192 -> 256 for the GEMM's 128-column tile).
-#include "image_tower.h"
-#include "consolver_hip.h"
+#include "depth_model.h"
 #include "../../include/consolver_hip_ops.h"
 
-namespace {
-struct DConv { f16* w = nullptr; f16* b = nullptr; };
-struct Fusion { DConv proj, r1c1, r1c2, r2c1, r2c2; };
-constexpr int RK[4] = {4, 2, 1, 1};      // reassemble_factors 4, 2, 1, 0.5: the first two are transposed convs with kernel = stride, the last a stride-2 3x3 conv
-}  // namespace
-
-struct CsDepth {
-    CsDepthConfig cfg;
-    ImageTower tower;                      // the DINOv2 backbone, its processor resizing to edge = crop = size: the whole image, no crop
-    int S = 0, F = 0, HH = 0;              // image size, fusion / head widths
-    int g[4] = {0, 0, 0, 0};               // sizes of the four reassembled maps: 4 G, 2 G, G, (G - 1) / 2 + 1
-    int cp[4] = {0, 0, 0, 0};              // their channel counts as stored (neck_hidden_sizes padded)
-    DConv reasm[4];                        // projection (folded with the transposed conv): [k k cp][D]
-    DConv down;                            // reassemble layer 3's stride-2 3x3 conv [cp3][9][cp3]
-    DConv neck[4];                         // neck.convs [F][9][cp]
-    Fusion fus[4];
-    DConv head1, head2, head3;
-};
+using depth_model::DConv;
+using depth_model::Fusion;
+using depth_model::RK;
 
 namespace {
 
@@ -87,37 +71,17 @@ std::vector<float> pad_vector(const std::vector<float>& v, int n) {
     return o;
 }
 
-// workspace carve-up (fp16 elements): the encoder stack | patch embeddings | normalised tap | reassemble GEMM output | reassembled map | map 3 after its
-// stride-2 conv | the four neck features | three rotating buffers for the fusion stage and the head
-struct Layout { size_t pe, tap, gemm, map, down, f[4], x, y, z, total; };
-Layout layout(const CsDepth* c, size_t B) {
-    const ImageTower& t = c->tower;
-    const size_t D = t.D, rows = B * t.T, F = c->F, G = t.G;
-    Layout L;
-    L.pe = pre_ln_workspace_elems(rows, D, t.I);
-    size_t o = t.workspace_elems(B);          // ... with the patch embeddings
-    L.tap = o; o += rows * D;
-    size_t nmax = 0, mmax = 0;
-    for (int i = 0; i < 4; ++i) {
-        nmax = std::max(nmax, (size_t)RK[i] * RK[i] * c->cp[i]);
-        mmax = std::max(mmax, G * RK[i] * G * RK[i] * c->cp[i]);
-    }
-    L.gemm = o; o += rows * nmax;
-    L.map = o; o += B * mmax;
-    L.down = o; o += B * c->g[3] * c->g[3] * c->cp[3];
-    for (int i = 0; i < 4; ++i) { L.f[i] = o; o += B * c->g[i] * c->g[i] * F; }
-    const size_t up = (size_t)2 * c->g[0], big = std::max(up * up * F, (size_t)c->S * c->S * std::max(F / 2, (size_t)c->HH));
-    L.x = o; o += B * big; L.y = o; o += B * big; L.z = o; o += B * big;
-    L.total = o;
-    return L;
-}
-
 // the backbone's layers up to the last tap (the ones behind it feed nothing), then the neck and the head with the folds of the header comment
 bool pack(CsDepth* c) {
     WeightStore<float>& W = c->tower.weights;
     auto T = [&](const std::string& n) -> const std::vector<float>& { return W.at(n).data; };
     const int D = c->tower.D, F = c->F;
     bool ok = image_tower::pack_dinov2_backbone(c->tower, "backbone.", c->cfg.image_size / c->cfg.patch_size, c->cfg.out_indices[3]);
+    if (ok) {          // the trained grid without its class row, in fp32: what cs_depth_forward_hw interpolates for another grid
+        const auto& pos = T("backbone.embeddings.position_embeddings");
+        c->pos_grid = W.upload_f32(std::vector<float>(pos.begin() + D, pos.end()));
+        ok = c->pos_grid != nullptr;
+    }
     for (int i = 0; i < 4 && ok; ++i) {
         // reassemble layer i as one linear map: row (ky k + kx) cp + co of the GEMM = sum_ci resize[ci][co][ky][kx] projection[ci][:] (k = 1: the projection itself)
         const std::string p = "neck.reassemble_stage.layers." + std::to_string(i);
@@ -206,6 +170,7 @@ int cs_depth_create(const CsDepthConfig* cfg, CsDepth** out) {
 
 void cs_depth_destroy(CsDepth* c) {
     if (!c) return;
+    for (auto& kv : c->pos_tables) (void)hipFree(kv.second);
     c->tower.free_device();
     delete c;
 }
@@ -225,25 +190,10 @@ int cs_depth_num_tokens(const CsDepth* c) { return c ? c->tower.T : 0; }
 
 size_t cs_depth_workspace_bytes(const CsDepth* c, int batch) {
     if (!c || batch <= 0) return 0;
-    return layout(c, (size_t)batch).total * sizeof(f16) + 4096;
+    return depth_model::workspace_bytes(c, depth_model::make_grid(c, c->S, c->S), batch);
 }
 
-double cs_depth_flops(const CsDepth* c, int batch) {
-    if (!c) return 0;
-    const double D = c->tower.D, F = c->F, B = batch;
-    double f = c->tower.flops(c->cfg.out_indices[3], batch);
-    for (int i = 0; i < 4; ++i) {
-        const double px = (double)c->g[i] * c->g[i];
-        f += 2.0 * B * c->tower.T * D * RK[i] * RK[i] * c->cp[i];                                   // reassemble GEMM
-        f += 2.0 * B * px * 9 * c->cp[i] * F;                                                 // neck conv
-        const int lvl = 3 - i;                                                                // fusion layer `lvl` runs at this map's size
-        const double nxt = i ? (double)c->g[i - 1] * c->g[i - 1] : 4.0 * px;
-        f += (lvl ? 4 : 2) * 2.0 * B * px * 9 * F * F + 2.0 * B * nxt * F * F;
-    }
-    f += 2.0 * B * c->g[3] * c->g[3] * 9.0 * c->cp[3] * c->cp[3];                             // the stride-2 conv
-    f += 2.0 * B * 4.0 * c->g[0] * c->g[0] * 9 * F * (F / 2) + 2.0 * B * c->S * (double)c->S * (9.0 * (F / 2) * c->HH + c->HH);
-    return f;
-}
+double cs_depth_flops(const CsDepth* c, int batch) { return c ? depth_model::flops(c, depth_model::make_grid(c, c->S, c->S), batch) : 0; }
 
 size_t cs_depth_preprocess_workspace_bytes(const CsDepth* c, int batch, int height, int width) {
     return image_tower::preprocess_workspace_bytes(tower_of(c), batch, height, width);
@@ -252,7 +202,8 @@ size_t cs_depth_preprocess_workspace_bytes(const CsDepth* c, int batch, int heig
 int cs_depth_preprocess(CsDepth* c, const void* images, int dtype, int batch, int height, int width, void* patches, unsigned char* crop_u8,
                         void* workspace, size_t workspace_bytes, void* stream) {
     if (c && batch >= 0 && height != width)          // (behind the null-handle and negative-size refusals, in front of the empty batch's return)
-        CS_FAIL(CS_E_UNSUPPORTED, "depth: %d x %d image: only square inputs are built (the processor's keep_aspect_ratio rule then gives %d x %d)", height, width, c->S, c->S);
+        CS_FAIL(CS_E_UNSUPPORTED, "depth: %d x %d image: this entry point takes square inputs only (they resize to %d x %d); cs_depth_preprocess_hw takes any aspect ratio", height, width, c->S,
+                c->S);
     return image_tower::preprocess(NAMES, tower_of(c), images, dtype, batch, height, width, patches, crop_u8, workspace, workspace_bytes, stream);
 }
 
@@ -260,66 +211,12 @@ int cs_depth_forward(CsDepth* c, const void* patches, int batch, float* predicte
     bool run = false;
     int rc = image_tower::begin_forward(NAMES, tower_of(c), batch, patches && predicted_depth && workspace, workspace_bytes, cs_depth_workspace_bytes(c, batch), &run);
     if (!run) return rc;
-    const ImageTower& t = c->tower;
-    const int D = t.D, I = t.I, H = t.heads, Tn = t.T, F = c->F, B = batch, G = t.G;
-    const Layout L = layout(c, (size_t)B);
-    if (t.too_many_rows(B, 16 * c->cp[0]) || (long)B * c->S * c->S > 0x7fffffffL / 64) CS_FAIL(CS_E_SHAPE, "depth: batch too large for one call");
+    const depth_model::DepthGrid g = depth_model::make_grid(c, c->S, c->S);
+    if (depth_model::too_large(c, g, batch)) CS_FAIL(CS_E_SHAPE, "depth: batch too large for one call");
     hipStream_t s = (hipStream_t)stream;
-    const long rows = (long)B * Tn;
-    const PreLnWorkspace w = carve_pre_ln(workspace, rows, D, I);
-    f16* base = (f16*)workspace;
-    f16 *pe = base + L.pe, *tap = base + L.tap, *gemm = base + L.gemm, *map = base + L.map, *down = base + L.down;
-    f16* f[4] = {base + L.f[0], base + L.f[1], base + L.f[2], base + L.f[3]};
-    f16 *X = base + L.x, *Y = base + L.y, *Z = base + L.z;
-    auto conv = [&](const f16* x, int size, int cin, const DConv& cv, int cout, int taps, int relu_in, int relu_out, const f16* res, const f16* res2, f16* out) {
-        DptConvArgs a{};
-        a.x = x; a.B = B; a.H = size; a.W = size; a.Cin = cin; a.w = cv.w; a.bias = cv.b; a.Cout = cout; a.taps = taps;
-        a.relu_in = relu_in; a.relu_out = relu_out; a.res = res; a.res2 = res2; a.out = out;
-        return launch_dpt_conv(a, s);
-    };
-    // pre-activation residual unit: out = conv2(relu(conv1(relu(x)))) + x (+ skip); tmp holds the inner activation
-    auto rcu = [&](const f16* x, int size, const DConv& c1, const DConv& c2, const f16* skip, f16* tmp, f16* out) {
-        const int rc = conv(x, size, F, c1, F, 9, 1, 0, nullptr, nullptr, tmp);
-        return rc != CS_OK ? rc : conv(tmp, size, F, c2, F, 9, 1, 0, x, skip, out);
-    };
-
-    // ---- backbone, tapped after out_indices[i] layers: final LayerNorm -> reassemble layer i -> neck conv i ----
-    rc = image_tower::embed_patches(t, patches, B, pe, w.x, s);
-    size_t done = 0;
-    for (int i = 0; i < 4 && rc == CS_OK; ++i) {
-        const int k = RK[i], cp = c->cp[i];
-        rc = run_pre_ln_layers(t.layers, w, B, Tn, D, I, H, t.eps, 0, launch_gelu_erf, s, done, (size_t)c->cfg.out_indices[i]);
-        done = (size_t)c->cfg.out_indices[i];
-        if (rc == CS_OK) rc = launch_layer_norm(w.x, t.lnfg, t.lnfb, tap, (int)rows, D, t.eps, s);
-        if (rc == CS_OK) rc = linear(tap, (int)rows, D, c->reasm[i].w, c->reasm[i].b, k * k * cp, nullptr, gemm, s);
-        if (rc == CS_OK) rc = launch_dpt_pixel_shuffle(gemm, B, G, k, cp, 1, map, s);               // drops the CLS rows
-        const f16* src = map;
-        if (i == 3 && rc == CS_OK) {
-            IgemmArgs a{};
-            a.a0 = map; a.c0 = cp; a.B = B; a.Hi = G; a.Wi = G; a.Ho = c->g[3]; a.Wo = c->g[3]; a.taps = 9; a.stride = 2; a.N = cp;
-            a.w = c->down.w; a.bias = c->down.b; a.out = down;
-            rc = launch_igemm(a, s);
-            src = down;
-        }
-        if (rc == CS_OK) rc = conv(src, c->g[i], cp, c->neck[i], F, 9, 0, 0, nullptr, nullptr, f[i]);
-    }
-    // ---- fusion stage, coarse to fine: X holds the fused state ----
-    for (int l = 0; l < 4 && rc == CS_OK; ++l) {
-        const int i = 3 - l, size = c->g[i], next = i ? c->g[i - 1] : 2 * size;
-        const Fusion& fu = c->fus[l];
-        const f16* h = f[i];
-        if (l) { rc = rcu(f[i], size, fu.r1c1, fu.r1c2, X, Y, Z); h = Z; }                         // Z = fused + residual_layer1(feature)
-        if (rc == CS_OK) rc = rcu(h, size, fu.r2c1, fu.r2c2, nullptr, Y, X);                        // X = residual_layer2(h)
-        if (rc == CS_OK) rc = launch_dpt_bilinear(X, B, size, size, F, next, next, Y, s);
-        if (rc == CS_OK) rc = conv(Y, next, F, fu.proj, F, 1, 0, 0, nullptr, nullptr, X);
-    }
-    // ---- head ----
-    const int up = 2 * c->g[0];
-    if (rc == CS_OK) rc = conv(X, up, F, c->head1, F / 2, 9, 0, 0, nullptr, nullptr, Y);
-    if (rc == CS_OK) rc = launch_dpt_bilinear(Y, B, up, up, F / 2, c->S, c->S, Z, s);
-    if (rc == CS_OK) rc = conv(Z, c->S, F / 2, c->head2, c->HH, 9, 0, 1, nullptr, nullptr, Y);
-    if (rc == CS_OK) rc = launch_dpt_head(Y, (long)B * c->S * c->S, c->HH, c->head3.w, c->head3.b, c->cfg.max_depth, predicted_depth, s);
-    return rc;
+    const int G = c->tower.G;
+    return depth_model::forward(c, g, c->tower.pos, patches, batch, predicted_depth, workspace, s,
+                                [&](const f16* y, int k, int C, f16* out) { return launch_dpt_pixel_shuffle(y, batch, G, k, C, 1, out, s); });
 }
 
 int cs_depth_normalized_maps(CsDepth* c, const float* predicted_depth, int batch, int height, int width, float* maps, void* stream) {

@@ -130,17 +130,17 @@ __global__ __launch_bounds__(256) void dpt_bilinear_kernel(const f16* __restrict
     *reinterpret_cast<f16x8*>(out + i * 8) = o;
 }
 
-__global__ __launch_bounds__(256) void dpt_pixel_shuffle_kernel(const f16* __restrict__ y, int G, int k, int C8, int skip, long total, f16* __restrict__ out) {
+__global__ __launch_bounds__(256) void dpt_pixel_shuffle_kernel(const f16* __restrict__ y, int Gh, int Gw, int k, int C8, int skip, long total, f16* __restrict__ out) {
     const long i = (long)blockIdx.x * 256 + threadIdx.x;
     if (i >= total) return;
     const int c8 = (int)(i % C8);
     long t = i / C8;
-    const int S = G * k;
-    const int ox = (int)(t % S); t /= S;
-    const int oy = (int)(t % S);
-    const long b = t / S;
+    const int Sh = Gh * k, Sw = Gw * k;
+    const int ox = (int)(t % Sw); t /= Sw;
+    const int oy = (int)(t % Sh);
+    const long b = t / Sh;
     const int gy = oy / k, ky = oy - gy * k, gx = ox / k, kx = ox - gx * k;
-    const long row = b * ((long)skip + (long)G * G) + skip + (long)gy * G + gx;
+    const long row = b * ((long)skip + (long)Gh * Gw) + skip + (long)gy * Gw + gx;
     *reinterpret_cast<f16x8*>(out + i * 8) = *reinterpret_cast<const f16x8*>(y + (row * k * k + ky * k + kx) * C8 * 8 + c8 * 8);
 }
 
@@ -244,12 +244,16 @@ int launch_dpt_bilinear(const f16* x, int B, int Hi, int Wi, int C, int Ho, int 
 }
 
 int launch_dpt_pixel_shuffle(const f16* y, int B, int G, int k, int C, int skip, f16* out, hipStream_t s) {
+    return launch_dpt_pixel_shuffle_hw(y, B, G, G, k, C, skip, out, s);
+}
+
+int launch_dpt_pixel_shuffle_hw(const f16* y, int B, int Gh, int Gw, int k, int C, int skip, f16* out, hipStream_t s) {
     if (!y || !out) CS_FAIL(CS_E_ARG, "dpt pixel shuffle: null pointer");
-    if (C < 8 || C % 8 || G < 1 || k < 1 || skip < 0 || B < 0) CS_FAIL(CS_E_SHAPE, "dpt pixel shuffle: C %% 8 == 0 and positive sizes required");
-    const long total = (long)B * G * k * G * k * (C / 8);
+    if (C < 8 || C % 8 || Gh < 1 || Gw < 1 || k < 1 || skip < 0 || B < 0) CS_FAIL(CS_E_SHAPE, "dpt pixel shuffle: C %% 8 == 0 and positive sizes required");
+    const long total = (long)B * Gh * k * Gw * k * (C / 8);
     if (total == 0) return CS_OK;
     if (total > 0x7fffffffL * 256) CS_FAIL(CS_E_SHAPE, "dpt pixel shuffle: too large for one launch");
-    hipLaunchKernelGGL(dpt_pixel_shuffle_kernel, dim3(blocks_for(total)), dim3(256), 0, s, y, G, k, C / 8, skip, total, out);
+    hipLaunchKernelGGL(dpt_pixel_shuffle_kernel, dim3(blocks_for(total)), dim3(256), 0, s, y, Gh, Gw, k, C / 8, skip, total, out);
     CS_CHECK_LAUNCH();
     return CS_OK;
 }

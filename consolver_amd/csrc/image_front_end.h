@@ -7,6 +7,7 @@
 #include <algorithm>
 #include <cmath>
 #include <map>
+#include <tuple>
 #include <utility>
 #include <vector>
 
@@ -87,13 +88,14 @@ struct PlanCache {
     CropRule crop_rule = CROP_FLOOR;                        // the processor's center-crop offset (set once, next to filter)
     std::map<std::pair<int, int>, Plan> plans;
     std::map<std::pair<int, int>, FloatPlan> float_plans;   // get_float_plan's; the bound and the allocations are shared with `plans`
+    std::map<std::tuple<int, int, int, int>, Plan> hw_plans;   // get_plan_hw's, per (H, W, out_h, out_w); the same bound and allocations
     std::vector<void*> plan_allocs;
 
     // a full cache is emptied before a new table is allocated
     int make_room() {
-        if (plans.size() + float_plans.size() < MAX_PLANS) return CS_OK;
+        if (plans.size() + float_plans.size() + hw_plans.size() < MAX_PLANS) return CS_OK;
         for (void* q : plan_allocs) CS_CHECK_HIP(hipFree(q));
-        plan_allocs.clear(); plans.clear(); float_plans.clear();
+        plan_allocs.clear(); plans.clear(); float_plans.clear(); hw_plans.clear();
         return CS_OK;
     }
 
@@ -108,11 +110,30 @@ struct PlanCache {
         if (nh < C || nw < C) CS_FAIL(CS_E_UNSUPPORTED, "%s: resized image %d x %d is smaller than the %d crop (the processor would pad)", who, nh, nw, C);
         const Taps th = pil_taps(W, nw, crop_offset(nw, C, crop_rule), C, filter), tv = pil_taps(H, nh, crop_offset(nh, C, crop_rule), C, filter);
         Plan p{};
+        const int rc = upload(who, H, W, th, tv, &p);
+        if (rc != CS_OK) return rc;
+        *out = &(plans[{H, W}] = p);
+        return CS_OK;
+    }
+    // the plan of an H x W input resized straight to out_h x out_w on the integer-tap uint8 path: the two axes on independent scales, no crop window (what
+    // Image.resize((out_w, out_h)) does; a side that has its size already gets the identity taps, which the fixed-point pass reproduces exactly)
+    int get_plan_hw(const char* who, int H, int W, int out_h, int out_w, const Plan** out) {
+        auto it = hw_plans.find({H, W, out_h, out_w});
+        if (it != hw_plans.end()) { *out = &it->second; return CS_OK; }
+        if (H < 1 || W < 1 || out_h < 1 || out_w < 1) CS_FAIL(CS_E_SHAPE, "%s: bad image size %d x %d -> %d x %d", who, H, W, out_h, out_w);
+        const Taps th = pil_taps(W, out_w, 0, out_w, filter), tv = pil_taps(H, out_h, 0, out_h, filter);
+        Plan p{};
+        const int rc = upload(who, H, W, th, tv, &p);
+        if (rc != CS_OK) return rc;
+        *out = &(hw_plans[{H, W, out_h, out_w}] = p);
+        return CS_OK;
+    }
+    // the two tap tables of an H x W input onto the device as one allocation (a full cache is emptied first), and the input rows / columns they read
+    int upload(const char* who, int H, int W, const Taps& th, const Taps& tv, Plan* out) {
+        Plan p{};
         int row0 = H, row1 = 0, col0 = W, col1 = 0;
-        for (int i = 0; i < C; ++i) {
-            row0 = std::min(row0, tv.lo[i]); row1 = std::max(row1, tv.lo[i] + tv.cnt[i]);
-            col0 = std::min(col0, th.lo[i]); col1 = std::max(col1, th.lo[i] + th.cnt[i]);
-        }
+        for (size_t i = 0; i < tv.lo.size(); ++i) { row0 = std::min(row0, tv.lo[i]); row1 = std::max(row1, tv.lo[i] + tv.cnt[i]); }
+        for (size_t i = 0; i < th.lo.size(); ++i) { col0 = std::min(col0, th.lo[i]); col1 = std::max(col1, th.lo[i] + th.cnt[i]); }
         std::vector<int> all;
         auto put = [&](const std::vector<int>& v) { const size_t o = all.size(); all.insert(all.end(), v.begin(), v.end()); return o; };
         const size_t o0 = put(th.lo), o1 = put(th.cnt), o2 = put(th.kk), o3 = put(tv.lo), o4 = put(tv.cnt), o5 = put(tv.kk);
@@ -123,7 +144,7 @@ struct PlanCache {
         if (hipMemcpy(d, all.data(), all.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(d); CS_FAIL(CS_E_HIP, "%s: resize table upload failed", who); }
         plan_allocs.push_back(d);
         p.dev = VitResizePlan{d + o0, d + o1, d + o2, th.ksize, d + o3, d + o4, d + o5, tv.ksize, row0, row1 - row0, col0, col1};
-        *out = &(plans[{H, W}] = p);
+        *out = p;
         return CS_OK;
     }
     // the plan of an H x W mode-"F" image resized straight to out x out (clean-fid's resize): both axes independent, no crop window, double taps
@@ -156,7 +177,7 @@ struct PlanCache {
     // the owner's destroy: nothing reads a table any more
     void free_device() {
         for (void* p : plan_allocs) (void)hipFree(p);
-        plan_allocs.clear(); plans.clear(); float_plans.clear();
+        plan_allocs.clear(); plans.clear(); float_plans.clear(); hw_plans.clear();
     }
 };
 

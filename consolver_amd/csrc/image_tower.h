@@ -180,6 +180,24 @@ inline int preprocess(const TowerNames& nm, ImageTower* t, const void* images, i
                                 (f16*)patches, crop_u8, (hipStream_t)stream);
 }
 
+// the front end of a processor that resizes the whole image to out_h x out_w (no crop), behind the handle's own size rule: the argument checks of `preprocess`,
+// the two-axis plan, the workspace check.  *plan is set when the call has work to do; otherwise the return value is the call's
+inline size_t preprocess_hw_workspace_bytes(int batch, int height, int out_w) { return (size_t)batch * 3 * height * out_w + 256; }
+inline int begin_preprocess_hw(const TowerNames& nm, ImageTower* t, const void* images, int batch, int height, int width, int out_h, int out_w, const void* patches,
+                               const void* workspace, size_t workspace_bytes, const image_front_end::Plan** plan) {
+    *plan = nullptr;
+    if (!t) CS_FAIL(CS_E_ARG, "%s", nm.null_handle);
+    if (batch < 0) CS_FAIL(CS_E_ARG, "negative size");
+    if (batch == 0) return CS_OK;
+    if (!images || !patches || !workspace) CS_FAIL(CS_E_ARG, "null pointer");
+    const image_front_end::Plan* pl = nullptr;
+    const int rc = t->plans.get_plan_hw(nm.who, height, width, out_h, out_w, &pl);
+    if (rc != CS_OK) return rc;
+    if (workspace_bytes < (size_t)batch * 3 * pl->dev.nrows * out_w) CS_FAIL(CS_E_ARG, "%s: preprocess workspace too small", nm.who);
+    *plan = pl;
+    return CS_OK;
+}
+
 // ---- forward -------------------------------------------------------------------------------------------------------------------------------------------
 // the argument checks of cs_X_forward.  *run is set when the call has work to do; otherwise the return value is the call's (CS_OK for an empty batch).
 // pointers_ok: none of the caller's buffers is null; need: cs_X_workspace_bytes of this batch

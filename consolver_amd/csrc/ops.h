@@ -279,6 +279,13 @@ struct VitResizePlan {
 // tmp: B * 3 * nrows * (P G) bytes; crop (optional): the resized + cropped uint8 image [B][3][P G][P G]
 int launch_vit_front_end(const void* images, int dtype, int B, int H, int W, const VitResizePlan& pl, const float* mean, const float* stdv, double rescale,
                          int P, int G, int Kpad, unsigned char* tmp, f16* patches, unsigned char* crop, hipStream_t s);
+// the same for a resized image of Gh x Gw patches (the plan's tables then have P Gw columns and P Gh rows): patches [B * Gh * Gw][Kpad], tmp B * 3 * nrows * (P Gw)
+// bytes, crop [B][3][P Gh][P Gw]
+int launch_vit_front_end_hw(const void* images, int dtype, int B, int H, int W, const VitResizePlan& pl, const float* mean, const float* stdv, double rescale,
+                            int P, int Gh, int Gw, int Kpad, unsigned char* tmp, f16* patches, unsigned char* crop, hipStream_t s);
+// F.interpolate(mode="bicubic", align_corners=False, size=(gh, gw)) of the trained fp32 position grid [s][s][D] (A = -0.75, clamped reads, fp32 arithmetic, one
+// rounding) -> table [1 + gh * gw][D] fp16 as launch_vit_tokens reads it; row 0 (the class row, which the packed CLS token carries) is zero.  D % 8 == 0
+int launch_vit_pos_interp(const float* grid, int s, int gh, int gw, int D, f16* table, hipStream_t st);
 // x[b][0] = cls + pos[0], x[b][1 + p] = pe[b * NP + p] + pos[1 + p]
 int launch_vit_tokens(const f16* pe, const f16* cls, const f16* pos, f16* x, int B, int NP, int D, hipStream_t s);
 // x <- 0.5 x (1 + erf(x / sqrt 2)) in place
@@ -311,6 +318,8 @@ int launch_dpt_bilinear(const f16* x, int B, int Hi, int Wi, int C, int Ho, int 
 // the store of a transposed conv whose kernel equals its stride k, after its GEMM: y [B * T][k * k * C] (row b * T + skip + gy * G + gx, column (ky * k + kx) * C + c)
 // -> out NHWC [B][G k][G k][C]; skip = rows in front of every sample's grid (the CLS token), T = skip + G * G; C % 8 == 0.  k = 1 drops the CLS rows.
 int launch_dpt_pixel_shuffle(const f16* y, int B, int G, int k, int C, int skip, f16* out, hipStream_t s);
+// the same for a Gh x Gw token grid: T = skip + Gh * Gw, out NHWC [B][Gh k][Gw k][C]
+int launch_dpt_pixel_shuffle_hw(const f16* y, int B, int Gh, int Gw, int k, int C, int skip, f16* out, hipStream_t s);
 // out[m] = max(sum_c x[m][c] w[c] + bias, 0) * scale: the head's last 1x1 conv + ReLU (x max_depth) -> fp32; C % 8 == 0, C <= 64
 int launch_dpt_head(const f16* x, long M, int C, const f16* w, const f16* bias, float scale, float* out, hipStream_t s);
 // F.interpolate(mode="bicubic", align_corners=False) (A = -0.75, clamped reads, no antialias) of fp32 maps [B][Hi][Wi] -> [B][Ho][Wo]

@@ -259,8 +259,22 @@ size_t cs_seg_preprocess_workspace_bytes(const CsSeg* c, int batch, int height, 
 int cs_seg_preprocess(CsSeg* c, const void* images, int dtype, int batch, int height, int width, void* patches, unsigned char* crop_u8,
                       void* workspace, size_t workspace_bytes, void* stream) {
     if (c && batch >= 0 && height != width)
-        CS_FAIL(CS_E_UNSUPPORTED, "segformer: %d x %d image: only square inputs are built (they resize to %d x %d)", height, width, c->S, c->S);
+        CS_FAIL(CS_E_UNSUPPORTED, "segformer: %d x %d image: this entry point takes square inputs only; cs_seg_preprocess_hw stretches any image to %d x %d", height, width,
+                c->S, c->S);
     return image_tower::preprocess(NAMES, tower_of(c), images, dtype, batch, height, width, patches, crop_u8, workspace, workspace_bytes, stream);
+}
+
+// the processor stretches every image to S x S (both axes on their own scale), so the output is the square one's and the plan is all that differs
+int cs_seg_preprocess_hw(CsSeg* c, const void* images, int dtype, int batch, int height, int width, int* out_h, int* out_w, void* patches, unsigned char* crop_u8,
+                         void* workspace, size_t workspace_bytes, void* stream) {
+    if (c && out_h) *out_h = c->S;
+    if (c && out_w) *out_w = c->S;
+    const image_front_end::Plan* pl = nullptr;
+    const int rc = image_tower::begin_preprocess_hw(NAMES, tower_of(c), images, batch, height, width, c ? c->S : 0, c ? c->S : 0, patches, workspace, workspace_bytes, &pl);
+    if (!pl) return rc;
+    const ImageTower& t = c->tower;
+    return launch_vit_front_end(images, dtype, batch, height, width, pl->dev, t.mean, t.stdv, t.rescale, t.P, t.G, t.Kpad, (unsigned char*)workspace, (f16*)patches,
+                                crop_u8, (hipStream_t)stream);
 }
 
 int cs_seg_forward(CsSeg* c, const void* patches, int batch, float* logits, void* workspace, size_t workspace_bytes, void* stream) {

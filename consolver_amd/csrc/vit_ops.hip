@@ -53,25 +53,26 @@ __global__ __launch_bounds__(256) void vit_hresize_kernel(const T* __restrict__ 
     tmp[i] = (unsigned char)clip8(acc);
 }
 
-// vertical pass + normalise + patch rows: A[(b * G * G + py * G + px)][c * P * P + ky * P + kx], columns K .. Kpad zero
-__global__ __launch_bounds__(256) void vit_vresize_patch_kernel(const unsigned char* __restrict__ tmp, int B, int row0, int nrows, int cw, ResizeTab tv, int P, int G,
-                                                                int K, int Kpad, float m0, float m1, float m2, float s0, float s1, float s2, double rescale,
+// vertical pass + normalise + patch rows: A[(b * Gh * Gw + py * Gw + px)][c * P * P + ky * P + kx], columns K .. Kpad zero (the window is P Gh rows of cw = P Gw
+// columns; the square crop has Gh = Gw)
+__global__ __launch_bounds__(256) void vit_vresize_patch_kernel(const unsigned char* __restrict__ tmp, int B, int row0, int nrows, int cw, ResizeTab tv, int P, int Gh,
+                                                                int Gw, int K, int Kpad, float m0, float m1, float m2, float s0, float s1, float s2, double rescale,
                                                                 f16* __restrict__ patches, unsigned char* __restrict__ crop) {
     const long i = (long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= (long)B * G * G * Kpad) return;
+    if (i >= (long)B * Gh * Gw * Kpad) return;
     const int k = (int)(i % Kpad);
     if (k >= K) { patches[i] = (f16)0.0f; return; }
     const long t = i / Kpad;
-    const int p = (int)(t % (G * G)), b = (int)(t / (G * G));
+    const int p = (int)(t % (Gh * Gw)), b = (int)(t / (Gh * Gw));
     const int c = k / (P * P), r = k - c * P * P, ky = r / P, kx = r - ky * P;
-    const int y = (p / G) * P + ky, x = (p % G) * P + kx;
+    const int y = (p / Gw) * P + ky, x = (p % Gw) * P + kx;
     const unsigned char* col = tmp + ((long)(b * 3 + c) * nrows + (tv.lo[y] - row0)) * cw + x;
     const int* kk = tv.kk + (long)y * tv.ksize;
     const int n = tv.cnt[y];
     int acc = 1 << (RS_BITS - 1);
     for (int j = 0; j < n; ++j) acc += (int)col[(long)j * cw] * kk[j];
     const int u = clip8(acc);
-    if (crop) crop[((long)(b * 3 + c) * cw + y) * cw + x] = (unsigned char)u;
+    if (crop) crop[((long)(b * 3 + c) * (P * Gh) + y) * cw + x] = (unsigned char)u;
     const float mean = c == 0 ? m0 : (c == 1 ? m1 : m2), sd = c == 0 ? s0 : (c == 1 ? s1 : s2);
     const float v = (float)((double)u * rescale);        // the processor rescales in double and rounds to fp32, then normalises in fp32
     patches[i] = (f16)((v - mean) / sd);
@@ -92,6 +93,66 @@ __global__ __launch_bounds__(256) void vit_tokens_kernel(const f16* __restrict__
 #pragma unroll
     for (int e = 0; e < 8; ++e) o[e] = (f16)((float)a[e] + (float)q[e]);
     *reinterpret_cast<f16x8*>(x + row * D + d) = o;
+}
+
+// torch upsample_bicubic2d (align_corners = False, size given: scale = in / out per axis) of the trained position grid [s][s][D] fp32 to [gh][gw][D], written as
+// rows 1 .. gh gw of the fp16 table launch_vit_tokens reads (row 0 zero: the packed CLS token carries the class row).  fp32 arithmetic in the order of
+// torch's CPU kernel, one rounding to fp16.  Which of its multiply-adds that kernel's build fuses was found by comparing its weights and sums bit for bit
+// (an fp32 emulation of every candidate against F.interpolate): source = fma(scale, dst + 0.5, -0.5); lambda = source - floor(source); of the A = -0.75
+// coefficients the outer polynomial's first two steps are fused and nothing else; each sum of four terms starts from the SECOND product and takes the first,
+// third and fourth as fmas, over x inside the sum over y.  With that the table is torch's fp32 result bit for bit, rounded once.
+// Contraction is switched off so that exactly the fmas written here are fused.  One thread per 8 channels of one output position: 16 clamped taps of 32
+// bytes each, consecutive lanes on consecutive channels.
+__device__ __forceinline__ void pos_cubic_coeffs(float t, float* k) {
+#pragma clang fp contract(off)
+    const float A = -0.75f;
+    const float a = t + 1.0f, b = 1.0f - t, c = b + 1.0f;
+    k[0] = fmaf(fmaf(A, a, -5.0f * A), a, 8.0f * A) * a - 4.0f * A;
+    k[1] = ((A + 2.0f) * t - (A + 3.0f)) * t * t + 1.0f;
+    k[2] = ((A + 2.0f) * b - (A + 3.0f)) * b * b + 1.0f;
+    k[3] = fmaf(fmaf(A, c, -5.0f * A), c, 8.0f * A) * c - 4.0f * A;
+}
+__global__ __launch_bounds__(256) void vit_pos_interp_kernel(const float* __restrict__ grid, int s, int gh, int gw, int D8, float sy, float sx, long total,
+                                                             f16* __restrict__ table) {
+#pragma clang fp contract(off)
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total) return;
+    const int d = (int)(i % D8) * 8;
+    const long row = i / D8;
+    f16x8 o = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (row > 0) {
+        const int p = (int)(row - 1), oy = p / gw, ox = p - oy * gw;
+        const float ry = fmaf(sy, (float)oy + 0.5f, -0.5f), rx = fmaf(sx, (float)ox + 0.5f, -0.5f);
+        const float fy = floorf(ry), fx = floorf(rx);
+        const int iy = (int)fy, ix = (int)fx;
+        float ky[4], kx[4];
+        pos_cubic_coeffs(fminf(fmaxf(ry - fy, 0.0f), 1.0f), ky);
+        pos_cubic_coeffs(fminf(fmaxf(rx - fx, 0.0f), 1.0f), kx);
+        // a sum of four terms is t1 w1 first, then fma(t0, w0, .), fma(t2, w2, .), fma(t3, w3, .): the order of that build, over x and over y alike
+        float acc[8];
+#pragma unroll
+        for (int aa = 0; aa < 4; ++aa) {
+            const int a = aa == 0 ? 1 : (aa == 1 ? 0 : aa);
+            const int yy = min(max(iy - 1 + a, 0), s - 1);
+            float r[8];
+#pragma unroll
+            for (int bb = 0; bb < 4; ++bb) {
+                const int b = bb == 0 ? 1 : (bb == 1 ? 0 : bb);
+                const float* src = grid + ((long)yy * s + min(max(ix - 1 + b, 0), s - 1)) * (D8 * 8) + d;
+                const f32x4 v0 = *reinterpret_cast<const f32x4*>(src), v1 = *reinterpret_cast<const f32x4*>(src + 4);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    r[e] = bb ? fmaf(v0[e], kx[b], r[e]) : v0[e] * kx[b];
+                    r[e + 4] = bb ? fmaf(v1[e], kx[b], r[e + 4]) : v1[e] * kx[b];
+                }
+            }
+#pragma unroll
+            for (int e = 0; e < 8; ++e) acc[e] = aa ? fmaf(r[e], ky[a], acc[e]) : r[e] * ky[a];
+        }
+#pragma unroll
+        for (int e = 0; e < 8; ++e) o[e] = (f16)acc[e];
+    }
+    *reinterpret_cast<f16x8*>(table + i * 8) = o;
 }
 
 // x <- 0.5 x (1 + erf(x / sqrt 2)) in place (nn.GELU, the "gelu" activation of the Dinov2 MLP)
@@ -227,20 +288,26 @@ inline unsigned blocks_for(long n) { return (unsigned)((n + 255) / 256); }
 
 int launch_vit_front_end(const void* images, int dtype, int B, int H, int W, const VitResizePlan& pl, const float* mean, const float* stdv, double rescale,
                          int P, int G, int Kpad, unsigned char* tmp, f16* patches, unsigned char* crop, hipStream_t s) {
+    return launch_vit_front_end_hw(images, dtype, B, H, W, pl, mean, stdv, rescale, P, G, G, Kpad, tmp, patches, crop, s);
+}
+
+int launch_vit_front_end_hw(const void* images, int dtype, int B, int H, int W, const VitResizePlan& pl, const float* mean, const float* stdv, double rescale,
+                            int P, int Gh, int Gw, int Kpad, unsigned char* tmp, f16* patches, unsigned char* crop, hipStream_t s) {
     if (!images || !tmp || !patches || !mean || !stdv) CS_FAIL(CS_E_ARG, "vit front end: null pointer");
     if (dtype != CS_F16 && dtype != CS_F32) CS_FAIL(CS_E_UNSUPPORTED, "vit front end: images must be fp16 or fp32");
     if (B <= 0) return B < 0 ? CS_E_SHAPE : CS_OK;
-    const int cw = P * G, K = 3 * P * P;
+    if (P < 1 || Gh < 1 || Gw < 1 || (long)P * Gh > 0x7fff || (long)P * Gw > 0x7fff) CS_FAIL(CS_E_SHAPE, "vit front end: bad patch grid %d x %d of %d", Gh, Gw, P);
+    const int cw = P * Gw, K = 3 * P * P;
     // bounds of everything the two kernels index, checked on the host copy of the plan (vit.cpp builds both from one table)
     if (pl.row0 < 0 || pl.nrows <= 0 || pl.row0 + pl.nrows > H || pl.col_hi > W || pl.col_lo < 0 || Kpad < K || Kpad % 8)
         CS_FAIL(CS_E_SHAPE, "vit front end: resize plan does not fit a %d x %d image", H, W);
     const ResizeTab th{pl.h_lo, pl.h_cnt, pl.h_kk, pl.h_ksize}, tv{pl.v_lo, pl.v_cnt, pl.v_kk, pl.v_ksize};
-    const long n1 = (long)B * 3 * pl.nrows * cw, n2 = (long)B * G * G * Kpad;
+    const long n1 = (long)B * 3 * pl.nrows * cw, n2 = (long)B * Gh * Gw * Kpad;
     if (n1 > 0x7fffffffL * 256 || n2 > 0x7fffffffL * 256) CS_FAIL(CS_E_SHAPE, "vit front end: batch too large");
     if (dtype == CS_F16) hipLaunchKernelGGL(vit_hresize_kernel<f16>, dim3(blocks_for(n1)), dim3(256), 0, s, (const f16*)images, B * 3, H, W, pl.row0, pl.nrows, cw, th, tmp);
     else hipLaunchKernelGGL(vit_hresize_kernel<float>, dim3(blocks_for(n1)), dim3(256), 0, s, (const float*)images, B * 3, H, W, pl.row0, pl.nrows, cw, th, tmp);
     CS_CHECK_LAUNCH();
-    hipLaunchKernelGGL(vit_vresize_patch_kernel, dim3(blocks_for(n2)), dim3(256), 0, s, tmp, B, pl.row0, pl.nrows, cw, tv, P, G, K, Kpad, mean[0], mean[1], mean[2],
+    hipLaunchKernelGGL(vit_vresize_patch_kernel, dim3(blocks_for(n2)), dim3(256), 0, s, tmp, B, pl.row0, pl.nrows, cw, tv, P, Gh, Gw, K, Kpad, mean[0], mean[1], mean[2],
                        stdv[0], stdv[1], stdv[2], rescale, patches, crop);
     CS_CHECK_LAUNCH();
     return CS_OK;
@@ -250,6 +317,15 @@ int launch_vit_tokens(const f16* pe, const f16* cls, const f16* pos, f16* x, int
     if (!pe || !cls || !pos || !x || D % 8) CS_FAIL(CS_E_ARG, "vit tokens: pointers required, D %% 8 == 0");
     if (B <= 0) return B < 0 ? CS_E_SHAPE : CS_OK;
     hipLaunchKernelGGL(vit_tokens_kernel, dim3(blocks_for((long)B * (NP + 1) * (D / 8))), dim3(256), 0, s, pe, cls, pos, x, B, NP, D);
+    CS_CHECK_LAUNCH();
+    return CS_OK;
+}
+
+int launch_vit_pos_interp(const float* grid, int s, int gh, int gw, int D, f16* table, hipStream_t st) {
+    if (!grid || !table) CS_FAIL(CS_E_ARG, "vit position table: null pointer");
+    if (s < 1 || gh < 1 || gw < 1 || D < 8 || D % 8 || (long)gh * gw >= 0x7fffffffL / D) CS_FAIL(CS_E_SHAPE, "vit position table: bad grid %d -> %d x %d at D = %d", s, gh, gw, D);
+    const long total = ((long)gh * gw + 1) * (D / 8);
+    hipLaunchKernelGGL(vit_pos_interp_kernel, dim3(blocks_for(total)), dim3(256), 0, st, grid, s, gh, gw, D / 8, (float)s / (float)gh, (float)s / (float)gw, total, table);
     CS_CHECK_LAUNCH();
     return CS_OK;
 }

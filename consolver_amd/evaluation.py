@@ -75,19 +75,37 @@ def calculate_statistics(results):
 def score_image_pairs(image_pairs, reward_types=("image_psnr",), batch_size=16, device="cuda:0", reward_models=None):
     """-> {reward_type: [score per pair]} (compute_reward.py:98-330).  ``reward_models``: {reward_type: (model, processor)} as returned by
     ``reward_model.load_reward_model`` / ``load_depth_reward`` / ``load_segmentation_reward`` / ``load_inception_reward`` for the rewards that need a network ("dino", "clip", "depth",
-    "segmentation", "inception")."""
+    "segmentation", "inception").  The pairs of a chunk may differ in size (``group_by_size``); the scores come back in input order."""
     results = {}
     reward_models = reward_models or {}
     for rt in reward_types:
         scores = []
+        model, processor = reward_models.get(rt, (None, None))
         for s in range(0, len(image_pairs), batch_size):
             chunk = image_pairs[s:s + batch_size]
-            a = torch.stack([load_image_tensor(p, device) for p, _ in chunk])
-            b = torch.stack([load_image_tensor(q, device) for _, q in chunk])
-            model, processor = reward_models.get(rt, (None, None))
-            scores.extend(float(v) for v in ppo.calculate_reward(rt, model, processor, a, b, device).flatten().cpu())
+            a = [load_image_tensor(p, device) for p, _ in chunk]
+            b = [load_image_tensor(q, device) for _, q in chunk]
+            out = [None] * len(chunk)
+            for idx in group_by_size(a, b, chunk):
+                r = ppo.calculate_reward(rt, model, processor, torch.stack([a[i] for i in idx]), torch.stack([b[i] for i in idx]), device).flatten().cpu()
+                for i, v in zip(idx, r):
+                    out[i] = float(v)
+            scores.extend(out)
         results[rt] = scores
     return results
+
+
+def group_by_size(a, b, names=None):
+    """the positions of a chunk's pairs grouped by image size, each group in input order, the groups in order of first appearance: images of one size stack
+    into one batch (edits made at their inputs' aspect ratios come in many sizes).  A pair whose two images differ in size cannot be compared: ValueError
+    naming it (``names[i]``: its two files)."""
+    groups = {}
+    for i, (x, y) in enumerate(zip(a, b)):
+        if tuple(x.shape) != tuple(y.shape):
+            what = f"{names[i][0]} and {names[i][1]}" if names is not None else f"pair {i}"
+            raise ValueError(f"{what}: the two images of a pair differ in size ({tuple(x.shape[-2:])} vs {tuple(y.shape[-2:])})")
+        groups.setdefault(tuple(x.shape), []).append(i)
+    return list(groups.values())
 
 
 def write_results(output_path, results, config):

@@ -20,15 +20,15 @@ and the same tail on ``image_embeds``.  Weights load under their ``transformers.
 CLIPVisionModelWithProjection one).  The fp32 restatement lives in tests/clip_vision_oracle.py.
 
 ``depth`` (:92-96, :359-422; the reward the reference trains with by default): ``load_depth_reward()`` -> a ``HipDepthAnythingModel`` of the
-``depth-anything/Depth-Anything-V2-Small-hf`` shape and a ``DepthImageProcessor``; ``calculate_depth_reward`` runs the front end (PIL bicubic resize of the
-square image to 518 x 518, bit-identical on the uint8 image), the DINOv2-small backbone tapped at four depths, the DPT neck and head (cs_depth_forward),
+``depth-anything/Depth-Anything-V2-Small-hf`` shape and a ``DepthImageProcessor``; ``calculate_depth_reward`` runs the front end (PIL bicubic resize to the
+DPT processor's size for the image's aspect ratio -- 518 x 518 for a square, 518 x 700 for 880 x 1184 --, bit-identical on the uint8 image), the DINOv2-small backbone tapped at four depths, the DPT neck and head (cs_depth_forward),
 torch's bicubic resize back to the images' size with the per-map min / max normalisation (cs_depth_normalized_maps) and the PSNR tail
 (``ppo.depth_psnr_tail``).  Weights load under their ``transformers.DepthAnythingForDepthEstimation`` names.  The fp32 restatement lives in
 tests/depth_oracle.py.
 
 ``segmentation`` (:110-117, :425-481): ``load_segmentation_reward()`` -> a ``HipSegformerModel`` of the ``nvidia/segformer-b4-finetuned-ade-512-512`` shape
-and a ``SegImageProcessor``; ``calculate_segmentation_reward`` runs the front end (PIL BILINEAR resize of the square image to 512 x 512, bit-identical on the
-uint8 image), the MiT-B4 encoder and the all-MLP head (cs_seg_forward), the class argmax at a quarter of the processor's size (cs_seg_masks) and the
+and a ``SegImageProcessor``; ``calculate_segmentation_reward`` runs the front end (PIL BILINEAR resize of the image, whatever its aspect ratio, to 512 x 512,
+bit-identical on the uint8 image), the MiT-B4 encoder and the all-MLP head (cs_seg_forward), the class argmax at a quarter of the processor's size (cs_seg_masks) and the
 agreement tail 100 * mean(mask_pred == mask_target) (cs_seg_agreement).  Weights load under their ``transformers.SegformerForSemanticSegmentation`` names.
 The fp32 restatement lives in tests/segformer_oracle.py.
 
@@ -275,7 +275,7 @@ class HipCLIPVisionModel(_HipImageEncoder):
 class DepthImageProcessor:
     """The preprocessing constants of ``depth-anything/Depth-Anything-V2-Small-hf`` (its preprocessor_config.json, a DPTImageProcessor; from memory: no hub
     access here): resize to 518 x 518 with PIL BICUBIC under ``keep_aspect_ratio`` and ``ensure_multiple_of = 14`` (for a square input exactly
-    ``size`` x ``size``; other inputs are refused by the front end), no crop, no pad, rescale 1/255, normalise with the ImageNet mean / std.  A plain
+    ``size`` x ``size``; ``output_size`` gives the rule for every input), no crop, no pad, rescale 1/255, normalise with the ImageNet mean / std.  A plain
     holder: the arithmetic runs in ``HipDepthAnythingModel.preprocess``."""
     do_resize = do_rescale = do_normalize = keep_aspect_ratio = True
     do_pad = False
@@ -291,9 +291,20 @@ class DepthImageProcessor:
     def constants(self):
         return (self.size["height"], self.size["height"], self.rescale_factor, self.image_mean, self.image_std)
 
+    def output_size(self, height, width):
+        """the processed (height, width) of an input: transformers' ``get_resize_output_image_size`` with ``keep_aspect_ratio`` -- the scale closer to 1
+        serves both axes, each side is then rounded (Python's ``round``: half to even) to a multiple of ``ensure_multiple_of``.  880 x 1184 -> (518, 700)."""
+        m = self.ensure_multiple_of
+        scale_h, scale_w = self.size["height"] / height, self.size["width"] / width
+        if abs(1 - scale_w) < abs(1 - scale_h):
+            scale_h = scale_w
+        else:
+            scale_w = scale_h
+        return round(scale_h * height / m) * m, round(scale_w * width / m) * m
+
 
 class _DepthOutput(tuple):
-    """(predicted_depth,): ``outputs.predicted_depth`` [B, size, size] fp32, as transformers' DepthEstimatorOutput names it"""
+    """(predicted_depth,): ``outputs.predicted_depth`` [B, h, w] fp32 (the processed size), as transformers' DepthEstimatorOutput names it"""
     predicted_depth = property(lambda self: self[0])
 
 
@@ -322,40 +333,141 @@ class HipDepthAnythingModel(_HipImageModel):
         """patch rows -> ``predicted_depth`` [B, size, size] fp32, ``max_batch`` images per call"""
         return self._forward(patches, self.crop, self.crop)
 
+    # ---- any aspect ratio: the `_hw` entry points ---------------------------------------------------------------------
+    def processed_size(self, height, width):
+        """the (height, width) the front end resizes an input to (cs_depth_processed_size: the processor's rule; RuntimeError beyond the limits of
+        include/consolver_hip.h)"""
+        oh, ow = C.c_int(), C.c_int()
+        L.check(L.lib().cs_depth_processed_size(self._h, height, width, C.byref(oh), C.byref(ow)))
+        if (oh.value, ow.value) != tuple(self.processor.output_size(height, width)):
+            raise ValueError(f"the processor's size rule gives {self.processor.output_size(height, width)} for {height} x {width}, the front end "
+                             f"{(oh.value, ow.value)}: ensure_multiple_of must be the model's patch size")
+        return oh.value, ow.value
+
+    def preprocess_hw(self, images, return_crop=False):
+        """[B,3,H,W] fp16 / fp32 in [0,1], any aspect ratio -> (patch rows [B * gh * gw, patch_cols] fp16, (out_h, out_w)) and, with ``return_crop``, the
+        resized uint8 image [B,3,out_h,out_w] as a third item (what PIL hands the processor's rescale)"""
+        L.require_cuda(images, "images")
+        if images.dim() != 4 or images.shape[1] != 3:
+            raise ValueError(f"images must be [B,3,H,W], got {tuple(images.shape)}")
+        if images.dtype not in _DT:
+            raise TypeError(f"images must be float16 or float32 (the two quantisation paths that are built), got {images.dtype}")
+        images = images.contiguous()
+        B, _, H, W = images.shape
+        oh, ow = self.processed_size(H, W)
+        patches = torch.empty(B * (oh // self.patch) * (ow // self.patch), self.patch_cols, dtype=torch.float16, device=images.device)
+        crop = torch.empty(B, 3, oh, ow, dtype=torch.uint8, device=images.device) if return_crop else None
+        if B:
+            need = int(L.lib().cs_depth_preprocess_workspace_bytes_hw(self._h, B, H, W))
+            if self._pws is None or self._pws.numel() < need or self._pws.device != images.device:
+                self._pws = torch.empty(need, dtype=torch.uint8, device=images.device)
+            with torch.cuda.device(images.device):          # the resize tables of a new image size are allocated on the current device
+                L.check(L.lib().cs_depth_preprocess_hw(self._h, L.ptr(images), _DT[images.dtype], B, H, W, None, None, L.ptr(patches), L.ptr(crop),
+                                                       L.ptr(self._pws), self._pws.numel(), L.stream_ptr(images.device)))
+        return (patches, (oh, ow), crop) if return_crop else (patches, (oh, ow))
+
+    def depth_from_patches_hw(self, patches, size):
+        """patch rows of images processed to ``size`` = (out_h, out_w) -> ``predicted_depth`` [B, out_h, out_w] fp32.  Images per call: ``max_batch``,
+        and no more than ``workspace_budget`` holds of this size's workspace."""
+        if not self._finalized:
+            raise RuntimeError("weights not loaded")
+        L.require_cuda(patches, "patches")
+        oh, ow = size
+        per_image = int(L.lib().cs_depth_workspace_bytes_hw(self._h, 1, oh, ow))
+        if not per_image:
+            L.check(L.lib().cs_depth_forward_hw(self._h, None, 0, oh, ow, None, None, 0, None))          # raises with the library's reason for the refusal
+            raise RuntimeError(f"processed size {oh} x {ow} is not supported")
+        step = max(1, min(self.max_batch, self.workspace_budget // per_image))
+        n_rows = (oh // self.patch) * (ow // self.patch)
+        if patches.dim() != 2 or patches.shape[1] != self.patch_cols or patches.shape[0] % n_rows:
+            raise ValueError(f"patches must be [B * {n_rows}, {self.patch_cols}] for a {oh} x {ow} image, got {tuple(patches.shape)}")
+        patches = patches.contiguous()
+        B = patches.shape[0] // n_rows
+        out = torch.empty(B, oh, ow, dtype=torch.float32, device=patches.device)
+        with torch.cuda.device(patches.device):             # the position table of a new grid is allocated on the current device
+            for s in range(0, B, step):
+                n = min(step, B - s)
+                need = int(L.lib().cs_depth_workspace_bytes_hw(self._h, n, oh, ow))
+                if self._ws is None or self._ws.numel() < need or self._ws.device != patches.device:
+                    self._ws = torch.empty(need, dtype=torch.uint8, device=patches.device)
+                L.check(L.lib().cs_depth_forward_hw(self._h, L.ptr(patches[s * n_rows:]), n, oh, ow, L.ptr(out[s:]), L.ptr(self._ws), self._ws.numel(),
+                                                    L.stream_ptr(patches.device)))
+        return out
+
+    def flops_hw(self, batch, size):
+        return float(L.lib().cs_depth_flops_hw(self._h, batch, size[0], size[1]))
+
+    def position_table(self, gh, gw):
+        """-> (the position table [1 + gh * gw, hidden] fp16 the forward reads at a gh x gw patch grid, whether this call interpolated it on the device)"""
+        if not self._finalized:
+            raise RuntimeError("weights not loaded")
+        table = torch.empty(1 + gh * gw, self.config["hidden_size"], dtype=torch.float16, device=self.device)
+        launched = C.c_int(-1)
+        with torch.cuda.device(self.device):
+            L.check(L.lib().cs_depth_position_table(self._h, gh, gw, L.ptr(table), C.byref(launched), L.stream_ptr(self.device)))
+        return table, bool(launched.value)
+
+    def patches_to_pixel_values(self, patches, size=None):
+        """the patch rows back in the processor's layout: ``pixel_values`` [B,3,out_h,out_w] fp16 (``size``: the processed size; default the square one)"""
+        if size is None:
+            return super().patches_to_pixel_values(patches)
+        gh, gw, P = size[0] // self.patch, size[1] // self.patch, self.patch
+        B = patches.shape[0] // (gh * gw)
+        return patches[:, :3 * P * P].reshape(B, gh, gw, 3, P, P).permute(0, 3, 1, 4, 2, 5).reshape(B, 3, gh * P, gw * P)
+
+    def pixel_values_to_patches(self, pixel_values):
+        """``pixel_values`` [B,3,h,w], h and w multiples of the patch size -> the patch rows"""
+        P = self.patch
+        B, ch, h, w = pixel_values.shape
+        if ch != 3 or h % P or w % P or not h or not w:
+            raise ValueError(f"pixel_values must be [B,3,h,w] with h and w multiples of the patch size {P}, got {tuple(pixel_values.shape)}")
+        gh, gw = h // P, w // P
+        rows = pixel_values.to(torch.float16).reshape(B, 3, gh, P, gw, P).permute(0, 2, 4, 1, 3, 5).reshape(B * gh * gw, 3 * P * P)
+        out = rows.new_zeros(B * gh * gw, self.patch_cols)
+        out[:, :3 * P * P] = rows
+        return out
+
     @torch.no_grad()
     def __call__(self, pixel_values=None, **_ignored):
-        """``reward_model(**inputs)`` with the processor's ``pixel_values`` [B,3,size,size] -> see ``_DepthOutput``"""
+        """``reward_model(**inputs)`` with the processor's ``pixel_values`` [B,3,h,w] (h and w multiples of the patch size, as transformers takes them; the
+        processor's own square size runs the square entry point) -> see ``_DepthOutput``"""
         if pixel_values is None:
             raise ValueError("You have to specify pixel_values")
         L.require_cuda(pixel_values, "pixel_values")
-        return _DepthOutput((self.depth_from_patches(self.pixel_values_to_patches(pixel_values)),))
+        patches = self.pixel_values_to_patches(pixel_values)
+        size = tuple(pixel_values.shape[-2:])
+        return _DepthOutput((self.depth_from_patches(patches) if size == (self.crop, self.crop) else self.depth_from_patches_hw(patches, size),))
 
     def predicted_depth(self, images):
-        """[B,3,H,H] in [0,1] -> ``predicted_depth`` [B, size, size] fp32"""
+        """[B,3,H,W] in [0,1] -> ``predicted_depth`` [B, out_h, out_w] fp32 at the processed size (a square image: [B, size, size], the square entry points)"""
+        if images.dim() == 4 and images.shape[-1] != images.shape[-2]:
+            return self.depth_from_patches_hw(*self.preprocess_hw(images))
         return self.depth_from_patches(self.preprocess(images))
 
     def post_process(self, predicted_depth, height, width):
         """``post_process_depth_estimation(target_sizes=[(height, width)])`` (torch bicubic) and the reward's per-map (d - min) / (max - min + 1e-8):
-        [B, size, size] fp32 -> [B, height, width] fp32"""
+        [B, h, w] fp32 -> [B, height, width] fp32"""
         L.require_cuda(predicted_depth, "predicted_depth")
         d = predicted_depth.to(torch.float32).contiguous()
-        B = d.shape[0]
-        if tuple(d.shape[1:]) != (self.crop, self.crop):
-            raise ValueError(f"predicted_depth must be [B,{self.crop},{self.crop}], got {tuple(d.shape)}")
+        if d.dim() != 3 or not d.shape[1] or not d.shape[2]:
+            raise ValueError(f"predicted_depth must be [B,h,w], got {tuple(d.shape)}")
+        B, ih, iw = d.shape
         out = torch.empty(B, height, width, dtype=torch.float32, device=d.device)
-        if B:
+        if B and (ih, iw) == (self.crop, self.crop):
             L.check(self._fn("normalized_maps")(self._h, L.ptr(d), B, height, width, L.ptr(out), L.stream_ptr(d.device)))
+        elif B:
+            L.check(L.lib().cs_depth_normalized_maps_hw(self._h, L.ptr(d), B, ih, iw, height, width, L.ptr(out), L.stream_ptr(d.device)))
         return out
 
     def normalized_depth(self, images):
-        """[B,3,H,H] in [0,1] -> the normalised depth maps at the images' size, [B,H,H] fp32: the whole per-image path of the reward up to the PSNR"""
+        """[B,3,H,W] in [0,1] -> the normalised depth maps at the images' size, [B,H,W] fp32: the whole per-image path of the reward up to the PSNR"""
         return self.post_process(self.predicted_depth(images), images.shape[-2], images.shape[-1])
 
 
 class SegImageProcessor:
     """The preprocessing constants of ``nvidia/segformer-b4-finetuned-ade-512-512`` (its preprocessor_config.json, a SegformerImageProcessor; from memory: no
     hub access here): resize to 512 x 512 with PIL BILINEAR, no crop, rescale 1/255, normalise with the ImageNet mean / std, labels not reduced.  A plain
-    holder: the arithmetic runs in ``HipSegformerModel.preprocess`` (square inputs; others are refused by the front end)."""
+    holder: the arithmetic runs in ``HipSegformerModel.preprocess`` (square inputs) and ``preprocess_hw`` (any aspect ratio: stretched to the same size)."""
     do_resize = do_rescale = do_normalize = True
     do_reduce_labels = False
     resample = 2                                   # PIL.Image.BILINEAR
@@ -441,14 +553,37 @@ class HipSegformerModel(_HipImageModel):
         L.require_cuda(pixel_values, "pixel_values")
         return _SegOutput((self._run(self.pixel_values_to_patches(pixel_values), True, False)[0],))
 
+    def preprocess_hw(self, images, return_crop=False):
+        """``preprocess`` for images of any aspect ratio: the processor stretches them to size x size, so the outputs have the square call's shapes"""
+        L.require_cuda(images, "images")
+        if images.dim() != 4 or images.shape[1] != 3:
+            raise ValueError(f"images must be [B,3,H,W], got {tuple(images.shape)}")
+        if images.dtype not in _DT:
+            raise TypeError(f"images must be float16 or float32 (the two quantisation paths that are built), got {images.dtype}")
+        images = images.contiguous()
+        B, _, H, W = images.shape
+        patches = torch.empty(B * self.crop * self.crop, self.patch_cols, dtype=torch.float16, device=images.device)
+        crop = torch.empty(B, 3, self.crop, self.crop, dtype=torch.uint8, device=images.device) if return_crop else None
+        if B:
+            need = int(self._fn("preprocess_workspace_bytes")(self._h, B, H, W))
+            if self._pws is None or self._pws.numel() < need or self._pws.device != images.device:
+                self._pws = torch.empty(need, dtype=torch.uint8, device=images.device)
+            with torch.cuda.device(images.device):
+                L.check(L.lib().cs_seg_preprocess_hw(self._h, L.ptr(images), _DT[images.dtype], B, H, W, None, None, L.ptr(patches), L.ptr(crop), L.ptr(self._pws),
+                                                     self._pws.numel(), L.stream_ptr(images.device)))
+        return (patches, crop) if return_crop else patches
+
+    def _front_end(self, images):
+        return self.preprocess_hw(images) if images.dim() == 4 and images.shape[-1] != images.shape[-2] else self.preprocess(images)
+
     def logits_and_masks(self, images):
-        """[B,3,H,H] in [0,1] -> (logits [B, num_labels, g, g] fp32, masks [B, g, g] int32) of one pass"""
-        return self._run(self.preprocess(images), True, True)
+        """[B,3,H,W] in [0,1] -> (logits [B, num_labels, g, g] fp32, masks [B, g, g] int32) of one pass"""
+        return self._run(self._front_end(images), True, True)
 
     def masks(self, images):
-        """[B,3,H,H] in [0,1] -> the class masks [B, size / 4, size / 4] int32 (argmax of the logits, a tie to the lowest class): the whole per-image path of
+        """[B,3,H,W] in [0,1] -> the class masks [B, size / 4, size / 4] int32 (argmax of the logits, a tie to the lowest class): the whole per-image path of
         the reward up to the comparison"""
-        return self._run(self.preprocess(images), False, True)[1]
+        return self._run(self._front_end(images), False, True)[1]
 
 
 class InceptionImageProcessor:

@@ -683,7 +683,8 @@ int cs_depth_patch_cols(const CsDepth* d);
 int cs_depth_num_tokens(const CsDepth* d);
 size_t cs_depth_preprocess_workspace_bytes(const CsDepth* d, int batch, int height, int width);
 /* the image front end of cs_vit_preprocess with the DPT processor's rule: the whole image resized to size x size, no crop.  height != width (where the
- * processor's keep_aspect_ratio rule gives another shape): CS_E_UNSUPPORTED.  crop_u8 (may be NULL): the resized uint8 image [batch, 3, size, size] */
+ * processor's keep_aspect_ratio rule gives another shape): CS_E_UNSUPPORTED -- the output shape of this entry point implies the square grid;
+ * cs_depth_preprocess_hw takes any aspect ratio.  crop_u8 (may be NULL): the resized uint8 image [batch, 3, size, size] */
 int cs_depth_preprocess(CsDepth* d, const void* images, int dtype, int batch, int height, int width, void* patches,
                         unsigned char* crop_u8, void* workspace, size_t workspace_bytes, void* stream);
 /* patches from cs_depth_preprocess -> predicted_depth [batch, size, size] fp32 */
@@ -692,6 +693,37 @@ int cs_depth_forward(CsDepth* d, const void* patches, int batch, float* predicte
 /* post_process_depth_estimation + the reward's normalisation: predicted_depth [batch, size, size] fp32 -> torch-style bicubic (align_corners = False) to
  * height x width -> per map (d - min) / (max - min + 1e-8): maps [batch, height, width] fp32 */
 int cs_depth_normalized_maps(CsDepth* d, const float* predicted_depth, int batch, int height, int width, float* maps, void* stream);
+
+/* ---- images of any aspect ratio: the `_hw` entry points.  The square entry points above are their (size, size) case, bit for bit. ----
+ * Size rule: the DPT processor's with keep_aspect_ratio and ensure_multiple_of = patch_size.  scale_h = size / height, scale_w = size / width; the scale
+ * closer to 1 serves both axes; each side becomes round-half-even(scale * side / patch_size) * patch_size (in double, as the processor computes it).
+ * 880 x 1184 -> 518 x 700, 512 x 768 -> 518 x 784, 64 x 96 -> 350 x 518.
+ * Limits: height and width 1 .. 16384; each processed side 1 patch .. CS_DEPTH_MAX_SIDE_FACTOR * size (size 518: up to 1554, a 111-patch side; every aspect
+ * ratio up to 3:1 of images no smaller than the processor's size is inside, 672 x 1568 -> 518 x 1204 = 37 x 86 patches).  Beyond them every entry point
+ * below answers CS_E_UNSUPPORTED (the size_t ones 0) before any allocation or launch. */
+#define CS_DEPTH_MAX_SIDE_FACTOR 3
+int cs_depth_processed_size(const CsDepth* d, int height, int width, int* out_h, int* out_w);
+size_t cs_depth_preprocess_workspace_bytes_hw(const CsDepth* d, int batch, int height, int width);
+/* PIL BICUBIC on the uint8 image straight to out_h x out_w (the two axes on independent scales, no crop; bit-identical to Image.resize), rescale, normalise:
+ * patches [batch * (out_h / patch) * (out_w / patch)][patch_cols] fp16.  out_h / out_w (may be NULL): the processed size.  crop_u8 (may be NULL): the resized
+ * uint8 image [batch, 3, out_h, out_w].  The resize tables of an image size are built on its first call and kept (a bounded cache, shared with the square
+ * entry point's). */
+int cs_depth_preprocess_hw(CsDepth* d, const void* images, int dtype, int batch, int height, int width, int* out_h, int* out_w, void* patches,
+                           unsigned char* crop_u8, void* workspace, size_t workspace_bytes, void* stream);
+/* workspace and FLOPs of one cs_depth_forward_hw call at a processed size (multiples of patch_size within the limits) */
+size_t cs_depth_workspace_bytes_hw(const CsDepth* d, int batch, int out_h, int out_w);
+double cs_depth_flops_hw(const CsDepth* d, int batch, int out_h, int out_w);
+/* patches from cs_depth_preprocess_hw -> predicted_depth [batch, out_h, out_w] fp32.  A patch grid other than the training grid reads a position table that
+ * is interpolated on the device (torch's bicubic, align_corners = False, fp32 arithmetic, one rounding to fp16) from the trained fp32 grid the handle keeps,
+ * on the first call at that grid: one hipMalloc, one kernel and a stream synchronisation then; the handle keeps at most 16 tables and empties the cache when it
+ * is full.  The training grid reads the packed table and launches nothing more than cs_depth_forward. */
+int cs_depth_forward_hw(CsDepth* d, const void* patches, int batch, int out_h, int out_w, float* predicted_depth, void* workspace, size_t workspace_bytes,
+                        void* stream);
+/* cs_depth_normalized_maps for predicted_depth [batch, in_h, in_w] */
+int cs_depth_normalized_maps_hw(CsDepth* d, const float* predicted_depth, int batch, int in_h, int in_w, int height, int width, float* maps, void* stream);
+/* the position table [1 + gh * gw][hidden_size] fp16 the forward reads at a gh x gw patch grid (row 0, the class row, is zero: the packed CLS token carries
+ * it), copied to `table` (device memory); *kernel_launched (may be NULL): 1 when this call interpolated the table, 0 for the training grid or a cached table */
+int cs_depth_position_table(CsDepth* d, int gh, int gw, void* table, int* kernel_launched, void* stream);
 
 /* ------------------------------------------------------------------------
  * SegFormer mask-agreement reward (reward_type "segmentation": edit_ppo/reward_model.py:110-117, 425-481;
@@ -733,10 +765,16 @@ int cs_seg_patch_cols(const CsSeg* g);
 int cs_seg_num_tokens(const CsSeg* g);
 size_t cs_seg_preprocess_workspace_bytes(const CsSeg* g, int batch, int height, int width);
 /* the image front end of cs_vit_preprocess with the Segformer processor's rule: the whole image resized to size x size with PIL BILINEAR, no crop; `patches`
- * is the normalised image [batch * size * size][8] fp16 (NHWC, channels 3 .. 7 zero).  height != width: CS_E_UNSUPPORTED.  crop_u8 (may be NULL): the resized
+ * is the normalised image [batch * size * size][8] fp16 (NHWC, channels 3 .. 7 zero).  height != width: CS_E_UNSUPPORTED (cs_seg_preprocess_hw takes any
+ * aspect ratio).  crop_u8 (may be NULL): the resized
  * uint8 image [batch, 3, size, size] (an input of the processor's own size comes out byte-identical) */
 int cs_seg_preprocess(CsSeg* g, const void* images, int dtype, int batch, int height, int width, void* patches,
                       unsigned char* crop_u8, void* workspace, size_t workspace_bytes, void* stream);
+/* the same for an image of any aspect ratio: the Segformer processor stretches it to size x size (PIL BILINEAR, the two axes on independent scales, bit-identical
+ * to Image.resize), so *out_h = *out_w = size (may be NULL), the outputs have the square call's shapes and cs_seg_forward takes them as they are.  Workspace:
+ * cs_seg_preprocess_workspace_bytes of the same height and width */
+int cs_seg_preprocess_hw(CsSeg* g, const void* images, int dtype, int batch, int height, int width, int* out_h, int* out_w, void* patches,
+                         unsigned char* crop_u8, void* workspace, size_t workspace_bytes, void* stream);
 /* patches from cs_seg_preprocess -> logits [batch, num_labels, size / 4, size / 4] fp32 (NULL: not written; the fp16 logits stay in the workspace for cs_seg_masks) */
 int cs_seg_forward(CsSeg* g, const void* patches, int batch, float* logits, void* workspace, size_t workspace_bytes,
                    void* stream);

@@ -324,6 +324,11 @@ int cs_op_dpt_conv(const void* x, int B, int H, int W, int Cin, const void* w, c
 int cs_op_dpt_bilinear(const void* x, int B, int Hi, int Wi, int C, int Ho, int Wo, void* out, void* stream);
 /* y [B * (skip + G * G)][k * k * C] (column (ky * k + kx) * C + c) -> out [B][G k][G k][C]: the store of a kernel = stride transposed conv after its GEMM */
 int cs_op_dpt_pixel_shuffle(const void* y, int B, int G, int k, int C, int skip, void* out, void* stream);
+/* the same for a Gh x Gw token grid: y [B * (skip + Gh * Gw)][k * k * C] -> out [B][Gh k][Gw k][C] */
+int cs_op_dpt_pixel_shuffle_hw(const void* y, int B, int Gh, int Gw, int k, int C, int skip, void* out, void* stream);
+/* F.interpolate(mode="bicubic", align_corners=False, size=(gh, gw)) of a position grid [s][s][D] fp32 (device) -> table [1 + gh * gw][D] fp16, row 0 zero:
+ * fp32 arithmetic in torch's order, one rounding; D % 8 == 0 */
+int cs_op_vit_pos_interp(const float* grid, int s, int gh, int gw, int D, void* table, void* stream);
 /* out [M] fp32 = max(x [M][C] . w [C] + bias[0], 0) * scale */
 int cs_op_dpt_head(const void* x, int64_t M, int C, const void* w, const void* bias, float scale, float* out, void* stream);
 /* torch-style bicubic (A = -0.75, align_corners = False, no antialias) of fp32 maps [B][Hi][Wi] -> [B][Ho][Wo] */

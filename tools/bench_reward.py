@@ -3,8 +3,8 @@ medians of ``--reps`` runs after ``--warmup``; one JSON line at the end.
 
     python tools/bench_reward.py --reward dino  [--batch 80] [--reps 7] [--no-vae] [--out profiles/dino_reward_bench.txt]
     python tools/bench_reward.py --reward clip  [--batch 16] [--reps 7] [--out profiles/clip_reward_bench.txt]
-    python tools/bench_reward.py --reward depth [--batch 8]  [--reps 7] [--out profiles/depth_reward_bench.txt]
-    python tools/bench_reward.py --reward segmentation [--batch 4] [--reps 7] [--out profiles/segmentation_reward_bench.txt]
+    python tools/bench_reward.py --reward depth [--batch 8]  [--reps 7] [--height 880 --width 1184] [--out profiles/depth_reward_bench.txt]
+    python tools/bench_reward.py --reward segmentation [--batch 4] [--reps 7] [--height 880 --width 1184] [--out profiles/segmentation_reward_bench.txt]
     python tools/bench_reward.py --reward inception [--batch 4] [--reps 7] [--out profiles/inception_reward_bench.txt]
 
 * ``dino`` (config 5's batch, 80 + 80 images): front end (quantise + PIL-exact resize + crop + normalise + patch rows), encoder (12 layers, 257 tokens per
@@ -53,8 +53,14 @@ def timed(fn, warmup, reps):
     return sorted(ms)[len(ms) // 2]
 
 
+def image_hw(a):
+    """--height / --width (depth and segmentation: any aspect ratio), each defaulting to --size"""
+    return a.height or a.size, a.width or a.size
+
+
 def random_images(a, n):
-    return torch.rand(n, 3, a.size, a.size, device=DEV, dtype=torch.float16)
+    h, w = image_hw(a)
+    return torch.rand(n, 3, h, w, device=DEV, dtype=torch.float16)
 
 
 def bench_features(a, res, B, n):
@@ -94,33 +100,53 @@ def bench_depth(a, res, B, n):
     model, proc = load_depth_reward(device=DEV)
     model.load_state_dict(synth.synthetic_depth_anything_state_dict(model.manifest()))
     images = random_images(a, n)
-    patches = model.preprocess(images)
-    depth = model.depth_from_patches(patches)
-    maps = model.post_process(depth, a.size, a.size)
+    h, w = image_hw(a)
+    lines = []
+    if h == w:                                          # the square entry points
+        front_end, run = (lambda: model.preprocess(images)), model.depth_from_patches
+        patches, flops = front_end(), model.flops
+        res["workspace_mb_per_image"] = int(model._fn("workspace_bytes")(model._h, 1)) / 1e6
+        res["calls_hold"] = model.max_batch
+    else:                                               # the `_hw` entry points at the processed size of an h x w image
+        size = model.processed_size(h, w)
+        gh, gw = size[0] // model.patch, size[1] // model.patch
+        front_end, run = (lambda: model.preprocess_hw(images)[0]), (lambda p: model.depth_from_patches_hw(p, size))
+        patches, flops = front_end(), (lambda k: model.flops_hw(k, size))
+        res["processed_size"], res["patch_grid"] = list(size), [gh, gw]
+        res["workspace_mb_per_image"] = int(L.lib().cs_depth_workspace_bytes_hw(model._h, 1, size[0], size[1])) / 1e6
+        res["calls_hold"] = max(1, min(model.max_batch, int(model.workspace_budget // (res["workspace_mb_per_image"] * 1e6))))
+        # the position-table kernel alone, as a cache miss runs it (the handle keeps the table afterwards)
+        D, s = model.config["hidden_size"], model.config["image_size"] // model.patch
+        grid, table = torch.randn(s, s, D, device=DEV), torch.empty(1 + gh * gw, D, device=DEV, dtype=torch.float16)
+        st = L.stream_ptr(DEV)
+        res["position_table_kernel_ms"] = timed(lambda: L.check(L.lib().cs_op_vit_pos_interp(L.ptr(grid), s, gh, gw, D, L.ptr(table), st)), a.warmup, a.reps)
+        lines.append(f"  {h} x {w} -> {size[0]} x {size[1]}: {gh} x {gw} = {gh * gw} patches against {s} x {s} = {s * s} at the processor's own size; position table "
+                     f"{s} x {s} -> {gh} x {gw} on a cache miss: {res['position_table_kernel_ms']:.4f} ms (kernel alone)")
+    depth = run(patches)
+    maps = model.post_process(depth, h, w)
     res["max_batch"] = model.max_batch
-    res["front_end_ms"] = timed(lambda: model.preprocess(images), a.warmup, a.reps)
-    res["model_ms"] = timed(lambda: model.depth_from_patches(patches), a.warmup, a.reps)
-    res["post_process_ms"] = timed(lambda: model.post_process(depth, a.size, a.size), a.warmup, a.reps)
+    res["front_end_ms"] = timed(front_end, a.warmup, a.reps)
+    res["model_ms"] = timed(lambda: run(patches), a.warmup, a.reps)
+    res["post_process_ms"] = timed(lambda: model.post_process(depth, h, w), a.warmup, a.reps)
     res["tail_ms"] = timed(lambda: depth_psnr_tail(maps[:B], maps[B:]), a.warmup, a.reps)
     res["reward_call_ms"] = timed(lambda: calculate_depth_reward(model, proc, images[:B], images[B:], DEV), a.warmup, a.reps)
-    res["model_tflop"] = model.flops(n) / 1e12
-    res["model_tflops"] = model.flops(n) / res["model_ms"] / 1e9
-    res["workspace_mb_per_image"] = int(model._fn("workspace_bytes")(model._h, 1)) / 1e6
-    return [f"  front end     {res['front_end_ms']:9.3f} ms",
-            f"  model         {res['model_ms']:9.3f} ms  ({res['model_tflop']:.2f} TFLOP, {res['model_tflops']:.0f} TFLOP/s)",
-            f"  post-process  {res['post_process_ms']:9.3f} ms", f"  tail          {res['tail_ms']:9.3f} ms",
-            f"  calculate_depth_reward, whole call {res['reward_call_ms']:9.3f} ms"]
+    res["model_tflop"] = flops(n) / 1e12
+    res["model_tflops"] = flops(n) / res["model_ms"] / 1e9
+    return lines + [f"  front end     {res['front_end_ms']:9.3f} ms",
+                    f"  model         {res['model_ms']:9.3f} ms  ({res['model_tflop']:.2f} TFLOP, {res['model_tflops']:.0f} TFLOP/s)",
+                    f"  post-process  {res['post_process_ms']:9.3f} ms", f"  tail          {res['tail_ms']:9.3f} ms",
+                    f"  calculate_depth_reward, whole call {res['reward_call_ms']:9.3f} ms"]
 
 
 def bench_segmentation(a, res, B, n):
     model, proc = load_segmentation_reward(device=DEV)
     model.load_state_dict(synth.synthetic_segformer_state_dict(model.manifest()))
     images = random_images(a, n)
-    patches = model.preprocess(images)
+    patches = model._front_end(images)                  # a non-square image is stretched to the processor's size: the model's shapes do not change
     _, masks = model._run(patches, False, True)
     lib = L.lib()
     res["max_batch"] = model.max_batch
-    res["front_end_ms"] = timed(lambda: model.preprocess(images), a.warmup, a.reps)
+    res["front_end_ms"] = timed(lambda: model._front_end(images), a.warmup, a.reps)
     upto = []
     try:
         for parts in range(1, 6):                      # the forward stopped after stage 1 .. 4, then with the head
@@ -138,7 +164,7 @@ def bench_segmentation(a, res, B, n):
     res["model_tflops"] = model.flops(n) / res["model_ms"] / 1e9
     res["workspace_mb_per_image"] = int(model._fn("workspace_bytes")(model._h, 1)) / 1e6
     # the depthwise 3x3 + GELU kernel alone at the stage-1 shape: [n][size / 4][size / 4][4 * 64] halfs in, the same out
-    g, C = a.size // 4, 4 * model.config["hidden_sizes"][0]
+    g, C = model.grid, 4 * model.config["hidden_sizes"][0]
     x = torch.randn(n, g, g, C, device=DEV, dtype=torch.float16)
     w, bias, out = torch.randn(9, C, device=DEV, dtype=torch.float16) / 3, torch.randn(C, device=DEV, dtype=torch.float16), torch.empty_like(x)
     st = L.stream_ptr(DEV)
@@ -206,6 +232,8 @@ def main():
     ap.add_argument("--reward", choices=sorted(DEFAULT_BATCH), required=True)
     ap.add_argument("--batch", type=int, default=None, help="pred / target pairs (default: 80 dino, 16 clip, 8 depth, 4 segmentation, 4 inception)")
     ap.add_argument("--size", type=int, default=512)
+    ap.add_argument("--height", type=int, default=None, help="depth / segmentation: image height (default --size)")
+    ap.add_argument("--width", type=int, default=None, help="depth / segmentation: image width (default --size)")
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--no-vae", action="store_true", help="dino: skip the VAE decode of the same images")
@@ -213,10 +241,12 @@ def main():
     a = ap.parse_args()
     B = a.batch if a.batch is not None else DEFAULT_BATCH[a.reward]
     n = 2 * B
-    res = {"batch_pairs": B, "images": n, "size": a.size}
+    h, w = image_hw(a)
+    res = {"batch_pairs": B, "images": n, "size": a.size, "height": h, "width": w}
     stages = {"depth": bench_depth, "segmentation": bench_segmentation, "inception": bench_inception}.get(a.reward, bench_features)(a, res, B, n)
     model_name = {"clip": ", ViT-L/14", "segmentation": ", SegFormer-B4", "inception": ", Inception-v3 at 299"}.get(a.reward, "")
-    lines = [f"{a.reward} reward, {n} images ({B} pred + {B} target) at {a.size}^2 fp16{model_name}, synthetic weights, medians of {a.reps}"] + stages
+    shape = f"{h}^2" if h == w else f"{h} x {w}"
+    lines = [f"{a.reward} reward, {n} images ({B} pred + {B} target) at {shape} fp16{model_name}, synthetic weights, medians of {a.reps}"] + stages
     lines.append(json.dumps(res))
     text = "\n".join(lines)
     print(text)
