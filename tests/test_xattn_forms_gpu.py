@@ -1,5 +1,6 @@
 """The six instantiations of the fused cross-attention block (csrc/xattn.hip: xattn_block_kernel<0|1|2> on 128-row tiles, xattn64_kernel<0|1|2> on 64-row tiles; 0 plain
-fp16 stream, 1 split-fp16, 2 hi + e5m2 lo8) through the C ABI -- cs_op_xattn_block, cs_op_xattn_block_x2, cs_op_xattn_block_lo8 -- against a float64 reference of the
+fp16 stream, 1 split-fp16, 2 hi + e5m2 lo8; the two tile sizes are two kernel bodies over one set of per-wave phase functions and differ in the wave grid, the
+weight-stage geometry of the GEMMs and V as one tile or two half tiles) through the C ABI -- cs_op_xattn_block, cs_op_xattn_block_x2, cs_op_xattn_block_lo8 -- against a float64 reference of the
 same rounded inputs, per (row, head) of the attention output and per row of the branch, at every mask boundary of the key layout, on exact families whose planes are
 known bit for bit, across the forms bit for bit, on the row statistics, and at the launcher's rejections.  tests/xattn_ref.py holds the references and the families.
 
