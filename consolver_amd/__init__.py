@@ -14,6 +14,8 @@ from .factor_net import FactorNetPPO, FluxFactorNetPPO  # noqa: F401
 from .scheduling_dpm import DPMSolverMultistepScheduler, SD15_MULTISTEP_DPM_KWARGS  # noqa: F401
 from .scheduling_unipc import UniPCMultistepScheduler, SD15_UNIPC_KWARGS  # noqa: F401
 from .scheduling_amed import AMEDSolverScheduler, SD15_AMED_KWARGS  # noqa: F401
+from .scheduling_deis import DEISMultistepScheduler, SD15_DEIS_KWARGS  # noqa: F401
+from .scheduling_pndm import PNDMScheduler, SD15_PNDM_KWARGS  # noqa: F401
 from .fid import FIDStatistics, HipFIDInception, compute_fid, frechet_distance, load_fid_inception  # noqa: F401
 from .ppo_flux import (as_rollout_noise, collect_rollout_flux, compute_advantages_flux, decode_latents_flux,  # noqa: F401
                        train_iteration_flux)

@@ -13,6 +13,7 @@ LIB_PATH = os.environ.get("CONSOLVER_HIP_LIB") or os.path.join(PKG, "libconsolve
 
 CS_F32, CS_F16, CS_BF16, CS_U8 = 0, 1, 2, 3
 CS_MAX_ORDER = 8
+CS_LIN_MAX_TERMS = 4
 _DT = {torch.float32: CS_F32, torch.float16: CS_F16, torch.bfloat16: CS_BF16}
 
 
@@ -37,6 +38,13 @@ class CsDpmStepArgs(C.Structure):
                 ("B", C.c_int), ("elems", C.c_int64), ("io_dtype", C.c_int), ("out_dtype", C.c_int), ("x_is_f32", C.c_int),
                 ("x_out", C.c_void_p), ("m_out", C.c_void_p), ("x_out_lp", C.c_void_p), ("lp_dtype", C.c_int),
                 ("conv_x", C.c_float), ("conv_e", C.c_float), ("cx", C.c_float), ("c0", C.c_float), ("c1", C.c_float)]
+
+
+class CsLinStepArgs(C.Structure):
+    _fields_ = [("x", C.c_void_p), ("eps_text", C.c_void_p), ("eps_uncond", C.c_void_p), ("guidance", C.c_float), ("x_base", C.c_void_p),
+                ("hist", C.c_void_p * (CS_LIN_MAX_TERMS - 1)), ("terms", C.c_int), ("B", C.c_int), ("elems", C.c_int64), ("io_dtype", C.c_int),
+                ("out_dtype", C.c_int), ("x_is_f32", C.c_int), ("x_out", C.c_void_p), ("m_out", C.c_void_p), ("x_out_lp", C.c_void_p),
+                ("lp_dtype", C.c_int), ("conv_x", C.c_float), ("conv_e", C.c_float), ("cx", C.c_float), ("c", C.c_float * CS_LIN_MAX_TERMS)]
 
 
 class CsUnipcStepArgs(C.Structure):
@@ -140,6 +148,7 @@ SYMBOLS = {
     "cs_lms_ddim_step": (C.c_int, [C.POINTER(CsStepArgs), C.c_void_p]),
     "cs_lms_euler_step": (C.c_int, [C.POINTER(CsStepArgs), C.c_void_p]),
     "cs_dpm_multistep_step": (C.c_int, [C.POINTER(CsDpmStepArgs), C.c_void_p]),
+    "cs_linear_step": (C.c_int, [C.POINTER(CsLinStepArgs), C.c_void_p]),
     "cs_unipc_step": (C.c_int, [C.POINTER(CsUnipcStepArgs), C.c_void_p]),
     "cs_fm_general_step": (C.c_int, [C.POINTER(CsFmStepArgs), C.c_void_p]),
     "cs_true_cfg_combine": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_int, C.c_int64, C.c_void_p]),

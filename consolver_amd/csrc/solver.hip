@@ -5,6 +5,7 @@
 //   cs_lms_euler_step : same with the flow-matching Euler epilogue
 //                       (edit_ppo/scheduler_fmppo.py:400-436)
 //   cs_dpm_multistep_step : CFG combine + model-output conversion + Multistep DPM-Solver update (orders 1, 2)
+//   cs_linear_step : CFG combine + model-output conversion + an n-term linear update, n <= 4 (DEIS, iPNDM)
 //   cs_unipc_step : CFG combine + x0 conversion + UniPC corrector of the previous update + predictor (bh1 / bh2, orders 1, 2)
 //   cs_fm_general_step : the flow-matching baselines' update (Euler / Heun / dpm-solver / multistep, edit_ppo/scheduler_fm.py:405-482)
 //   cs_true_cfg_combine : true classifier-free guidance of the Kontext edit, neg + scale * (pos - neg) (edit_ppo/pipeline.py:1115)
@@ -261,6 +262,61 @@ struct DpmStep {
     }
 };
 
+// ---------------------------------------------------------------- n-term linear update (DEIS, iPNDM)
+// x' = cx xb + c[0] m0 + c[1] hist[0] + ... + c[terms - 1] hist[terms - 2], left to right: DEIS up to order 3 and iPNDM's Adams-Bashforth
+// combinations up to four terms, all variant logic in host scalars (scheduling_deis.py, scheduling_pndm.py).  m0 is the converted model output
+// as in the dpm step, except that the identity conversion is skipped; xb is x, or a saved sample that the update restarts from (iPNDM's
+// second forward at the first grid point).
+struct LinParams {
+    const void* x; const void* ec; const void* eu; float g;
+    const void* xb;
+    const void* hist[CS_LIN_MAX_TERMS - 1];
+    int terms, convert;
+    void* x_out; void* m_out;
+    float conv_x, conv_e, cx, c[CS_LIN_MAX_TERMS];
+    void* x_lp;  // as StepParams::x_lp
+    int lp_bf16;
+};
+
+// h[k].get(j) is element j of history entry k: loaded, and converted and read here, for k < terms - 1 only
+template <typename TI, int W>
+__device__ __forceinline__ float lin_one(const LinParams& p, float xb, float m0, const Raw<TI, W> (&h)[CS_LIN_MAX_TERMS - 1], int j) {
+    float r = p.cx * xb + p.c[0] * m0;
+#pragma unroll
+    for (int k = 1; k < CS_LIN_MAX_TERMS; ++k)
+        if (k < p.terms) r = r + p.c[k] * h[k - 1].get(j);
+    return r;
+}
+
+template <typename TI, typename TX, typename TO>
+struct LinStep {
+    typedef LinParams Params;
+    static constexpr int V = Io<TI>::VEC;
+    __device__ __forceinline__ LinStep(const LinParams&, int) {}
+    template <int W>
+    __device__ __forceinline__ void step(const LinParams& p, int64_t i) const {
+        Raw<TX, W> rx, rb;
+        Raw<TI, W> re, ru, rh[CS_LIN_MAX_TERMS - 1];
+        rx.load(p.x, i);
+        if (p.xb) rb.load(p.xb, i);
+        re.load(p.ec, i);
+        if (p.eu) ru.load(p.eu, i);
+#pragma unroll
+        for (int k = 0; k < CS_LIN_MAX_TERMS - 1; ++k)
+            if (k < p.terms - 1) rh[k].load(p.hist[k], i);   // (lin_one reads entry k under the same condition)
+        float x[W], b[W], e[W], u[W], o[W];
+        rx.unpack(x); re.unpack(e);
+        if (p.eu) { ru.unpack(u); cfg_combine<TI>(e, u, p.g); }
+        if (p.convert) convert_output<TI>(e, x, p.conv_x, p.conv_e);
+        if (p.m_out) store<TI, W>(p.m_out, i, e);
+        if (p.xb) rb.unpack(b);
+#pragma unroll
+        for (int j = 0; j < W; ++j) o[j] = lin_one<TI>(p, p.xb ? b[j] : x[j], e[j], rh, j);
+        store<TO, W>(p.x_out, i, o);
+        if (p.x_lp) store_lp<W>(p.x_lp, i, o, p.lp_bf16);
+    }
+};
+
 // ---------------------------------------------------------------- UniPC (bh1 / bh2, orders 1 and 2, x0 prediction)
 // One step of UniPC is the corrector of the PREVIOUS update (it needs this step's model output) followed by this step's predictor.  Both are
 // linear in the same tensors, so the step is one pass: the variant lives in nine host scalars (scheduling_unipc.py).  x is the predicted sample
@@ -480,6 +536,47 @@ int launch_dpm_step(const CsDpmStepArgs* a, void* stream) {
     // per sample like launch_step, so a ragged b * elems is accepted and no alignment is checked
     return with_step_dtypes(a->io_dtype, x_f32(a), a->out_dtype == CS_F32, [&](auto ti, auto tx, auto to) {
         return launch_stream<DpmStep<TYPE_OF(ti), TYPE_OF(tx), TYPE_OF(to)>>(p, a->B, a->elems, stream);
+    });
+}
+
+int launch_lin_step(const CsLinStepArgs* a, void* stream) {
+    bool empty;
+    if (int rc = refuse_common(a, &empty)) return rc;
+    if (!empty && (!a->x || !a->eps_text || !a->x_out)) CS_FAIL(CS_E_ARG, "x, eps_text and x_out are required");
+    const int io = a->io_dtype, od = a->out_dtype;
+    if (a->x_is_f32 && io == CS_F32) CS_FAIL(CS_E_DTYPE, "x_is_f32 marks an fp32 sample beside 16-bit model outputs (io_dtype %d is fp32 already)", io);
+    if (x_f32(a) && od != CS_F32) CS_FAIL(CS_E_DTYPE, "an fp32 sample gives an fp32 result (out_dtype %d)", od);
+    if (a->terms < 1 || a->terms > CS_LIN_MAX_TERMS) CS_FAIL(CS_E_ARG, "terms %d out of range [1,%d]", a->terms, CS_LIN_MAX_TERMS);
+    if (empty) return CS_OK;
+    for (int k = 0; k < a->terms - 1; ++k)
+        if (!a->hist[k]) CS_FAIL(CS_E_ARG, "hist[%d] is NULL but terms=%d", k, a->terms);
+    const bool identity = (a->conv_x == 0.f && a->conv_e == 1.f);
+    if ((a->eps_uncond || !identity) && !a->m_out)
+        CS_FAIL(CS_E_ARG, "m_out is required with CFG or a model-output conversion (the converted output is the history entry)");
+    LinParams p;
+    p.x = a->x; p.ec = a->eps_text; p.eu = a->eps_uncond; p.g = a->guidance;
+    p.xb = a->x_base;
+    // a history tensor is read only where a term uses it
+    for (int k = 0; k < CS_LIN_MAX_TERMS - 1; ++k) p.hist[k] = k < a->terms - 1 ? a->hist[k] : nullptr;
+    p.terms = a->terms; p.convert = !identity;
+    p.x_out = a->x_out; p.m_out = a->m_out;
+    p.conv_x = a->conv_x; p.conv_e = a->conv_e; p.cx = a->cx;
+    for (int k = 0; k < CS_LIN_MAX_TERMS; ++k) p.c[k] = a->c[k];
+    p.x_lp = a->x_out_lp; p.lp_bf16 = a->lp_dtype == CS_BF16;
+    uintptr_t bits = (uintptr_t)a->x | (uintptr_t)a->x_base | (uintptr_t)a->eps_text | (uintptr_t)a->eps_uncond | (uintptr_t)a->x_out | (uintptr_t)a->m_out;
+    bool out_aliased = a->x_out == a->x || a->x_out == a->x_base || a->x_out == a->eps_text || a->x_out == a->eps_uncond, m_aliased = false;
+    for (int k = 0; k < a->terms - 1; ++k) {
+        bits |= (uintptr_t)p.hist[k];
+        out_aliased = out_aliased || a->x_out == p.hist[k];
+        m_aliased = m_aliased || (a->m_out && a->m_out == p.hist[k]);
+    }
+    if (out_aliased) CS_FAIL(CS_E_ARG, "x_out aliases an input");
+    if (m_aliased) CS_FAIL(CS_E_ARG, "m_out aliases a history entry that this step reads");
+    // 16-byte loads / stores on every tensor (two per lane on an fp32 state next to 16-bit outputs; the 16-bit copy of a 4-wide fp32 result is 8 bytes)
+    if ((bits & 15) || ((uintptr_t)a->x_out_lp & (io == CS_F32 ? 7 : 15)))
+        CS_FAIL(CS_E_ARG, "x, x_base, eps_*, hist, m_out, x_out and x_out_lp must be 16-byte aligned");
+    return with_step_dtypes(io, x_f32(a), od == CS_F32, [&](auto ti, auto tx, auto to) {
+        return launch_stream<LinStep<TYPE_OF(ti), TYPE_OF(tx), TYPE_OF(to)>>(p, 1, (int64_t)a->B * a->elems, stream);
     });
 }
 
@@ -775,6 +872,7 @@ int cs_lms_ddim_step(const CsStepArgs* args, void* stream) { return launch_step<
 int cs_lms_euler_step(const CsStepArgs* args, void* stream) { return launch_step<true>(args, stream); }
 int cs_dpm_multistep_step(const CsDpmStepArgs* args, void* stream) { return launch_dpm_step(args, stream); }
 int cs_unipc_step(const CsUnipcStepArgs* args, void* stream) { return launch_unipc_step(args, stream); }
+int cs_linear_step(const CsLinStepArgs* args, void* stream) { return launch_lin_step(args, stream); }
 int cs_fm_general_step(const CsFmStepArgs* args, void* stream) { return launch_fm_step(args, stream); }
 int cs_true_cfg_combine(const void* pos, const void* neg, int in_dtype, float scale, void* out, int out_dtype, int64_t n, void* stream) {
     return launch_true_cfg(pos, neg, in_dtype, scale, out, out_dtype, n, stream);

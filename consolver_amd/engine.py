@@ -70,7 +70,8 @@ class SDSamplingEngine:
         key = (B, tuple(shape), str(device), self.latents_dtype, self.eps_dtype)
         if self._bufs is None or self._bufs["key"] != key:
             cfg = self.scheduler.config
-            # (DPMSolverMultistepScheduler keeps `solver_order` converted outputs; UniPCMultistepScheduler reads that many and writes one more: history_slots)
+            # (DPMSolverMultistepScheduler keeps `solver_order` converted outputs; UniPCMultistepScheduler reads that many and writes one more, DEISMultistepScheduler
+            # and PNDMScheduler say how many the slot written must stay clear of: history_slots)
             order = cfg.get("order_dim") or getattr(self.scheduler, "history_slots", None) or cfg["solver_order"]
             C, H, W = shape
             self._graph = self._graph_key = None      # a captured graph holds the OLD buffers' addresses (latents_dtype is a public attribute and part of the key)
@@ -99,7 +100,8 @@ class SDSamplingEngine:
     def _loop(self, ctx, bufs, n, B, do_cfg):
         sch, unet = self.scheduler, self.unet
         self._base_mode = getattr(unet, "residual", None)
-        self._n_steps = n
+        # one forward per entry of scheduler.timesteps: num_inference_steps of them for every scheduler but PNDMScheduler, whose table repeats its second entry
+        self._n_steps = len(sch.timesteps)
         try:
             return self._loop_steps(ctx, bufs, n, B, do_cfg)
         finally:
@@ -111,7 +113,7 @@ class SDSamplingEngine:
         x = bufs["lat"][0]
         cur = 0
         t_dev = self._t_dev
-        for i in range(n):
+        for i in range(self._n_steps):
             if self.forward_events is not None:
                 a = torch.cuda.Event(enable_timing=True); b = torch.cuda.Event(enable_timing=True)
                 a.record()

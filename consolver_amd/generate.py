@@ -89,6 +89,23 @@ def make_scheduler(solver, order_dim=4, scaler_dim=0, use_conv=False, num_action
     raise ValueError(f"unknown solver {solver!r}; expected one of {SOLVERS}")
 
 
+# the reference's own flag (gen_ppo.py:402): the learned solver and the training-free methods of its results table
+TYPES = ("consistencysolver", "unipc", "deis", "ipndm", "multistep-dpmsolver", "amed")
+
+
+def make_type_scheduler(type, order_dim=4, scaler_dim=0, use_conv=False, num_actions=11, amed_schedule=None):
+    """``gen_ppo.load_pipeline(type=...)`` by the reference's own names: DEIS (gen_ppo.py:139-143) and iPNDM (:144-148) on SD1.5's schedule;
+    a type that is also a ``--solver`` value is ``make_scheduler``'s."""
+    import consolver_amd
+    if type == "deis":
+        return consolver_amd.DEISMultistepScheduler(**consolver_amd.SD15_DEIS_KWARGS)
+    if type == "ipndm":
+        return consolver_amd.PNDMScheduler(**consolver_amd.SD15_PNDM_KWARGS)
+    if type not in TYPES:
+        raise ValueError(f"unknown type {type!r}; expected one of {TYPES}")
+    return make_scheduler(type, order_dim, scaler_dim, use_conv, num_actions, amed_schedule)
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--out", required=True)
@@ -104,16 +121,29 @@ def parse_args(argv=None):
     ap.add_argument("--num-actions", type=int, default=11)
     ap.add_argument("--use_conv", "--use-conv", dest="use_conv", action="store_true",
                     help="gen_ppo.py:399: the policy also sees the cosine-similarity features of the eps history (factor_net_ppo.py:72-73,146-149)")
-    ap.add_argument("--solver", default="consistencysolver", choices=SOLVERS,
+    class Solver(argparse.Action):                # (--solver as it was; remembers that it was given, for --type)
+        def __call__(self, parser, namespace, values, option_string=None):
+            namespace.solver, namespace.solver_given = values, True
+    ap.set_defaults(solver_given=False)
+    ap.add_argument("--solver", default="consistencysolver", choices=SOLVERS, action=Solver,
                     help="gen_ppo.load_pipeline(type=...): the learned solver (default), the Multistep-DPM-Solver, UniPC or AMED baseline, or DDIM; the baselines have no policy")
+    ap.add_argument("--type", default=None, choices=TYPES,
+                    help="gen_ppo.py:402, by the reference's names: the learned solver, or the UniPC, DEIS, iPNDM, Multistep-DPM-Solver or AMED baseline; a type that "
+                         "is also a --solver value means the same")
     ap.add_argument("--amed-schedule", help="--solver amed: JSON file of the AMED tables {\"<steps>\": {\"amed\": [...], \"grad_scale\": [...], \"time_scale\": [...]}}")
     ap.add_argument("--residual", default="f16x2", choices=["f16", "f16x2", "residual_fp32"],
                     help="residual-stream storage of the UNet executor (include/consolver_hip.h): f16x2 meets the 1e-3 latent gate, f16 is ~8 %% faster")
     args = ap.parse_args(argv)
-    if args.solver != "consistencysolver" and (args.policy or args.use_conv):
-        ap.error(f"--policy / --use_conv belong to the learned solver; --solver {args.solver} has no policy")
-    if (args.solver == "amed") != bool(args.amed_schedule):
-        ap.error("--amed-schedule FILE.json goes with --solver amed, and only with it")
+    if args.type is not None:
+        if args.solver_given and args.solver != args.type:
+            ap.error(f"--type {args.type} and --solver {args.solver} name different solvers; give one of them")
+        if args.type in SOLVERS:
+            args.solver = args.type
+    method = args.type or args.solver
+    if method != "consistencysolver" and (args.policy or args.use_conv):
+        ap.error(f"--policy / --use_conv belong to the learned solver; {'--type' if args.type else '--solver'} {method} has no policy")
+    if (method == "amed") != bool(args.amed_schedule):
+        ap.error("--amed-schedule FILE.json goes with --solver amed (--type amed), and only with it")
     return args
 
 
@@ -142,7 +172,8 @@ def main(argv=None, *, unet=None, vae=None):
             unet.load_state_dict(_load_sd(args.unet))
             vae.load_state_dict(_load_sd(args.vae))
         prompts, pe, ne = load_prompt_cache(args.prompt_cache)
-    sch = make_scheduler(args.solver, args.order_dim, args.scaler_dim, args.use_conv, args.num_actions, args.amed_schedule)
+    sch = (make_type_scheduler if args.type else make_scheduler)(args.type or args.solver, args.order_dim, args.scaler_dim, args.use_conv, args.num_actions,
+                                                                 args.amed_schedule)
     if sch.factor_net is not None:
         if args.policy:
             sch.factor_net.load_state_dict(torch.load(args.policy, map_location="cpu"))
@@ -161,7 +192,7 @@ def main(argv=None, *, unet=None, vae=None):
     if dist is not None:
         dist.destroy_process_group()
     return {"images": n, "use_conv": bool(sch.factor_net.use_conv) if sch.factor_net is not None else False, "residual": unet.residual, "seconds": secs,
-            "solver": args.solver}
+            "solver": args.type or args.solver}
 
 
 if __name__ == "__main__":

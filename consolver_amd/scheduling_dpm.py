@@ -34,7 +34,7 @@ SD15_MULTISTEP_DPM_KWARGS = dict(beta_start=0.00085, beta_end=0.012, beta_schedu
 class SigmaGridMixin:
     """what the sigma-parametrised multistep schedulers (this module, scheduling_unipc.py, scheduling_amed.py) share: the beta tables, the
     timestep / sigma grid of diffusers 0.26.3's ``set_timesteps``, the step counter and the protocol stubs.  The class needs ``config`` with
-    ``num_train_timesteps``, ``timestep_spacing``, ``steps_offset`` and ``final_sigmas_type``."""
+    ``num_train_timesteps``, ``timestep_spacing`` and ``steps_offset``; ``final_sigmas_type`` is read where the class has it."""
 
     def _init_tables(self, beta_schedule, beta_start, beta_end, num_train_timesteps, trained_betas):
         self._betas = tables.make_betas(beta_schedule, beta_start, beta_end, num_train_timesteps, trained_betas)
@@ -84,7 +84,7 @@ class SigmaGridMixin:
         ac = self._ac.astype(np.float64)
         s = np.sqrt((1.0 - ac) / ac)
         sig = np.interp(ts, np.arange(T), s)
-        last = s[0] if cfg.final_sigmas_type == "sigma_min" else 0.0
+        last = s[0] if cfg.get("final_sigmas_type", "sigma_min") == "sigma_min" else 0.0      # (a class without the key, DEIS, ends on the sigma of timestep 0)
         self._sigmas = np.concatenate([sig, [last]]).astype(np.float32)
         self.sigmas = torch.from_numpy(self._sigmas)
         self.num_inference_steps = n

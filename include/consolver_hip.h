@@ -179,6 +179,45 @@ typedef struct CsDpmStepArgs {
 int cs_dpm_multistep_step(const CsDpmStepArgs* args, void* stream);
 
 /* ------------------------------------------------------------------------
+ * n-term linear update (DEIS, iPNDM; consolver_amd/scheduling_deis.py, scheduling_pndm.py).
+ * A multistep update with up to four model outputs and host coefficients:
+ *     eps = eps_uncond ? round_io(u + guidance * (c - u)) : c
+ *     m0  = round_io(conv_x * x + conv_e * eps)        skipped when (conv_x, conv_e) == (0, 1); written to m_out
+ *     xb  = x_base ? x_base : x
+ *     x'  = cx * xb + c[0] * m0 + c[1] * hist[0] + ... + c[terms - 1] * hist[terms - 2]
+ * in fp32, left to right, rounded once to out_dtype.  Pointer, dtype and x_out_lp fields mean what they
+ * mean in CsDpmStepArgs.  A tensor whose pointer is NULL is not read; hist[k] with k >= terms - 1 is not read.
+ * All [B, elems] tensors are contiguous and 16-byte aligned (one flat range of B * elems elements).
+ * Aliasing: x_out aliases no input; m_out aliases no history entry that is read.
+ * Refused before any launch: terms outside 1..CS_LIN_MAX_TERMS, a NULL among the first terms - 1 history
+ * pointers, x_is_f32 with fp32 io, an fp32 sample with a 16-bit result, and what cs_dpm_multistep_step refuses.
+ * ---------------------------------------------------------------------- */
+#define CS_LIN_MAX_TERMS 4
+typedef struct CsLinStepArgs {
+    const void* x;            /* [B, elems] current sample (io_dtype, or fp32 when x_is_f32) */
+    const void* eps_text;     /* [B, elems] model output (conditional branch)       */
+    const void* eps_uncond;   /* [B, elems] unconditional branch, or NULL (no CFG)  */
+    float guidance;
+    const void* x_base;       /* [B, elems] the sample the update starts from (dtype of x), or NULL: x */
+    const void* hist[CS_LIN_MAX_TERMS - 1]; /* earlier converted outputs, newest first; the first terms - 1 are read */
+    int terms;                /* model outputs in the update, 1..CS_LIN_MAX_TERMS   */
+    int B;
+    int64_t elems;            /* elements per sample                                */
+    int io_dtype;             /* dtype of eps_*, hist, m_out (and of x, x_base unless x_is_f32) */
+    int out_dtype;            /* dtype of x_out                                     */
+    int x_is_f32;             /* the sample is fp32 beside 16-bit model outputs (an error with fp32 io) */
+    void* x_out;              /* [B, elems]                                         */
+    void* m_out;              /* [B, elems] m0; required when eps_uncond != NULL or
+                                 (conv_x, conv_e) != (0, 1), else optional           */
+    void* x_out_lp;           /* optional 16-bit copy of an fp32 result, as CsStepArgs::x_out_lp */
+    int lp_dtype;
+    float conv_x, conv_e, cx;
+    float c[CS_LIN_MAX_TERMS];
+} CsLinStepArgs;
+
+int cs_linear_step(const CsLinStepArgs* args, void* stream);
+
+/* ------------------------------------------------------------------------
  * UniPC update (bh1 / bh2, orders 1 and 2, x0 prediction; consolver_amd/scheduling_unipc.py).
  * One step is the corrector of the PREVIOUS update, which needs this step's model output, and this
  * step's predictor from the corrected sample -- one pass, the variant in nine host scalars:

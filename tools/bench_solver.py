@@ -11,6 +11,11 @@ as hipGraph replays of 500 captured launches (a Python launch loop measures the 
 updated in place, the fp16 copy of the result in the same pass: 16 bytes read and 12 written per element -- next to cs_dpm_multistep_step (18 bytes per
 element) on the same tensors and the 1 GiB device copy, timed in the same run by the same captured-graph method as ``--dpm``.
 
+``--lin``: the n-term linear update of DEIS and iPNDM (cs_linear_step) in the engine's form -- fp32 state, fp16 model outputs, CFG, the fp16 copy of
+the result in the same pass -- at B = 16 and 80 of SD's 4 x 64 x 64 latents for terms = 1..4 (16 + 2 (terms - 1) bytes per element), and at terms = 2
+alternating in the same process with cs_dpm_multistep_step at order 2 on the same tensors (the same 18 bytes per element), by the captured-graph method
+of ``--dpm``, next to the 1 GiB device copy.
+
 ``--fm``: the flow-matching baselines' update (cs_fm_general_step; Euler form x + dt v, Heun form x + c (v1 + v2)) at FLUX's packed latent size
 [1, 4096, 64] bf16 next to cs_lms_euler_step with a history of one on the same tensors, timed the same way in the same run as the 1 GiB copy.  At
 0.5 MB per tensor the kernels are launch-latency-bound: the figure is microseconds per launch, not a share of a roofline."""
@@ -173,6 +178,53 @@ def run_fm(B=1, elems=4096 * 64):
                          MB=round(nbytes / 1e6, 2), GBps=round(nbytes / us / 1e3, 1), copy_1gib_GBps=round(copy_gbps, 1)))
     return rows
 
+
+def run_lin(elems=4 * 64 * 64):
+    src = torch.randn(1 << 28, device=dev); dst = torch.empty_like(src)
+    copy_gbps = 2.0 * (1 << 30) / time_us(lambda: dst.copy_(src), 20) / 1e3
+    del src, dst
+    rows = []
+    for B in (16, 80):
+        h = lambda: torch.randn(B, elems, device=dev).half()
+        x, out = torch.randn(B, elems, device=dev), torch.empty(B, elems, device=dev)
+        eu, ec, mo, lp = h(), h(), h(), h()
+        hist = [h() for _ in range(3)]
+        d = L.CsDpmStepArgs()
+        d.x, d.eps_text, d.eps_uncond, d.guidance, d.m_prev = x.data_ptr(), ec.data_ptr(), eu.data_ptr(), 3.0, hist[0].data_ptr()
+        d.B, d.elems, d.io_dtype, d.out_dtype, d.x_is_f32 = B, elems, L.CS_F16, L.CS_F32, 1
+        d.x_out, d.m_out, d.x_out_lp, d.lp_dtype = out.data_ptr(), mo.data_ptr(), lp.data_ptr(), L.CS_F16
+        d.conv_x, d.conv_e, d.cx, d.c0, d.c1 = 0.0, 1.0, 1.02, -0.21, 0.07
+        lins = {}
+        for terms in (1, 2, 3, 4):
+            a = L.CsLinStepArgs()
+            a.x, a.eps_text, a.eps_uncond, a.guidance = x.data_ptr(), ec.data_ptr(), eu.data_ptr(), 3.0
+            for k in range(terms - 1): a.hist[k] = hist[k].data_ptr()
+            a.terms, a.B, a.elems, a.io_dtype, a.out_dtype, a.x_is_f32 = terms, B, elems, L.CS_F16, L.CS_F32, 1
+            a.x_out, a.m_out, a.x_out_lp, a.lp_dtype = out.data_ptr(), mo.data_ptr(), lp.data_ptr(), L.CS_F16
+            a.conv_x, a.conv_e, a.cx = 0.0, 1.0, 1.02
+            for k, c in enumerate((-0.21, 0.07, -0.03, 0.01)[:terms]): a.c[k] = c
+            lins[terms] = a
+        # x, eps_u, eps_c, hist | x', m0, fp16 copy of x'
+        kernels = [("cs_dpm_multistep_step_o2", lib.cs_dpm_multistep_step, d, 18), ("cs_linear_step_t2", lib.cs_linear_step, lins[2], 18)]
+        kernels += [(f"cs_linear_step_t{t}", lib.cs_linear_step, lins[t], 16 + 2 * (t - 1)) for t in (1, 3, 4)]
+        times = {name: [] for name, _, _, _ in kernels}
+        for _ in range(5):                                    # alternate the kernels; report the median window and the spread
+            for name, fn, args, _ in kernels:
+                times[name].append(graph_us(lambda: L.check(fn(C.byref(args), L.stream_ptr(dev)))))
+        for name, _, _, bpe in kernels:
+            us, nbytes = sorted(times[name])[2], bpe * B * elems
+            rows.append(dict(kernel=name, B=B, elems=elems, state="float32", outputs="float16", cfg=True, bytes_per_elem=bpe, us=round(us, 2),
+                             us_min_max=[round(min(times[name]), 2), round(max(times[name]), 2)], MB=round(nbytes / 1e6, 2),
+                             GBps=round(nbytes / us / 1e3, 1), copy_1gib_GBps=round(copy_gbps, 1), share_of_copy_rate=round(nbytes / us / 1e3 / copy_gbps, 3)))
+        dpm, lin = times["cs_dpm_multistep_step_o2"], times["cs_linear_step_t2"]
+        rows.append(dict(B=B, lin_t2_over_dpm_o2_time=round(sorted(lin)[2] / sorted(dpm)[2], 3), dpm_spread=round(max(dpm) / min(dpm), 3),
+                         lin_spread=round(max(lin) / min(lin), 3)))
+    return rows
+
+
+if "--lin" in sys.argv:
+    for r in run_lin(): print(json.dumps(r))
+    sys.exit(0)
 
 if "--fm" in sys.argv:
     for r in run_fm(): print(json.dumps(r))
