@@ -20,15 +20,13 @@
 //   * double-buffered LDS (64-72 KB -> 2 workgroups per CU), next tile's DMA is issued before the
 //     current tile's MFMAs; blockIdx is remapped so that each XCD (private L2) owns a contiguous
 //     run of tiles and the n-tiles of one pixel tile run back to back on it.
-#include "ops.h"
+#include "igemm_plan.h"      // the routing decision and the constants it shares with the kernels (BM, BK, HALO_ROWS_MAX, the LDS sizes)
 #include <stdlib.h>
+#include <atomic>
 #include <type_traits>
 
 
 namespace {
-
-constexpr int BM = 128;
-constexpr int BK = 64;
 
 __device__ __attribute__((aligned(256))) unsigned g_zero_page[64];
 
@@ -146,7 +144,7 @@ __device__ __forceinline__ void bias_tile_prologue(const IgemmParams& p, char* t
 //            and 1/8 of the activation rows through its L2 -- right when the activations dominate the bytes (the 64 x 64 / 32 x 32 levels);
 //   pn  > 0: the XCDs form an (8 / pn) x pn grid over (row tiles, column tiles): an XCD streams 1/pn of the weights and pn/8 of the activations.  At the
 //            16 x 16 / 8 x 8 levels the weights ARE the bytes (1280 x 1280 x 9: 29.5 MB against 5-21 MB of activations) and the contiguous order pulled them
-//            into all eight L2s: 8.3x / 3.9x the algorithmic bytes (profiles/r04_pmc_traffic_by_kernel.txt).  The host picks pn (launch_igemm_impl).
+//            into all eight L2s: 8.3x / 3.9x the algorithmic bytes (profiles/r04_pmc_traffic_by_kernel.txt).  The host picks pn (igemm_plan).
 __device__ __forceinline__ void tile_of(int bid, int nblk, int tiles_n, int gm, int pn, int& tm, int& tn) {
     const int xcd = bid & 7, slot = bid >> 3;
     if (pn > 0) {
@@ -469,7 +467,7 @@ __device__ __forceinline__ void igemm_epilogue_impl(const IgemmParams& p, f32x4 
 #pragma unroll
                         for (int r = 0; r < 8; ++r) f[r] += (float)t[r];
                         if (p.res_lo) {                       // split-fp16 residual stream: value = hi + lo
-                            if constexpr (LO8) {                // (the byte-plane family's kernels only ever see byte planes: launch_igemm_impl)
+                            if constexpr (LO8) {                // (the byte-plane family's kernels only ever see byte planes: igemm_plan)
                                 lo8_decode_add(f, *reinterpret_cast<const u32x2_t*>(reinterpret_cast<const unsigned char*>(p.res_lo) + off));
                             } else {
                                 const f16x8 t2 = *reinterpret_cast<const f16x8*>(p.res_lo + off);
@@ -586,9 +584,9 @@ template <bool GEGLU, int NT, int MT, int GROUP, class RowMap, int RSPLIT = 1, i
 __device__ __forceinline__ void igemm_epilogue(const IgemmParams& p, f32x4 (&acc)[NT][MT], const RowMap& rows, int n_base, int lane, char* wave_lds, char* ln_tab = nullptr, const char* ln_rows = nullptr) {
     if constexpr (LNM == 2) {                           // row statistics come from the fp32 values: always the fp32-patch path
         igemm_epilogue_f32<GEGLU, NT, MT, GROUP, RowMap, RSPLIT * 2, 2, EFAST, EPI>(p, acc, rows, n_base, lane, wave_lds, ln_tab, ln_rows);
-    } else if constexpr (LNM == 1) {                    // a folded LayerNorm's consumer adds nothing after the product (launch_igemm_impl checks)
+    } else if constexpr (LNM == 1) {                    // a folded LayerNorm's consumer adds nothing after the product (igemm_plan checks)
         igemm_epilogue_impl<GEGLU, NT, MT, GROUP, RowMap, RSPLIT, false, 1, 0, EFAST>(p, acc, rows, n_base, lane, wave_lds, ln_tab, ln_rows);
-    } else if constexpr (EPI != 0) {                    // (these families always add something: launch_igemm_impl routes only such layers here)
+    } else if constexpr (EPI != 0) {                    // (these families always add something: igemm_plan routes only such layers here)
         igemm_epilogue_f32<GEGLU, NT, MT, GROUP, RowMap, RSPLIT * 2, 0, EFAST, EPI>(p, acc, rows, n_base, lane, wave_lds, ln_tab, ln_rows);
     } else {
         if constexpr (!GEGLU) {
@@ -630,7 +628,6 @@ struct HaloParams {
                             // 2 + group B's DMA issues among its MFMAs
 };
 
-constexpr int HALO_ROWS_MAX = 400;
 #ifndef CS_HALO_NWB
 #define CS_HALO_NWB 3
 #endif
@@ -1352,7 +1349,7 @@ __global__ __launch_bounds__(512, 2) void conv3_lw_kernel(HaloParams p) {
     __builtin_amdgcn_s_barrier();                                               // E
     if (btab) __builtin_amdgcn_s_barrier();                                     // E2: loader wave 0 has put the tile's bias values into LDS
     if constexpr (SUB) {
-        // (launch_igemm_impl: never split-K) the tile's rows are INPUT pixels; phase (py, px) writes output pixels (2 y + py, 2 x + px)
+        // (igemm_plan: never split-K) the tile's rows are INPUT pixels; phase (py, px) writes output pixels (2 y + py, 2 x + px)
         const SubRows rows{wm * 64, b0, y0, x0, p.B, p.Ho, p.Wo, p.tw_shift, p.trw_shift, phase >> 1, phase & 1, phase * ((p.Ho * p.Wo) >> 8)};
         igemm_epilogue<false, NT, MT, NT, SubRows, 2, 0, true>(p.e, acc, rows, n_blk, lane, smem + w * 11264, btab ? smem + 4 * 11264 : nullptr);
         return;
@@ -1382,7 +1379,7 @@ __global__ __launch_bounds__(512, 2) void conv3_lw_kernel(HaloParams p) {
 // conv3_lw_kernel (round 3): tile 256 rows x 160 columns, waves 0-3 multiply (wave tile 64 x 160: 80 MFMAs, 28 hand-counted LDS reads, no vector ALU per
 // step), waves 4-7 stage [256 + 160 rows][64 k] = 52 KB per step into one of THREE stage buffers (156 of the CU's 160 KB), two steps ahead.
 // With ONE tile per CU and the operands in L2 / Infinity Cache this form is latency-free; as a general GEMM it loses to the 256 x 320 tile (twice the
-// L2 -> LDS bytes per FLOP: profiles/r03_ab_gemm_lw.txt), so launch_igemm_impl uses it only where gemm_big_kernel<false, 160> used to run.
+// L2 -> LDS bytes per FLOP: profiles/r03_ab_gemm_lw.txt), so igemm_plan uses it only where gemm_big_kernel<false, 160> used to run.
 // ------------------------------------------------------------------------------------------------
 template <int LNM = 0, int EPI = 0>
 __global__ __launch_bounds__(512, 2) void gemm_lw_kernel(IgemmParams p) {
@@ -1711,10 +1708,7 @@ __device__ __forceinline__ void dma16_uncounted(unsigned lds_dst, unsigned voff,
 __device__ __forceinline__ void mfma_first(f32x4& c, const f16x8& a, const f16x8& b) {
     asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, 0" : "=&v"(c) : "v"(a), "v"(b));
 }
-constexpr int AS_SLICE = 32 * 640, AS_RING = 3, AS_PATCH = 8192;
-// dynamic LDS: the ring, eight patches, 512 x (rstd, mean rstd), the (b' | s) tables (or the bias)
-static inline size_t gemm_as_lds(int N) { return (size_t)AS_RING * AS_SLICE + 8 * AS_PATCH + 512 * 8 + (size_t)N * 8; }
-constexpr int AS_MAX_N = (160 * 1024 - AS_RING * AS_SLICE - 8 * AS_PATCH - 512 * 8) / 8;      // = 4096
+// (AS_SLICE, AS_RING, AS_PATCH, the dynamic LDS gemm_as_lds(N) and AS_MAX_N: igemm_plan.h)
 
 template <bool GEGLU, int LNM>
 __global__ __launch_bounds__(512) void gemm_as_kernel(IgemmParams p) {
@@ -2048,9 +2042,9 @@ __global__ __launch_bounds__(256) void splitk_reduce_stats_kernel(IgemmParams p,
     }
 }
 
-// the reduce behind a split-K launch.  With p.gn_stats set (statistics wanted and allowed: launch_igemm_impl) and one 64-row statistics slot per sample it also
+// the reduce behind a split-K launch.  With p.gn_stats set (statistics wanted and allowed: igemm_plan) and one 64-row statistics slot per sample it also
 // leaves the GroupNorm statistics: reduce_leaves_stats(p) tells the caller that no statistics pass is needed.
-static bool reduce_leaves_stats(const IgemmParams& p) { return p.gn_stats && p.HoWo == 64 && p.M % 64 == 0 && p.N % 32 == 0 && !(p.debug & 64); }      // (debug bit 64: A/B against the statistics pass)
+static bool reduce_leaves_stats(const IgemmParams& p) { return splitk_reduce_leaves_stats(p.gn_stats != nullptr, p.HoWo, p.M, p.N, p.debug); }
 static int launch_splitk_reduce(const IgemmParams& p, const float* partial, int splits, hipStream_t s) {
     if (reduce_leaves_stats(p)) {
         hipLaunchKernelGGL(splitk_reduce_stats_kernel, dim3(p.N / 32, p.M / 64), dim3(256), 0, s, p, partial, splits, p.gn_stats);
@@ -2383,373 +2377,117 @@ __global__ __launch_bounds__(256, 2) void igemm_kernel(IgemmParams p) {
     igemm_epilogue<GEGLU, NT, MT, NT, LinearRows, 1, LNM, false, EPI>(p, acc, LinearRows{m_blk + wm * 64, p.M}, n_blk + wn * (BN / 2), lane, smem + w * 11264, LNM == 1 ? smem + 4 * 11264 + w * 1280 : nullptr);
 }
 
-template <int BN, bool CONV3, bool GEGLU, int LNM = 0, int EPI = 0>
-int launch_variant(const IgemmParams& p, hipStream_t s, int splits = 1) {
-    constexpr size_t lds = 2 * (BM * BK * 2 + BN * BK * 2);
-    static bool configured = false;
-    auto kfn = igemm_kernel<BN, CONV3, GEGLU, LNM, EPI>;
-    if (!configured) {
-        CS_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        configured = true;
-    }
-    hipLaunchKernelGGL(kfn, dim3(p.nblk, splits), dim3(256), lds, s, p);
-    CS_CHECK_LAUNCH();
-    if (splits > 1) return launch_splitk_reduce(p, (const float*)p.partial, splits, s);
-    return CS_OK;
-}
-
 }  // namespace
 
-// extra dynamic LDS of the folded-LayerNorm consumer instantiations (ln_tile_prologue): 256 rows x 8 B + the (b' | s) tables
-constexpr size_t LN_LDS_W8 = 256 * 8 + 2 * 2 * 160 * 4, LN_LDS_LW = 256 * 8 + 2 * 160 * 4;
-
-// tile_of's pn for a launch of tiles_m x tiles_n tiles that reads a_bytes of activations and w_bytes of weights once each algorithmically: per-XCD L2s mean the
-// contiguous order fetches a + 8 w, an (8 / pn) x pn grid pn a + (8 / pn) w.  Switch only for a clear gain (the contiguous order has the banded walk, IgemmParams::gm).
-static int choose_xcd_grid(int tiles_m, int tiles_n, double a_bytes, double w_bytes) {
-    if (!tune().xcd_grid) return 0;
-    int best = 0; double best_cost = 0.85 * (a_bytes + 8.0 * w_bytes);
-    for (int pn = 2; pn <= 8; pn *= 2) {
-        const int px = 8 / pn;
-        if (tiles_n % pn || tiles_m % px) continue;
-        const double cost = pn * a_bytes + px * w_bytes;
-        if (cost < best_cost) { best_cost = cost; best = pn; }
-    }
-    return best;
-}
-
+// ---- host side: igemm_plan (igemm_plan.h) decides; what follows fills the kernel parameters from the plan, launches from the kernel tables and runs the tail ---------
 double igemm_flops(const IgemmArgs& a) {
     const double M = (double)a.B * a.Ho * a.Wo;
     return 2.0 * M * a.N * (double)a.taps * (a.c0 + a.c1);
 }
 
-// one halo-conv instantiation per (upsample, tile width, k halves)
-template <bool UP, int BN, int KH, int SCHED>
-static int launch_halo_sched(const HaloParams& h, dim3 grid, size_t lds, hipStream_t s) {
-    static bool configured = false;
-    if (!configured) {
-        constexpr size_t max_lds = 2 * (HALO_ROWS_MAX * 128) + 3 * (160 * 128);
-        CS_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(conv3_halo_kernel<UP, BN, KH, SCHED>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)max_lds));
-        configured = true;
-    }
-    hipLaunchKernelGGL((conv3_halo_kernel<UP, BN, KH, SCHED>), grid, dim3(512), lds, s, h);
-    CS_CHECK_LAUNCH();
-    return CS_OK;
-}
-// the k32-step kernels (KH = 2: BN 320 / 256) run schedule 2 (priority + interleaved DMA for the staggered group: -6 ... -11 %, profiles/r02_ab_conv_sched.txt), the
-// k64-step kernels (BN 160 / 128) the lock-step schedule 0 (schedule 2 cost them 3 %); the other combinations were measured in round 2 and are not compiled any more
-template <bool UP, int BN, int KH>
-static int launch_halo(const HaloParams& h, dim3 grid, size_t lds, hipStream_t s) { return launch_halo_sched<UP, BN, KH, KH == 2 ? 2 : 0>(h, grid, lds, s); }
-
-struct LaunchInfo { bool gn_done = false; int row_groups = 0; };    // what the chosen kernel's epilogue left: GroupNorm statistics / row statistics in N / row_groups-column groups
-// the route record of this launch (IgemmRoute, ops.h): one host store per launch site
-static inline void route_set(int family, int tile_cols, int variant, int splits = 1) { t_igemm_route.family = family; t_igemm_route.tile_cols = tile_cols; t_igemm_route.variant = variant; t_igemm_route.splits = splits; }
-static int launch_igemm_impl(const IgemmArgs& a, hipStream_t s, LaunchInfo* li) {
+static void fill_params(const IgemmArgs& a, const TuneSet& t, const IgemmPlan& pl, IgemmParams& p) {
     const int cin = a.c0 + a.c1;
-    if (!a.a0 || !a.w || !a.out) CS_FAIL(CS_E_ARG, "igemm: a0, w, out required");
-    if (a.taps != 1 && a.taps != 9) CS_FAIL(CS_E_ARG, "igemm: taps must be 1 or 9");
-    if (cin % BK || a.c0 % BK || (a.c1 && !a.a1)) CS_FAIL(CS_E_SHAPE, "igemm: channels (%d,%d) must be multiples of %d", a.c0, a.c1, BK);
-    if (a.B <= 0 || a.Ho <= 0 || a.Wo <= 0) return (a.B < 0) ? CS_E_SHAPE : CS_OK;
-    if (a.taps == 1 && (a.stride != 1 || a.upsample || a.Hi != a.Ho || a.Wi != a.Wo)) CS_FAIL(CS_E_ARG, "igemm: 1x1 needs stride 1, no upsample");
-    // gemm_as_kernel (knob gemm_as): a K = 320 linear layer with a bias or folded-LayerNorm epilogue (GEGLU or not) and nothing else -- one A source, no lo plane, no
-    // time embedding / residual / lo plane out / statistics -- N a multiple of the 32-row weight slice that fits the LDS tables (which also keeps the weight buffer's
-    // 32-bit offsets in range), debug off.  The activation-size condition is gemm_w8_kernel's 32-bit-offset rule, kept so that the two routes cover the same shapes;
-    // this kernel itself reaches activations and outputs through 64-bit pointers.
-    // Auto: at least 192 512-row workgroups (the 64 x 64 level at batch >= 24; below that the 256 x 320 / 256 x 160 tiles have more workgroups to fill the chip with)
-    // and N >= 960 (QKV, the GEGLU projection): the N = 320 projections are at the HBM roof on gemm_w8_kernel and stay there.
-    const long long as_m = (long long)a.B * a.Ho * a.Wo;
-    const bool as_route = tune().gemm_as != 0 && a.taps == 1 && a.c1 == 0 && cin == 320 && !a.a0_lo && !a.temb && !a.res && !a.out_lo && !a.row_stats && !a.gn_stats &&
-                          a.N > 0 && a.N % 32 == 0 && a.N <= AS_MAX_N && !tune().debug && (double)as_m * 640 < 4.0e9 &&
-                          (tune().gemm_as == 2 || ((as_m + 511) / 512 >= 192 && a.N >= 960));
-    if (!as_route && a.geglu && (a.N % 256) && (a.N % 320)) CS_FAIL(CS_E_SHAPE, "igemm: GEGLU needs N %% 256 == 0 or N %% 320 == 0 (N=%d)", a.N);
-    IgemmParams p;
     p.a0 = a.a0; p.a1 = a.a1; p.c0 = a.c0; p.c1 = a.c1;
     p.Hi = a.Hi; p.Wi = a.Wi; p.Ho = a.Ho; p.Wo = a.Wo; p.HoWo = a.Ho * a.Wo;
     p.stride = a.stride; p.upsample = a.upsample; p.pad_lo = a.pad_after_only ? 0 : 1;
-    if (a.pad_after_only && !(a.taps == 9 && a.stride == 2)) CS_FAIL(CS_E_ARG, "igemm: pad_after_only is the stride-2 3x3 form");
-    p.M = a.B * a.Ho * a.Wo; p.N = a.N; p.cpt = cin / BK; p.KT = a.taps * p.cpt; p.Ktot = a.taps * cin;
-    p.w = a.w; p.bias = a.bias; p.temb = a.temb; p.temb_stride = a.temb_stride; p.res = a.res; p.out = a.out;
-    p.res_lo = a.res ? a.res_lo : nullptr; p.out_lo = a.out_lo; p.lo8 = (a.lo8 && (p.res_lo || p.out_lo)) ? 1 : 0;
-    const bool conv3_early = a.taps == 9;
+    p.M = pl.M; p.N = a.N; p.KT = pl.KT; p.cpt = cin / BK; p.Ktot = a.taps * cin;
+    p.w = pl.uses_w_up_sub ? a.w_up_sub : a.w; p.bias = a.bias; p.temb = a.temb; p.temb_stride = a.temb_stride; p.res = a.res; p.out = a.out;
+    p.res_lo = a.res ? a.res_lo : nullptr; p.out_lo = a.out_lo; p.lo8 = pl.lo8;
+    p.a0_lo = a.a0_lo; p.a1_lo = a.c1 ? a.a1_lo : nullptr; p.KTh = pl.KTh;
     p.row_stats = a.row_stats;
     p.ln_stats = a.ln_stats; p.ln_groups = a.ln_groups; p.ln_inv_c = 1.0f / (float)cin; p.ln_eps = a.ln_eps; p.ln_s = a.ln_s; p.ln_b = a.ln_b;
-    if (a.ln_stats) {
-        if (a.taps != 1 || a.c1 || a.temb || a.res || a.out_lo || a.row_stats || a.gn_stats)
-            CS_FAIL(CS_E_ARG, "igemm: a folded LayerNorm (ln_stats) is the epilogue of a plain linear layer (one source, no temb / residual / lo plane / statistics)");
-        if (!a.ln_s || !a.ln_b || a.ln_groups < 1) CS_FAIL(CS_E_ARG, "igemm: ln_stats needs ln_s, ln_b and ln_groups >= 1");
+    p.tiles_n = pl.tiles_n; p.nblk = pl.nblk; p.gm = pl.gm; p.pn = pl.pn;
+    p.partial = (pl.uses_splitk_ws && pl.route.family == FAM_IGEMM) ? a.splitk_ws : nullptr;     // igemm_kernel's partial sums (the conv kernels': HaloParams::partial)
+    p.gn_stats = pl.gn_by_epilogue ? a.gn_stats : nullptr;
+    p.epi_fast = t.epi_fast; p.debug = t.debug;
+}
+// h.e (the epilogue view) is filled already
+static void fill_halo(const IgemmArgs& a, const IgemmPlan& pl, HaloParams& h) {
+    h.e.row_stats = nullptr;                            // (row statistics of a conv output: the pass in launch_igemm)
+    h.x = a.a0; h.w = h.e.w; h.Cin = a.c0 + a.c1; h.H = a.Hi; h.W = a.Wi; h.B = a.B; h.NC = h.Cin / BK; h.Ho = a.Ho; h.Wo = a.Wo;
+    h.tw_shift = pl.tw_shift; h.trw_shift = pl.trw_shift; h.PX = pl.PX; h.PP = pl.PP;
+    h.HALO_W = pl.HALO_W; h.HALO_IMG = pl.HALO_IMG; h.NHALO = pl.NHALO; h.NQ = pl.NQ;
+    h.splits = pl.route.splits; h.partial = pl.route.family == FAM_SUB ? nullptr : a.splitk_ws; h.sched = pl.sched;
+}
+
+// One table per family in the order of the family's slot function (igemm_plan.h); every entry with the most dynamic LDS a launch of it may ask for.  These are all
+// the instantiations there are: a combination that is not listed here is not compiled.  (File-scope objects, filled once when the library is loaded: a launch
+// indexes them without a guard.)
+struct Kern { const void* fn; size_t max_lds; };
+struct KernTable { const Kern* k; int n; std::atomic<bool> configured{false}; };
+template <class P> static Kern kern(void (*fn)(P), size_t max_lds) { return {reinterpret_cast<const void*>(fn), max_lds}; }
+constexpr size_t IG128 = 2 * (BM * BK * 2 + 128 * BK * 2), IG160 = 2 * (BM * BK * 2 + 160 * BK * 2), W8 = gemm_big_lds(320) + LN_LDS_W8, GLW = GEMM_LW_LDS + LN_LDS_LW;
+static const Kern k_ig[IK_FORMS + IK_FORMS_160] = {       // igemm_kernel_slot: IgemmKernelForm at 128 columns, then at 160 (no GEGLU forms)
+    kern(igemm_kernel<128, false, false>, IG128), kern(igemm_kernel<128, false, false, 1>, IG128), kern(igemm_kernel<128, false, false, 2>, IG128),
+    kern(igemm_kernel<128, false, false, 0, 1>, IG128), kern(igemm_kernel<128, false, false, 2, 1>, IG128), kern(igemm_kernel<128, true, false>, IG128),
+    kern(igemm_kernel<128, false, true>, IG128), kern(igemm_kernel<128, false, true, 1>, IG128),
+    kern(igemm_kernel<160, false, false>, IG160), kern(igemm_kernel<160, false, false, 1>, IG160), kern(igemm_kernel<160, false, false, 2>, IG160),
+    kern(igemm_kernel<160, false, false, 0, 1>, IG160), kern(igemm_kernel<160, false, false, 2, 1>, IG160), kern(igemm_kernel<160, true, false>, IG160)};
+// halo_slot.  The k32-step kernels (KH = 2: BN 320 / 256) run schedule 2, the k64-step kernels (BN 160 / 128) the lock-step schedule 0 (igemm_plan.h, halo_or_lw);
+// the other combinations were measured in round 2 and are not compiled any more
+static const Kern k_halo[8] = {kern(conv3_halo_kernel<false, 320, 2, 2>, CONV_LDS_MAX), kern(conv3_halo_kernel<true, 320, 2, 2>, CONV_LDS_MAX),
+                             kern(conv3_halo_kernel<false, 256, 2, 2>, CONV_LDS_MAX), kern(conv3_halo_kernel<true, 256, 2, 2>, CONV_LDS_MAX),
+                             kern(conv3_halo_kernel<false, 160, 1, 0>, CONV_LDS_MAX), kern(conv3_halo_kernel<true, 160, 1, 0>, CONV_LDS_MAX),
+                             kern(conv3_halo_kernel<false, 128, 1, 0>, CONV_LDS_MAX), kern(conv3_halo_kernel<true, 128, 1, 0>, CONV_LDS_MAX)};
+static const Kern k_lw[LW_VARIANTS] = {            // ConvLwVariant
+    kern(conv3_lw_kernel<false, 160, false, true>, CONV_LDS_MAX), kern(conv3_lw_kernel<false, 160>, CONV_LDS_MAX), kern(conv3_lw_kernel<true, 160>, CONV_LDS_MAX),
+    kern(conv3_lw_kernel<false, 160, true, true>, CONV_LDS_MAX), kern(conv3_lw_kernel<false, 160, true, false>, CONV_LDS_MAX), kern(conv3_lw_kernel<true, 160, false, true>, CONV_LDS_MAX),
+    kern(conv3_lw_kernel<false, 128, false, true>, CONV_LDS_MAX), kern(conv3_lw_kernel<false, 128>, CONV_LDS_MAX), kern(conv3_lw_kernel<true, 128>, CONV_LDS_MAX),
+    kern(conv3_lw_kernel<true, 128, false, true>, CONV_LDS_MAX), kern(conv3_lw_kernel<false, 160, false, 2>, CONV_LDS_MAX)};
+static const Kern k_sub[SUB_VARIANTS] = {kern(conv3_lw_kernel<false, 160, false, 1, true>, CONV_LDS_MAX), kern(conv3_lw_kernel<false, 160, false, 2, true>, CONV_LDS_MAX),
+                                       kern(conv3_lw_kernel<false, 128, false, 1, true>, CONV_LDS_MAX)};
+static const Kern k_big[3] = {kern(gemm_big_kernel<false, 320>, gemm_big_lds(320)), kern(gemm_big_kernel<true, 320>, gemm_big_lds(320)), kern(gemm_big_kernel<false, 160>, gemm_big_lds(160))};      // gemm_big_slot
+static const Kern k_w8[W8_VARIANTS] = {kern(gemm_w8_kernel<false, 0>, W8), kern(gemm_w8_kernel<true, 0>, W8), kern(gemm_w8_kernel<false, 1>, W8), kern(gemm_w8_kernel<true, 1>, W8),
+                                     kern(gemm_w8_kernel<false, 2>, W8), kern(gemm_w8_kernel<false, 0, 1>, W8), kern(gemm_w8_kernel<false, 2, 1>, W8), kern(gemm_w8_kernel<false, 0, 2>, W8)};
+static const Kern k_glw[GLW_VARIANTS] = {kern(gemm_lw_kernel<0>, GLW), kern(gemm_lw_kernel<1>, GLW), kern(gemm_lw_kernel<2>, GLW), kern(gemm_lw_kernel<0, 1>, GLW), kern(gemm_lw_kernel<2, 1>, GLW),
+                                       kern(gemm_lw_kernel<0, 2>, GLW)};
+static const Kern k_as[AS_VARIANTS] = {kern(gemm_as_kernel<false, 0>, gemm_as_lds(AS_MAX_N)), kern(gemm_as_kernel<true, 0>, gemm_as_lds(AS_MAX_N)), kern(gemm_as_kernel<false, 1>, gemm_as_lds(AS_MAX_N)),
+                                     kern(gemm_as_kernel<true, 1>, gemm_as_lds(AS_MAX_N))};
+static KernTable g_tables[FAM_AS + 1] = {{nullptr, 0}, {k_ig, IK_FORMS + IK_FORMS_160}, {k_halo, 8}, {k_lw, LW_VARIANTS}, {k_sub, SUB_VARIANTS}, {k_big, 3}, {k_w8, W8_VARIANTS}, {k_glw, GLW_VARIANTS}, {k_as, AS_VARIANTS}};
+
+// the plan's kernel with its grid, block and LDS.  The first launch of a family raises the dynamic-LDS limit of the family's kernels; the flag is set only behind
+// the last successful hipFuncSetAttribute, so a failure is reported (CS_E_HIP) and tried again by the next launch, and two threads that meet here both set the
+// same values.
+template <class P>
+static int launch_planned(const IgemmPlan& pl, const P& params, hipStream_t s) {
+    KernTable& tb = g_tables[pl.route.family];
+    if (!tb.configured.load(std::memory_order_acquire)) {
+        for (int i = 0; i < tb.n; ++i) CS_CHECK_HIP(hipFuncSetAttribute(tb.k[i].fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)tb.k[i].max_lds));
+        tb.configured.store(true, std::memory_order_release);
     }
-    if (a.row_stats && (a.geglu || a.gn_stats)) CS_FAIL(CS_E_ARG, "igemm: row_stats excludes GEGLU and gn_stats");
-    if (a.row_stats && !a.row_stats_groups) CS_FAIL(CS_E_ARG, "igemm: row_stats needs row_stats_groups (the layout the chosen kernel wrote is returned there)");
-    p.a0_lo = a.a0_lo; p.a1_lo = a.c1 ? a.a1_lo : nullptr; p.KTh = p.KT;
-    const int lnm = a.ln_stats ? 1 : (a.row_stats && !conv3_early ? 2 : 0);      // epilogue instantiation: folded-LayerNorm consumer / row-statistics producer / neither
-    const bool split_a = a.a0_lo != nullptr;
-    if (split_a) {
-        if (a.taps != 1 || a.geglu) CS_FAIL(CS_E_ARG, "igemm: a split-fp16 A operand (a0_lo) is built for 1x1 / linear layers without GEGLU");
-        if (a.c1 && !a.a1_lo) CS_FAIL(CS_E_ARG, "igemm: a0_lo without a1_lo");
-        p.KT = 2 * p.KTh;                                  // Ktot (row length of w) stays cin: the lo k steps re-read the same weight columns
-    }
-    if (a.geglu && a.out_lo) CS_FAIL(CS_E_ARG, "igemm: the GEGLU epilogue writes no lo plane");
-    if (p.lo8 && (a.taps != 1 || a.temb || a.geglu || a.ln_stats)) CS_FAIL(CS_E_ARG, "igemm: 8-bit lo planes (lo8) are built for plain 1x1 / linear layers (the transformer hidden state)");
-    p.epi_fast = tune().epi_fast;
-    // the epilogue family (igemm_epilogue_f32, EPI): 1 = byte lo planes, or a residual with an fp16 lo plane and no lo plane out (FAST 4) -- separate kernel instantiations
-    const int epi = (a.taps == 1 && !a.geglu && !a.ln_stats && !a.temb) ? (p.lo8 ? 1 : (p.res && p.res_lo && !p.out_lo && (p.epi_fast & 2)) ? 2 : 0) : 0;
-    p.debug = tune().debug; p.partial = nullptr;
-    // GroupNorm statistics of the output: by the epilogue where the chosen kernel runs one (not the split-K forms), else by the caller below
-    const bool stats_ok = a.gn_stats && !a.geglu && p.HoWo % 64 == 0 && tune().gn_fuse != 0;
-    p.gn_stats = stats_ok ? a.gn_stats : nullptr;
-    p.gm = 1; p.pn = 0;
-    const double a_bytes = 2.0 * a.B * a.Hi * a.Wi * cin, w_bytes = 2.0 * a.N * a.taps * cin;
-    if (as_route) {
-        typedef void (*as_fn)(IgemmParams);
-        static const as_fn asv[4] = {gemm_as_kernel<false, 0>, gemm_as_kernel<true, 0>, gemm_as_kernel<false, 1>, gemm_as_kernel<true, 1>};
-        static bool configured_as = false;
-        if (!configured_as) {
-            for (as_fn f : asv) CS_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(f), hipFuncAttributeMaxDynamicSharedMemorySize, (int)gemm_as_lds(AS_MAX_N)));
-            configured_as = true;
-        }
-        const int av = 2 * lnm + (a.geglu ? 1 : 0);
-        route_set(8, 32, av);
-        hipLaunchKernelGGL(asv[av], dim3((p.M + 511) / 512), dim3(512), gemm_as_lds(a.N), s, p);
-        CS_CHECK_LAUNCH();
-        return CS_OK;
-    }
-    const int tiles_m = (p.M + BM - 1) / BM;
-    int bn;
-    if (a.N % 128 == 0) bn = 128;
-    else if (a.N % 160 == 0) bn = 160;
-    else CS_FAIL(CS_E_SHAPE, "igemm: N=%d must be a multiple of 128 or 160", a.N);
-    p.tiles_n = a.N / bn; p.nblk = tiles_m * p.tiles_n;
-    const bool conv3 = a.taps == 9;
-    const int use_halo = tune().halo;   // 0 = never, 1 = when it pays, 2 = whenever the shape allows (tests)
-    const int Wo = a.upsample ? 2 * a.Wi : a.Wi, Ho = a.upsample ? 2 * a.Hi : a.Hi;
-    int hbn = a.N % 160 == 0 ? 160 : (a.N % 128 == 0 ? 128 : 0);
-    // 256 x 320 tiles (k32 inner step) when they still fill the chip: SD1.5's 320- and 640-wide layers at 64 x 64 / 32 x 32 (tune().halo 3 forces,
-    // 4 forbids: tests / A-B)
-    bool wide = false;
-    // patch geometry: TW = min(Wo, 16) in {8, 16}; TH = min(Ho, 256 / TW); both powers of two dividing the image
-    const int TW = Wo >= 16 ? 16 : Wo, THmax = TW ? 256 / TW : 0, TH = Ho < THmax ? Ho : THmax;
-    const bool pow2 = TW == 8 || TW == 16;
-    const bool geom_ok = pow2 && TH >= 2 && (TH & (TH - 1)) == 0 && Wo % TW == 0 && Ho % TH == 0 && Ho == a.Ho && Wo == a.Wo &&
-                         (!a.upsample || (TH % 2 == 0 && TW % 2 == 0 && TW / 2 + 2 >= 10));
-    // round 6: nearest-x2 upsample + 3x3 conv in the sub-pixel form (conv3_lw_kernel<.., SUB>): tiles over INPUT pixels, four phases, 4 of 9 taps each with the
-    // filter's taps pre-summed (a.w_up_sub from conv_up_fold_pack_host: one more fp16 rounding of the weights, which is why the caller decides -- knob up_fold)
-    if (igemm_sub_pixel(a, tune())) {
-        const int sbn = a.N % 160 == 0 ? 160 : 128;                      // (the VAE decoder's 256 / 512-wide upsamplers: 128-column tiles)
-        const bool f1 = a.Wi % 16 == 0 && a.Hi % 16 == 0;                 // (else 8 x 8)
-        const int TWi = f1 ? 16 : 8, TRW = f1 ? 256 : 64, IPT = 256 / TRW;
-        const int PX = a.Wi / TWi, PY = a.Hi / TWi, PP = PX * PY;
-        const int tiles_lo = PP == 1 ? (a.B + IPT - 1) / IPT : a.B * PP, tiles_m = 4 * tiles_lo, tiles_n = a.N / sbn;
-        HaloParams h;
-        h.HALO_W = TWi + 2; h.HALO_IMG = (TWi + 2) * (TWi + 2); h.NHALO = IPT * h.HALO_IMG; h.NQ = (h.NHALO + 7) / 8;
-        h.e = p; h.e.w = a.w_up_sub; h.e.tiles_n = tiles_n; h.e.nblk = tiles_m * tiles_n; h.e.row_stats = nullptr; h.e.pn = choose_xcd_grid(tiles_m, tiles_n, a_bytes, w_bytes * 16.0 / 9.0);
-        h.x = a.a0; h.w = a.w_up_sub; h.Cin = cin; h.H = a.Hi; h.W = a.Wi; h.B = a.B; h.NC = cin / BK; h.Ho = Ho; h.Wo = Wo;
-        h.tw_shift = f1 ? 4 : 3; h.trw_shift = f1 ? 8 : 6; h.PX = PX; h.PP = PP; h.splits = 1; h.partial = nullptr; h.sched = 0;
-        typedef void (*lw_fn)(HaloParams);
-        static const lw_fn sub[3] = {conv3_lw_kernel<false, 160, false, 1, true>, conv3_lw_kernel<false, 160, false, 2, true>, conv3_lw_kernel<false, 128, false, 1, true>};
-        static bool configured_sub = false;
-        if (!configured_sub) {
-            for (lw_fn f : sub)
-                CS_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(f), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(2 * (HALO_ROWS_MAX * 128) + 3 * (160 * 128))));
-            configured_sub = true;
-        }
-        const size_t llw = 2 * ((size_t)h.NQ * 1024) + 3 * ((size_t)sbn * 128);
-        const int sv = sbn == 128 ? 2 : f1 ? 0 : 1;
-        route_set(4, sbn, sv);
-        hipLaunchKernelGGL(sub[sv], dim3(h.e.nblk, 1), dim3(512), llw, s, h);
-        CS_CHECK_LAUNCH();
-        li->gn_done = stats_ok;
-        return CS_OK;
-    }
-    if (use_halo && conv3 && a.stride == 1 && a.c1 == 0 && hbn && !a.geglu && geom_ok) {
-        const int TRW = TH * TW, IPT = 256 / TRW;                       // output pixels per image in a tile; images per tile
-        const int PX = Wo / TW, PY = Ho / TH, PP = PX * PY;
-        const int tiles_m = PP == 1 ? (a.B + IPT - 1) / IPT : a.B * PP;
-        if (a.N % 320 == 0 && tune().halo != 4 && (tiles_m * (a.N / 320) >= 192 || tune().halo == 3)) { hbn = 320; wide = true; }
-        else if (a.N % 256 == 0 && tune().halo != 4 && (tiles_m * (a.N / 256) >= 192 || tune().halo == 3)) { hbn = 256; wide = true; }   // VAE: 256 / 512 channels
-        // round 3: loader-wave kernel (256 pixels x 160 channels per workgroup) wherever the channel count allows it
-        // (conv3_lw_kernel's padded halo rows read g_zero_region + chunk offset: the region covers LW_ZERO_CHUNKS 64-channel chunks, wider inputs take the halo kernels)
-        const bool lw_cin_ok = cin / BK <= LW_ZERO_CHUNKS;
-        const bool lw160 = tune().conv_lw != 0 && a.N % 160 == 0 && lw_cin_ok;
-        const bool lw128 = tune().conv_lw != 0 && tune().conv_lw != 3 && !lw160 && a.N % 128 == 0 && lw_cin_ok;        // the VAE's widths 128 / 256 / 512 (conv_lw = 3: BN 160 only)
-        const bool lw = lw160 || lw128;
-        if (lw) { hbn = lw160 ? 160 : 128; wide = false; }
-        const int tiles_n = a.N / hbn;
-        const int NC = cin / BK;
-        int splits = 1;
-        if (tiles_m * tiles_n < 160 && a.splitk_ws) {          // small images: split the channel chunks to fill the chip
-            while (splits < 8 && tiles_m * tiles_n * splits < 192 && NC % (splits * 2) == 0 &&
-                   (size_t)(splits * 2) * p.M * a.N * sizeof(float) <= a.splitk_ws_bytes) splits *= 2;
-        }
-        const bool pays = tiles_m * tiles_n * splits >= 160;
-        const int tin_w = a.upsample ? TW / 2 : TW, tin_h = a.upsample ? TH / 2 : TH;
-        HaloParams h;
-        h.HALO_W = tin_w + 2; h.HALO_IMG = (tin_h + 2) * (tin_w + 2); h.NHALO = IPT * h.HALO_IMG; h.NQ = (h.NHALO + 7) / 8;
-        if ((pays || use_halo == 2 || use_halo == 3) && h.NHALO <= HALO_ROWS_MAX && h.NQ <= 64 && (PP == 1 || IPT == 1)) {
-            h.e = p; h.e.tiles_n = tiles_n; h.e.nblk = tiles_m * tiles_n; h.e.row_stats = nullptr; h.e.pn = choose_xcd_grid(tiles_m, tiles_n, a_bytes, w_bytes);       // (row statistics of a conv output: the pass in launch_igemm)
-            h.x = a.a0; h.w = a.w; h.Cin = cin; h.H = a.Hi; h.W = a.Wi; h.B = a.B; h.NC = NC; h.Ho = Ho; h.Wo = Wo;
-            h.tw_shift = TW == 16 ? 4 : 3; h.trw_shift = 0; while ((1 << h.trw_shift) < TRW) ++h.trw_shift;
-            h.PX = PX; h.PP = PP;
-            // schedule: the k32-step kernels (BN 320 / 256) gain 6-11 % from priority + interleaved DMA (A/B on one box, tools/ab_convsched.sh);
-            // the k64-step kernels (BN 160 / 128: 16 x 16 and 8 x 8 images) measured 0.207 -> 0.213 ms with it and keep the lock-step schedule
-            h.splits = splits; h.partial = a.splitk_ws; h.sched = wide ? 2 : 0;
-            const size_t l = 2 * (HALO_ROWS_MAX * 128) + 3 * ((size_t)hbn * (wide ? 64 : 128));
-            const dim3 grid(h.e.nblk, splits);
-            int rc;
-            route_set(2, hbn, a.upsample ? 1 : 0, splits);         // (conv3_lw_kernel: overwritten below)
-            if (lw) {
-                constexpr size_t llw_max = 2 * (HALO_ROWS_MAX * 128) + 3 * (160 * 128);      // = 160 KiB exactly: the whole LDS of a CU
-                const size_t llw = 2 * ((size_t)h.NQ * 1024) + 3 * ((size_t)hbn * 128);
-                // FAST: plain conv on 16 x 16 patches (every UNet level down to 16 x 16, the VAE): immediate-offset LDS addressing
-                const bool fast = TW == 16 && TH == 16 && tune().conv_lw != 2 && (a.upsample ? (h.HALO_W == 10 && h.NQ == 13) : (h.HALO_W == 18 && h.NQ == 41));
-                const bool fast8 = hbn == 160 && TW == 8 && TH == 8 && !a.upsample && IPT == 4 && PP == 1 && h.HALO_W == 10 && h.NQ == 50 && tune().conv_lw != 2 &&
-                                   !((tune().debug & 16384) != 0);
-                typedef void (*lw_fn)(HaloParams);
-                static const lw_fn variants[11] = {conv3_lw_kernel<false, 160, false, true>, conv3_lw_kernel<false, 160>, conv3_lw_kernel<true, 160>,
-                                                   conv3_lw_kernel<false, 160, true, true>, conv3_lw_kernel<false, 160, true, false>, conv3_lw_kernel<true, 160, false, true>,
-                                                   conv3_lw_kernel<false, 128, false, true>, conv3_lw_kernel<false, 128>, conv3_lw_kernel<true, 128>, conv3_lw_kernel<true, 128, false, true>,
-                                                   conv3_lw_kernel<false, 160, false, 2>};
-                static bool configured_lw = false;
-                if (!configured_lw) {
-                    for (lw_fn f : variants)
-                        CS_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(f), hipFuncAttributeMaxDynamicSharedMemorySize, (int)llw_max));
-                    configured_lw = true;
-                }
-                auto launch = [&](lw_fn kfn) -> int { hipLaunchKernelGGL(kfn, grid, dim3(512), llw, s, h); return CS_OK; };
-                const bool trace = (tune().debug & 16384) && !a.upsample;    // timing experiments: the stamped instantiations (plain conv only)
-                const int lv = fast8 ? 10 : hbn == 128 ? (a.upsample ? (fast ? 9 : 8) : (fast ? 6 : 7)) : trace ? (fast ? 3 : 4) : a.upsample ? (fast ? 5 : 2) : (fast ? 0 : 1);
-                route_set(3, hbn, lv, splits);
-                rc = launch(variants[lv]);
-                if (rc != CS_OK) return rc;
-                rc = CS_OK;
-            } else if (wide && hbn == 320) rc = a.upsample ? launch_halo<true, 320, 2>(h, grid, l, s) : launch_halo<false, 320, 2>(h, grid, l, s);
-            else if (wide) rc = a.upsample ? launch_halo<true, 256, 2>(h, grid, l, s) : launch_halo<false, 256, 2>(h, grid, l, s);
-            else if (hbn == 160) rc = a.upsample ? launch_halo<true, 160, 1>(h, grid, l, s) : launch_halo<false, 160, 1>(h, grid, l, s);
-            else rc = a.upsample ? launch_halo<true, 128, 1>(h, grid, l, s) : launch_halo<false, 128, 1>(h, grid, l, s);
-            if (rc != CS_OK) return rc;
-            CS_CHECK_LAUNCH();
-            li->gn_done = stats_ok && (splits == 1 || reduce_leaves_stats(h.e));
-            if (splits > 1) return launch_splitk_reduce(h.e, (const float*)a.splitk_ws, splits, s);
-            return CS_OK;
-        }
-    }
-    if (a.geglu && conv3) CS_FAIL(CS_E_ARG, "igemm: GEGLU epilogue only for linear layers");
-    if (tune().biggemm && !conv3 && a.N % 320 == 0) {
-        const int tiles_m = (p.M + 255) / 256, tn = a.N / 320;
-        // (GEGLU with N % 128 != 0 -- 320, 960, ...: the generic tiles below cannot take it (igemm_kernel's GEGLU form is the 128-column one), so it runs here
-        //  whatever the tile count)
-        if (tiles_m * tn >= 192 || tune().biggemm == 2 || (a.geglu && a.N % 128)) {
-            p.tiles_n = tn; p.nblk = tiles_m * tn; p.pn = choose_xcd_grid(tiles_m, tn, a_bytes, w_bytes); li->gn_done = stats_ok; li->row_groups = a.N / 160;      // gemm_w8 / gemm_big<., 320>: 64 x 160 wave tiles
-            p.gm = tune().gemm_gm >= 0 ? (tune().gemm_gm > 1 ? tune().gemm_gm : 1) : (tn >= 12 ? 4 : 1);
-            constexpr size_t lds = 2 * (256 * BK * 2 + 320 * BK * 2);
-            static bool configured = false;
-            if (!configured) {
-                CS_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_big_kernel<false, 320>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-                CS_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_big_kernel<true, 320>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-                configured = true;
-            }
-            // round 3: the hand-scheduled k loop (gemm_w8_kernel) whenever 32-bit byte offsets reach every operand row
-            const bool off32 = (double)p.M * (a.c0 > a.c1 ? a.c0 : a.c1) * 2 < 4.0e9 && (double)a.N * p.Ktot * 2 < 4.0e9;
-            if ((split_a || lnm || epi == 1) && !(tune().gemm_w8 && off32 && !tune().debug)) goto generic_tiles;       // gemm_big_kernel has no lo-plane staging, no LayerNorm epilogues, no byte planes
-            if (tune().gemm_w8 && off32 && !tune().debug) {
-                typedef void (*w8_fn)(IgemmParams);
-                static const w8_fn w8[8] = {gemm_w8_kernel<false, 0>, gemm_w8_kernel<true, 0>, gemm_w8_kernel<false, 1>, gemm_w8_kernel<true, 1>, gemm_w8_kernel<false, 2>,
-                                            gemm_w8_kernel<false, 0, 1>, gemm_w8_kernel<false, 2, 1>, gemm_w8_kernel<false, 0, 2>};
-                static bool configured_w8 = false;
-                if (!configured_w8) {
-                    for (w8_fn f : w8) CS_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(f), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(lds + LN_LDS_W8)));
-                    configured_w8 = true;
-                }
-                const int wv = epi == 1 ? (lnm == 2 ? 6 : 5) : (epi == 2 && lnm == 0) ? 7 : lnm == 2 ? 4 : 2 * lnm + (a.geglu ? 1 : 0);
-                route_set(6, 320, wv);
-                hipLaunchKernelGGL(w8[wv], dim3(p.nblk), dim3(512), lds + LN_LDS_W8, s, p);
-                CS_CHECK_LAUNCH();
-                return CS_OK;
-            }
-            route_set(5, 320, a.geglu ? 1 : 0);
-            if (a.geglu) hipLaunchKernelGGL((gemm_big_kernel<true, 320>), dim3(p.nblk), dim3(512), lds, s, p);
-            else hipLaunchKernelGGL((gemm_big_kernel<false, 320>), dim3(p.nblk), dim3(512), lds, s, p);
-            CS_CHECK_LAUNCH();
-            return CS_OK;
-        }
-    }
-    if (tune().biggemm && !conv3 && !a.geglu && a.N % 160 == 0) {       // too few 256 x 320 tiles: 256 x 160 tiles, same 8-wave structure
-        const int tiles_m = (p.M + 255) / 256, tn = a.N / 160;
-        if (tiles_m * tn >= 192 || tune().biggemm == 3) {
-            p.tiles_n = tn; p.nblk = tiles_m * tn; p.pn = choose_xcd_grid(tiles_m, tn, a_bytes, w_bytes); li->gn_done = stats_ok;
-            li->row_groups = (tune().gemm_lw && !tune().debug) ? a.N / 160 : a.N / 80;       // gemm_lw: 64 x 160 wave tiles; gemm_big<., 160>: 64 x 80
-            p.gm = tune().gemm_gm >= 0 ? (tune().gemm_gm > 1 ? tune().gemm_gm : 1) : (tn >= 12 ? 4 : 1);
-            constexpr size_t lds = 2 * (256 * BK * 2 + 160 * BK * 2);
-            static bool configured = false;
-            if (!configured) {
-                CS_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_big_kernel<false, 160>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-                configured = true;
-            }
-            if ((split_a || lnm || epi == 1) && !(tune().gemm_lw && !tune().debug)) goto generic_tiles;
-            if (tune().gemm_lw && !tune().debug) {                    // round 3: the loader-wave form (three 52 KB stages)
-                constexpr size_t lds_lw = 3 * (256 * BK * 2 + 160 * BK * 2);
-                typedef void (*lw_fn)(IgemmParams);
-                static const lw_fn lwk[6] = {gemm_lw_kernel<0>, gemm_lw_kernel<1>, gemm_lw_kernel<2>, gemm_lw_kernel<0, 1>, gemm_lw_kernel<2, 1>, gemm_lw_kernel<0, 2>};
-                static bool configured_lw = false;
-                if (!configured_lw) {
-                    for (lw_fn f : lwk) CS_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(f), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(lds_lw + LN_LDS_LW)));
-                    configured_lw = true;
-                }
-                const int kv = epi == 1 ? (lnm == 2 ? 4 : 3) : (epi == 2 && lnm == 0) ? 5 : lnm;
-                route_set(7, 160, kv);
-                hipLaunchKernelGGL(lwk[kv], dim3(p.nblk), dim3(512), lds_lw + LN_LDS_LW, s, p);
-                CS_CHECK_LAUNCH();
-                return CS_OK;
-            }
-            route_set(5, 160, 0);
-            hipLaunchKernelGGL((gemm_big_kernel<false, 160>), dim3(p.nblk), dim3(512), lds, s, p);
-            CS_CHECK_LAUNCH();
-            return CS_OK;
-        }
-    }
-generic_tiles:
-    p.tiles_n = a.N / bn; p.nblk = tiles_m * p.tiles_n; p.gm = 1; p.pn = choose_xcd_grid(tiles_m, p.tiles_n, a_bytes, w_bytes); li->gn_done = false; li->row_groups = 0;
-    if (a.geglu) {
-        // the GEGLU form of igemm_kernel is the 128-column one: with N % 128 != 0 (tiles_n counts 160-column tiles) it would leave the columns behind
-        // 128 tiles_n unwritten
-        if (a.N % 128) CS_FAIL(CS_E_SHAPE, "igemm: GEGLU with N %% 128 != 0 (N=%d) needs the 256 x 320 tiles (knob gemm_big != 0)", a.N);
-        route_set(1, 128, (lnm == 1 ? 1 : 0) | 16);
-        return lnm == 1 ? launch_variant<128, false, true, 1>(p, s) : launch_variant<128, false, true>(p, s);
-    }
-    // few tiles and a long k loop (stride-2 convs into the 16 x 16 / 8 x 8 levels, the 8 x 8 linears): split K to fill the chip
-    int splits = 1;
-    if (a.splitk_ws && !a.geglu && p.nblk < 192) {
-        while (splits < 8 && p.nblk * splits < 256 && p.KT % (splits * 2) == 0 && p.KT / (splits * 2) >= 8 &&
-               (size_t)(splits * 2) * p.M * a.N * sizeof(float) <= a.splitk_ws_bytes) splits *= 2;
-        if (splits > 1) p.partial = a.splitk_ws;
-    }
-    li->gn_done = stats_ok && (splits == 1 || reduce_leaves_stats(p));
-    li->row_groups = (splits == 1 && !conv3) ? a.N / (bn / 2) : 0;          // igemm_kernel: 64 x bn / 2 wave tiles; the split-K reduce leaves no row statistics
-    const int lk = splits > 1 ? 0 : lnm;            // (split-K: raw partial sums leave the main kernel; the reduce kernel applies a folded LayerNorm itself)
-    route_set(1, bn, conv3 ? 32 : (lk | ((epi == 1 && splits == 1) ? 1 << 2 : 0)), splits);
-    if (conv3) return bn == 128 ? launch_variant<128, true, false>(p, s, splits) : launch_variant<160, true, false>(p, s, splits);
-    if (epi == 1 && splits == 1) {                  // byte planes (split-K: the reduce kernel handles the planes, the main kernel writes raw partial sums)
-        if (bn == 128) return lk == 2 ? launch_variant<128, false, false, 2, 1>(p, s, splits) : launch_variant<128, false, false, 0, 1>(p, s, splits);
-        return lk == 2 ? launch_variant<160, false, false, 2, 1>(p, s, splits) : launch_variant<160, false, false, 0, 1>(p, s, splits);
-    }
-    if (bn == 128) return lk == 1 ? launch_variant<128, false, false, 1>(p, s, splits) : lk == 2 ? launch_variant<128, false, false, 2>(p, s, splits) : launch_variant<128, false, false>(p, s, splits);
-    return lk == 1 ? launch_variant<160, false, false, 1>(p, s, splits) : lk == 2 ? launch_variant<160, false, false, 2>(p, s, splits) : launch_variant<160, false, false>(p, s, splits);
+    void* args[1] = {const_cast<P*>(&params)};
+    (void)hipLaunchKernel(tb.k[pl.slot].fn, dim3(pl.grid_x, pl.grid_y), dim3(pl.block), args, pl.lds, s);
+    CS_CHECK_LAUNCH();                              // (as behind every hipLaunchKernelGGL here: reads and clears the thread's last error)
+    return CS_OK;
 }
 
 int launch_igemm(const IgemmArgs& a, hipStream_t s) {
-    LaunchInfo li;
+    const TuneSet& t = tune();
+    IgemmPlan pl;
     t_igemm_route = IgemmRoute();
-    const int rc = launch_igemm_impl(a, s, &li);
-    t_igemm_route.gn_done = li.gn_done ? 1 : 0; t_igemm_route.row_groups = a.row_stats ? li.row_groups : 0;
+    int rc = igemm_plan(a, t, &pl);
+    if (rc != CS_OK) return rc;
+    if (pl.route.family == FAM_NONE) {              // an empty shape: nothing to launch and no statistics to leave; the row-statistics layout is the pass's one group
+        if (a.row_stats && a.row_stats_groups) *a.row_stats_groups = 1;
+        return CS_OK;
+    }
+    t_igemm_route = pl.route;
+    HaloParams h;                                   // (the GEMM families: its epilogue view h.e alone)
+    const bool halo = pl.route.family == FAM_HALO || pl.route.family == FAM_CONV_LW || pl.route.family == FAM_SUB;
+    fill_params(a, t, pl, h.e);
+    if (halo) fill_halo(a, pl, h);
+    rc = halo ? launch_planned(pl, h, s) : launch_planned(pl, h.e, s);
+    if (rc == CS_OK && pl.uses_splitk_ws) rc = launch_splitk_reduce(h.e, a.splitk_ws, pl.route.splits, s);
     if (rc != CS_OK) return rc;
     if (a.row_stats) {                              // row statistics for a LayerNorm folded into the consumer: by the epilogue, else a pass over the output
-        if (li.row_groups > 0) *a.row_stats_groups = li.row_groups;
+        if (pl.route.row_groups > 0) *a.row_stats_groups = pl.route.row_groups;
         else {
-            const int M = a.B * a.Ho * a.Wo;
-            hipLaunchKernelGGL(row_stats_kernel, dim3((M + 3) / 4), dim3(256), 0, s, (const f16*)a.out, (const f16*)a.out_lo, M, a.N, a.row_stats, a.lo8);
+            hipLaunchKernelGGL(row_stats_kernel, dim3((pl.M + 3) / 4), dim3(256), 0, s, (const f16*)a.out, (const f16*)a.out_lo, pl.M, a.N, a.row_stats, a.lo8);
             CS_CHECK_LAUNCH();
             *a.row_stats_groups = 1; t_igemm_route.fallback |= 2;
         }
     }
-    if (!a.gn_stats || li.gn_done) return rc;
+    if (!a.gn_stats || pl.route.gn_done) return rc;
     // the chosen kernel has no statistics epilogue (split-K forms) or the knob is off: a statistics pass over the output, same layout
     if (a.geglu || (a.Ho * a.Wo) % 64) CS_FAIL(CS_E_ARG, "igemm: gn_stats needs Ho * Wo %% 64 == 0 and no GEGLU");
     t_igemm_route.fallback |= 1;

@@ -99,7 +99,8 @@ struct IgemmArgs {
     // LN(h) W^T + b = rstd (h W'^T - mean s) + b'  with  W' = W diag(gamma) (packed once, fp16),  s[n] = sum_k W'[n][k],  b' = W beta + b  (fp32).  The GEMM reads the
     // RAW hidden state; the per-row (mean, rstd) come from partial sums its PRODUCER left:
     //   producer: row_stats != null -> row_stats[M][G][2] = (sum, sum of squares) of every output row over G column groups, G returned in *row_stats_groups
-    //             (written by the epilogue from the fp32 values, or by a pass over the output where the chosen kernel cannot: split-K forms; then G = 1);
+    //             (written by the epilogue from the fp32 values, or by a pass over the output where the chosen kernel cannot: split-K forms; then G = 1;
+    //             an empty shape -- B, Ho or Wo = 0 -- launches nothing and returns G = 1);
     //   consumer: ln_stats (that buffer), ln_groups = G, ln_eps, ln_s, ln_b (fp32 [N]); w = W'; bias is ignored (b' holds it).  The row length is c0.
     float* row_stats; int* row_stats_groups;
     const float* ln_stats; int ln_groups; float ln_eps; const float* ln_s; const float* ln_b;
@@ -109,7 +110,7 @@ struct IgemmArgs {
     const f16* w_up_sub;
 };
 // padding rows of conv3_lw_kernel: the chunk offset c * 128 B (c < LW_ZERO_CHUNKS) is added to every source, the zero source included, so the region spans
-// LW_ZERO_CHUNKS chunks + one 128-byte row + slack.  launch_igemm_impl sends Cin > 64 * LW_ZERO_CHUNKS (SD1.5 / VAE: <= 2560) to the halo kernels.
+// LW_ZERO_CHUNKS chunks + one 128-byte row + slack.  igemm_plan (igemm_plan.h, halo_or_lw) sends Cin > 64 * LW_ZERO_CHUNKS (SD1.5 / VAE: <= 2560) to the halo kernels.
 constexpr int LW_ZERO_CHUNKS = 64;
 // launch_igemm runs `a` in the sub-pixel form (conv3_lw_kernel<.., SUB> on a.w_up_sub): the caller gave the filter and the shape fits -- input a multiple of
 // 16 x 16 with N % 160 == 0 or N % 128 == 0, or 8 x 8 with N % 160 == 0; one source of at most LW_ZERO_CHUNKS 64-channel chunks; no residual / temb / GEGLU --
@@ -122,8 +123,10 @@ inline bool igemm_sub_pixel(const IgemmArgs& a, const TuneSet& t) {
 }
 // Which kernel the calling thread's last launch_igemm took (cs_debug_igemm_last_route; tests assert the dispatch with it).  Host only: one store per launch.
 // family: 0 nothing launched, 1 igemm_kernel, 2 conv3_halo_kernel, 3 conv3_lw_kernel, 4 conv3_lw_kernel in the sub-pixel form, 5 gemm_big_kernel, 6 gemm_w8_kernel,
-// 7 gemm_lw_kernel, 8 gemm_as_kernel (variant 2 LNM + GEGLU, tile_cols 32).  variant: the index into the site's function-pointer table (variants / sub / w8 / lwk); igemm_kernel: LNM | EPI << 2 | GEGLU << 4 | CONV3 << 5;
-// conv3_halo_kernel: 1 with the fused upsample; gemm_big_kernel: 1 with GEGLU.  fallback: bit 0 launch_gn_stats64 ran behind the launch, bit 1 row_stats_kernel.
+// 7 gemm_lw_kernel, 8 gemm_as_kernel (tile_cols 32): IgemmFamily of igemm_plan.h.  variant: which instantiation, numbered by that header's enums and index functions --
+// conv_lw_variant (ConvLwVariant), sub_variant (SubVariant), w8_variant (W8Variant), gemm_lw_variant (GemmLwVariant), as_variant (AsVariant); igemm_kernel: IK_VARIANT of
+// igemm_kernel_form = LNM | EPI << 2 | GEGLU << 4 | CONV3 << 5; conv3_halo_kernel: 1 with the fused upsample; gemm_big_kernel: 1 with GEGLU.
+// fallback: bit 0 launch_gn_stats64 ran behind the launch, bit 1 row_stats_kernel.  Everything but `fallback` is decided by igemm_plan before anything is launched.
 struct IgemmRoute { int family = 0, tile_cols = 0, variant = 0, splits = 1, gn_done = 0, row_groups = 0, fallback = 0; };
 extern thread_local IgemmRoute t_igemm_route;      // (defined in ops_api.cpp, next to the knob sets)
 int launch_igemm(const IgemmArgs& a, hipStream_t s);

@@ -72,35 +72,37 @@ int cs_reset_tuning(void) {
     return CS_OK;
 }
 
-int cs_op_conv2d(const void* x0, int c0, const void* x1, int c1, int B, int Hi, int Wi, int taps, int stride, int upsample,
-                 const void* w, const void* bias, int N, const void* temb, int temb_stride, const void* res, void* out,
-                 void* splitk_ws, size_t splitk_ws_bytes, void* stream) {
-    IgemmArgs a{};
+// the arguments cs_op_conv2d, _gn and _x2 share (res_lo: _x2 only)
+static int conv2d_args(IgemmArgs& a, const void* x0, int c0, const void* x1, int c1, int B, int Hi, int Wi, int taps, int stride, int upsample, const void* w,
+                       const void* bias, int N, const void* temb, int temb_stride, const void* res, const void* res_lo, void* out, void* splitk_ws, size_t splitk_ws_bytes) {
     a.a0 = (const f16*)x0; a.a1 = (const f16*)x1; a.c0 = c0; a.c1 = c1; a.B = B; a.Hi = Hi; a.Wi = Wi;
     if (stride != 1 && stride != 2) CS_FAIL(CS_E_ARG, "conv2d: stride must be 1 or 2");
+    if (res_lo && !res) CS_FAIL(CS_E_ARG, "conv2d_x2: res_lo without res");
     // pad 1, stride 2 gives ceil(Hi / 2) rows: the floor below is that only for even sizes (the pad-after-only form, cs_op_conv_down, floors by definition)
     if (stride == 2 && !upsample && ((Hi | Wi) & 1)) CS_FAIL(CS_E_SHAPE, "conv2d: stride 2 needs an even input size (got %d x %d)", Hi, Wi);
     a.Ho = upsample ? 2 * Hi : (stride == 2 ? Hi / 2 : Hi);
     a.Wo = upsample ? 2 * Wi : (stride == 2 ? Wi / 2 : Wi);
     a.taps = taps; a.stride = stride; a.upsample = upsample; a.N = N; a.w = (const f16*)w; a.bias = (const f16*)bias;
-    a.temb = (const f16*)temb; a.temb_stride = temb_stride; a.res = (const f16*)res; a.out = (f16*)out;
+    a.temb = (const f16*)temb; a.temb_stride = temb_stride; a.res = (const f16*)res; a.res_lo = (const f16*)res_lo; a.out = (f16*)out;
     a.splitk_ws = (float*)splitk_ws; a.splitk_ws_bytes = splitk_ws_bytes;
-    return launch_igemm(a, (hipStream_t)stream);
+    return CS_OK;
+}
+
+int cs_op_conv2d(const void* x0, int c0, const void* x1, int c1, int B, int Hi, int Wi, int taps, int stride, int upsample,
+                 const void* w, const void* bias, int N, const void* temb, int temb_stride, const void* res, void* out,
+                 void* splitk_ws, size_t splitk_ws_bytes, void* stream) {
+    IgemmArgs a{};
+    const int rc = conv2d_args(a, x0, c0, x1, c1, B, Hi, Wi, taps, stride, upsample, w, bias, N, temb, temb_stride, res, nullptr, out, splitk_ws, splitk_ws_bytes);
+    return rc != CS_OK ? rc : launch_igemm(a, (hipStream_t)stream);
 }
 
 int cs_op_conv2d_gn(const void* x0, int c0, const void* x1, int c1, int B, int Hi, int Wi, int taps, int stride, int upsample,
                     const void* w, const void* bias, int N, const void* temb, int temb_stride, const void* res, void* out,
                     void* splitk_ws, size_t splitk_ws_bytes, float* gn_stats, void* stream) {
     IgemmArgs a{};
-    a.a0 = (const f16*)x0; a.a1 = (const f16*)x1; a.c0 = c0; a.c1 = c1; a.B = B; a.Hi = Hi; a.Wi = Wi;
-    if (stride != 1 && stride != 2) CS_FAIL(CS_E_ARG, "conv2d: stride must be 1 or 2");
-    // pad 1, stride 2 gives ceil(Hi / 2) rows: the floor below is that only for even sizes (the pad-after-only form, cs_op_conv_down, floors by definition)
-    if (stride == 2 && !upsample && ((Hi | Wi) & 1)) CS_FAIL(CS_E_SHAPE, "conv2d: stride 2 needs an even input size (got %d x %d)", Hi, Wi);
-    a.Ho = upsample ? 2 * Hi : (stride == 2 ? Hi / 2 : Hi);
-    a.Wo = upsample ? 2 * Wi : (stride == 2 ? Wi / 2 : Wi);
-    a.taps = taps; a.stride = stride; a.upsample = upsample; a.N = N; a.w = (const f16*)w; a.bias = (const f16*)bias;
-    a.temb = (const f16*)temb; a.temb_stride = temb_stride; a.res = (const f16*)res; a.out = (f16*)out;
-    a.splitk_ws = (float*)splitk_ws; a.splitk_ws_bytes = splitk_ws_bytes; a.gn_stats = gn_stats;
+    const int rc = conv2d_args(a, x0, c0, x1, c1, B, Hi, Wi, taps, stride, upsample, w, bias, N, temb, temb_stride, res, nullptr, out, splitk_ws, splitk_ws_bytes);
+    if (rc != CS_OK) return rc;
+    a.gn_stats = gn_stats;
     if (gn_stats && (a.Ho * a.Wo) % 64) CS_FAIL(CS_E_SHAPE, "conv2d_gn: Ho * Wo = %d must be a multiple of 64", a.Ho * a.Wo);
     return launch_igemm(a, (hipStream_t)stream);
 }
@@ -123,10 +125,16 @@ int cs_op_conv_up_sub(const void* x, int Cin, int B, int Hi, int Wi, const void*
     return launch_igemm(a, (hipStream_t)stream);
 }
 
+// a linear layer as a 1x1 conv over M x 1 pixels: the arguments every cs_op_linear* shares
+static void linear_args(IgemmArgs& a, const void* x, int M, int K, const void* w, const void* bias, int N, const void* res, void* out) {
+    a.a0 = (const f16*)x; a.c0 = K; a.B = 1; a.Hi = M; a.Wi = 1; a.Ho = M; a.Wo = 1; a.taps = 1; a.stride = 1; a.N = N;
+    a.w = (const f16*)w; a.bias = (const f16*)bias; a.res = (const f16*)res; a.out = (f16*)out;
+}
+
 int cs_op_linear(const void* x, int M, int K, const void* w, const void* bias, int N, const void* res, void* out, int geglu, void* stream) {
     IgemmArgs a{};
-    a.a0 = (const f16*)x; a.c0 = K; a.B = 1; a.Hi = M; a.Wi = 1; a.Ho = M; a.Wo = 1; a.taps = 1; a.stride = 1; a.N = N;
-    a.w = (const f16*)w; a.bias = (const f16*)bias; a.res = (const f16*)res; a.out = (f16*)out; a.geglu = geglu;
+    linear_args(a, x, M, K, w, bias, N, res, out);
+    a.geglu = geglu;
     if (M <= 0) return M < 0 ? CS_E_SHAPE : CS_OK;
     return launch_igemm(a, (hipStream_t)stream);
 }
@@ -144,45 +152,30 @@ int cs_op_conv2d_x2(const void* x0, const void* x0_lo, int c0, const void* x1, c
                     int upsample, const void* w, const void* bias, int N, const void* temb, int temb_stride, const void* res, const void* res_lo,
                     void* out, void* out_lo, float* row_stats, int* row_groups, void* splitk_ws, size_t splitk_ws_bytes, void* stream) {
     IgemmArgs a{};
-    a.a0 = (const f16*)x0; a.a1 = (const f16*)x1; a.c0 = c0; a.c1 = c1; a.B = B; a.Hi = Hi; a.Wi = Wi;
-    a.a0_lo = (const f16*)x0_lo; a.a1_lo = (const f16*)x1_lo; a.row_stats = row_stats; a.row_stats_groups = row_groups;
-    if (stride != 1 && stride != 2) CS_FAIL(CS_E_ARG, "conv2d: stride must be 1 or 2");
-    if (res_lo && !res) CS_FAIL(CS_E_ARG, "conv2d_x2: res_lo without res");
-    // pad 1, stride 2 gives ceil(Hi / 2) rows: the floor below is that only for even sizes (the pad-after-only form, cs_op_conv_down, floors by definition)
-    if (stride == 2 && !upsample && ((Hi | Wi) & 1)) CS_FAIL(CS_E_SHAPE, "conv2d: stride 2 needs an even input size (got %d x %d)", Hi, Wi);
-    a.Ho = upsample ? 2 * Hi : (stride == 2 ? Hi / 2 : Hi);
-    a.Wo = upsample ? 2 * Wi : (stride == 2 ? Wi / 2 : Wi);
-    a.taps = taps; a.stride = stride; a.upsample = upsample; a.N = N; a.w = (const f16*)w; a.bias = (const f16*)bias;
-    a.temb = (const f16*)temb; a.temb_stride = temb_stride; a.res = (const f16*)res; a.out = (f16*)out;
-    a.res_lo = (const f16*)res_lo; a.out_lo = (f16*)out_lo;
-    a.splitk_ws = (float*)splitk_ws; a.splitk_ws_bytes = splitk_ws_bytes;
+    const int rc = conv2d_args(a, x0, c0, x1, c1, B, Hi, Wi, taps, stride, upsample, w, bias, N, temb, temb_stride, res, res_lo, out, splitk_ws, splitk_ws_bytes);
+    if (rc != CS_OK) return rc;
+    a.a0_lo = (const f16*)x0_lo; a.a1_lo = (const f16*)x1_lo; a.out_lo = (f16*)out_lo; a.row_stats = row_stats; a.row_stats_groups = row_groups;
     return launch_igemm(a, (hipStream_t)stream);
 }
 
+// cs_op_linear_x2 (fp16 lo planes, optionally a split A operand) and cs_op_linear_lo8 (byte lo planes); what: the entry's name for its lo plane
+static int linear_split(const char* what, const void* x, const void* x_lo, int M, int K, const void* w, const void* bias, int N, const void* res, const void* res_lo, void* out,
+                        void* out_lo, int lo8, float* row_stats, int* row_groups, void* splitk_ws, size_t splitk_ws_bytes, void* stream) {
+    IgemmArgs a{};
+    if (res_lo && !res) CS_FAIL(CS_E_ARG, "%s without res", what);
+    linear_args(a, x, M, K, w, bias, N, res, out);
+    a.a0_lo = (const f16*)x_lo; a.res_lo = (const f16*)res_lo; a.out_lo = (f16*)out_lo; a.lo8 = lo8; a.row_stats = row_stats; a.row_stats_groups = row_groups;
+    a.splitk_ws = (float*)splitk_ws; a.splitk_ws_bytes = splitk_ws_bytes;
+    if (M <= 0) return M < 0 ? CS_E_SHAPE : CS_OK;
+    return launch_igemm(a, (hipStream_t)stream);
+}
 int cs_op_linear_x2(const void* x, const void* x_lo, int M, int K, const void* w, const void* bias, int N, const void* res, const void* res_lo,
                     void* out, void* out_lo, float* row_stats, int* row_groups, void* splitk_ws, size_t splitk_ws_bytes, void* stream) {
-    IgemmArgs a{};
-    a.a0_lo = (const f16*)x_lo; a.row_stats = row_stats; a.row_stats_groups = row_groups;
-    if (res_lo && !res) CS_FAIL(CS_E_ARG, "linear_x2: res_lo without res");
-    a.a0 = (const f16*)x; a.c0 = K; a.B = 1; a.Hi = M; a.Wi = 1; a.Ho = M; a.Wo = 1; a.taps = 1; a.stride = 1; a.N = N;
-    a.w = (const f16*)w; a.bias = (const f16*)bias; a.res = (const f16*)res; a.out = (f16*)out;
-    a.res_lo = (const f16*)res_lo; a.out_lo = (f16*)out_lo;
-    a.splitk_ws = (float*)splitk_ws; a.splitk_ws_bytes = splitk_ws_bytes;
-    if (M <= 0) return M < 0 ? CS_E_SHAPE : CS_OK;
-    return launch_igemm(a, (hipStream_t)stream);
+    return linear_split("linear_x2: res_lo", x, x_lo, M, K, w, bias, N, res, res_lo, out, out_lo, 0, row_stats, row_groups, splitk_ws, splitk_ws_bytes, stream);
 }
-
 int cs_op_linear_lo8(const void* x, int M, int K, const void* w, const void* bias, int N, const void* res, const void* res_lo8, void* out, void* out_lo8,
                      float* row_stats, int* row_groups, void* splitk_ws, size_t splitk_ws_bytes, void* stream) {
-    IgemmArgs a{};
-    a.row_stats = row_stats; a.row_stats_groups = row_groups;
-    if (res_lo8 && !res) CS_FAIL(CS_E_ARG, "linear_lo8: res_lo8 without res");
-    a.a0 = (const f16*)x; a.c0 = K; a.B = 1; a.Hi = M; a.Wi = 1; a.Ho = M; a.Wo = 1; a.taps = 1; a.stride = 1; a.N = N;
-    a.w = (const f16*)w; a.bias = (const f16*)bias; a.res = (const f16*)res; a.out = (f16*)out;
-    a.res_lo = (const f16*)res_lo8; a.out_lo = (f16*)out_lo8; a.lo8 = 1;
-    a.splitk_ws = (float*)splitk_ws; a.splitk_ws_bytes = splitk_ws_bytes;
-    if (M <= 0) return M < 0 ? CS_E_SHAPE : CS_OK;
-    return launch_igemm(a, (hipStream_t)stream);
+    return linear_split("linear_lo8: res_lo8", x, nullptr, M, K, w, bias, N, res, res_lo8, out, out_lo8, 1, row_stats, row_groups, splitk_ws, splitk_ws_bytes, stream);
 }
 
 int cs_op_xattn_block_lo8(const void* h, const void* h_lo8, const void* ln_gamma, const void* ln_beta, float ln_eps, const void* wq, const void* kv,
@@ -247,8 +240,8 @@ int cs_op_ln_fold_pack(const void* w_host, const void* bias_host, const void* ga
 int cs_op_linear_ln(const void* x, int M, int K, const void* w_folded, const float* ln_s, const float* ln_b, int N, const float* row_stats, int groups,
                     float eps, void* out, int geglu, void* splitk_ws, size_t splitk_ws_bytes, void* stream) {
     IgemmArgs a{};
-    a.a0 = (const f16*)x; a.c0 = K; a.B = 1; a.Hi = M; a.Wi = 1; a.Ho = M; a.Wo = 1; a.taps = 1; a.stride = 1; a.N = N;
-    a.w = (const f16*)w_folded; a.out = (f16*)out; a.geglu = geglu;
+    linear_args(a, x, M, K, w_folded, nullptr, N, nullptr, out);
+    a.geglu = geglu;
     a.ln_stats = row_stats; a.ln_groups = groups; a.ln_eps = eps; a.ln_s = ln_s; a.ln_b = ln_b;
     a.splitk_ws = (float*)splitk_ws; a.splitk_ws_bytes = splitk_ws_bytes;
     if (!row_stats) CS_FAIL(CS_E_ARG, "linear_ln: row_stats required");

@@ -1,4 +1,4 @@
-"""Float64 references, input families, bounds and case lists for csrc/igemm.hip (every conv3x3 / conv1x1 / linear route of launch_igemm_impl) and the small-Cout
+"""Float64 references, input families, bounds and case lists for csrc/igemm.hip (every conv3x3 / conv1x1 / linear route of igemm_plan, csrc/igemm_plan.h) and the small-Cout
 conv_out kernels of csrc/misc.hip.  Plain torch on the CPU; shares no code with consolver_amd/ops.py.  Yardstick of tests/test_igemm_forms_gpu.py, pinned on the
 CPU by tests/test_igemm_ref.py.
 

@@ -7,7 +7,7 @@
 //   * every launch_* stub TOUCHES the first and last byte of each tensor the real kernel would read or write (sizes from the launch arguments), so an
 //     arena block that is too small, freed too early or placed past the end of the workspace is an ASan error, exactly as it would be a silent
 //     corruption on the GPU.
-#include "../../consolver_amd/csrc/ops.h"
+#include "../../consolver_amd/csrc/igemm_plan.h"
 #include <cstdlib>
 #include <cstring>
 
@@ -43,7 +43,12 @@ static void wr(void* p, size_t bytes) { if (p && bytes) { ((volatile unsigned ch
 static size_t esz(int dtype) { return dtype == CS_F32 ? 4 : 2; }
 
 double igemm_flops(const IgemmArgs& a) { return 2.0 * a.B * a.Ho * a.Wo * (double)a.N * a.taps * (a.c0 + a.c1); }
+// asks the real router (igemm_plan, a header): its refusals are returned, the row statistics have the layout the chosen kernel writes and the split-K scratch is
+// touched only where the plan splits
 int launch_igemm(const IgemmArgs& a, hipStream_t) {
+    IgemmPlan pl;
+    const int rc = igemm_plan(a, tune(), &pl);
+    if (rc != CS_OK || pl.route.family == FAM_NONE) return rc;
     const size_t Min = (size_t)a.B * a.Hi * a.Wi, M = (size_t)a.B * a.Ho * a.Wo, Nout = a.geglu ? a.N / 2 : a.N;
     rd(a.a0, Min * a.c0 * 2); rd(a.a1, Min * a.c1 * 2); rd(a.a0_lo, Min * a.c0 * 2); rd(a.a1_lo, Min * a.c1 * 2);
     rd(a.w, (size_t)a.N * a.taps * (a.c0 + a.c1) * 2); rd(a.bias, (size_t)a.N * 2);
@@ -53,9 +58,9 @@ int launch_igemm(const IgemmArgs& a, hipStream_t) {
     rd(a.res, M * Nout * 2); rd(a.res_lo, M * Nout * lob);
     wr(a.out, M * Nout * 2); wr(a.out_lo, M * Nout * lob);
     if (a.gn_stats) wr(a.gn_stats, (size_t)a.B * (a.Ho * a.Wo / 64) * a.N * sizeof(float));
-    if (a.row_stats) { const int G = a.N % 160 == 0 ? a.N / 160 : a.N / 64; wr(a.row_stats, M * G * 2 * sizeof(float)); *a.row_stats_groups = G; }   // (the widest layout a kernel may pick is N / 64 groups)
+    if (a.row_stats) { const int G = pl.route.row_groups ? pl.route.row_groups : 1; wr(a.row_stats, M * G * 2 * sizeof(float)); *a.row_stats_groups = G; }   // (0 groups: the statistics pass behind the kernel, one group)
     if (a.ln_stats) { rd(a.ln_stats, M * a.ln_groups * 2 * sizeof(float)); rd(a.ln_s, (size_t)a.N * 4); rd(a.ln_b, (size_t)a.N * 4); }
-    if (a.splitk_ws) wr(a.splitk_ws, a.splitk_ws_bytes);
+    if (pl.uses_splitk_ws) wr(a.splitk_ws, (size_t)pl.route.splits * M * a.N * sizeof(float));       // [splits][M][N] partial sums
     return CS_OK;
 }
 int launch_row_stats(const f16* x, const f16* x_lo, int M, int C, float* stats, hipStream_t, int lo8) { rd(x, (size_t)M * C * 2); rd(x_lo, (size_t)M * C * (lo8 ? 1 : 2)); wr(stats, (size_t)M * 8); return CS_OK; }

@@ -1,25 +1,26 @@
-"""csrc/igemm.hip route by route against float64: every conv3x3 / conv1x1 / linear launch site of launch_igemm_impl, the split-K reduce kernels, the GroupNorm and
+"""csrc/igemm.hip route by route against float64: every conv3x3 / conv1x1 / linear route of launch_igemm (decided by igemm_plan, csrc/igemm_plan.h), the split-K reduce kernels, the GroupNorm and
 row statistics the epilogues leave, and the small-Cout conv_out kernels of csrc/misc.hip.  References, input families, bounds and the case lists: tests/igemm_ref.py
 (pinned on the CPU by tests/test_igemm_ref.py).
 
 Every case
   * runs with its outputs (and statistics buffers) inside NaN-filled buffers whose margins, and every element the op must not write, are compared bit for bit;
-  * asserts with ops.igemm_last_route() that the dispatcher took the kernel the case is for (family, tile columns, variant index of the launch site's table,
-    split-K factor, who left the statistics);
+  * asserts with ops.igemm_last_route() that the dispatcher took the kernel the case is for (family, tile columns, variant as numbered by the index functions of
+    csrc/igemm_plan.h, split-K factor, who left the statistics);
   * exact family (small integers, every fp32 sum exact in any order): EVERY output element equals the reference bit for bit;
   * random family: prints RATIO = worst |out - rnd16(ref)| / bound over the elements and asserts it <= 1.0, the bound derived per element in tests/igemm_ref.py;
   * restores the knobs with ops.reset_tuning() in a finally.
 
-Route table (knobs -> what the record must say; the shapes are in tests/igemm_ref.py):
+Route table (knobs -> what the record must say; the shapes are in tests/igemm_ref.py; the variant numbers are the enums next to the named index functions of
+csrc/igemm_plan.h, which tests/test_igemm_plan.py asserts for the same cases on the CPU):
     conv_halo 0                              generic igemm_kernel<128 | 160, CONV3> (N = 640: 128 columns); split-K 2 / 4 / 8 at 16 x 16 -> 8 x 8 stride 2 with
                                              cin 128 / 256 / 512; splitk_reduce_stats_kernel when HoWo = 64, else splitk_reduce_kernel + the statistics pass
     conv_halo 2, conv_lw 0                   conv3_halo_kernel<UP, 128 | 160, 1>; conv_halo 3: <UP, 256 | 320, 2>; split over chunks 2 / 4 / 8 at cin 128 / 256 / 512
-    conv_halo 2, conv_lw 1 | 2               conv3_lw_kernel, variants[] index: 0 FAST 160, 1 plain 160, 2 upsample plain 160, 5 upsample FAST 160, 6 FAST 128, 7 plain 128,
+    conv_halo 2, conv_lw 1 | 2               conv3_lw_kernel, conv_lw_variant (ConvLwVariant): 0 FAST 160, 1 plain 160, 2 upsample plain 160, 5 upsample FAST 160, 6 FAST 128, 7 plain 128,
                                              8 upsample plain 128, 9 upsample FAST 128, 10 fast8 (8 x 8, four images per tile); N = 640 -> 160 columns
-    cs_op_conv_up_sub                        sub[] index: 0 f1 160 (16 x 16 input patches), 1 f2 160 (8 x 8), 2 f1 128
-    gemm_big 0                               igemm_kernel<128 | 160> (variant: LNM | EPI << 2 | GEGLU << 4)
-    gemm_big 2, gemm_w8 0 | 1                gemm_big_kernel<., 320> | gemm_w8_kernel, w8[] index: 0 plain, 1 GEGLU, 4 row statistics, 7 residual + lo plane in, no lo plane out
-    gemm_big 3, gemm_lw 0 | 1                gemm_big_kernel<false, 160> | gemm_lw_kernel, lwk[] index: 0 plain, 2 row statistics, 5 residual + lo plane in, no lo plane out
+    cs_op_conv_up_sub                        sub_variant (SubVariant): 0 f1 160 (16 x 16 input patches), 1 f2 160 (8 x 8), 2 f1 128
+    gemm_big 0                               igemm_kernel<128 | 160> (igemm_kernel_form / IK_VARIANT: LNM | EPI << 2 | GEGLU << 4)
+    gemm_big 2, gemm_w8 0 | 1                gemm_big_kernel<., 320> | gemm_w8_kernel, w8_variant (W8Variant): 0 plain, 1 GEGLU, 4 row statistics, 7 residual + lo plane in, no lo plane out
+    gemm_big 3, gemm_lw 0 | 1                gemm_big_kernel<false, 160> | gemm_lw_kernel, gemm_lw_variant (GemmLwVariant): 0 plain, 2 row statistics, 5 residual + lo plane in, no lo plane out
 Every row of the table was confirmed by the record on an MI355X: no listed shape took another route.  The reduce kernels: splitk_reduce_stats_kernel behind the
 HoWo = 64 split-K cases with statistics (generic, halo and loader-wave), splitk_reduce_kernel behind the others.
 
@@ -30,11 +31,11 @@ Worst RATIO seen per route family on an MI355X (0.98 = one fp16 ulp off rnd16(re
 Wall time of the module on an MI355X: 4.6 s for its 177 tests (the slowest 0.25 s).
 
 What the module found: GEGLU with N % 128 != 0 (N = 320, 960) and too few rows to fill the 320-column kernels went to the generic tiles, which counted
-160-column tiles and launched the 128-column GEGLU kernel: output columns 128 tiles_n .. N / 2 were never written.  launch_igemm_impl now sends that shape to the
+160-column tiles and launched the 128-column GEGLU kernel: output columns 128 tiles_n .. N / 2 were never written.  igemm_plan sends that shape to the
 320-column kernels and refuses it when gemm_big is 0 (test_geglu_on_each_route_that_has_it, test_refusals_leave_the_output_untouched).
 
-Launch-site entries no case reaches: variants[3] / variants[4] (the stamped conv3_lw instantiations: debug bit 16384 only); w8[2] / w8[3] / lwk[1] (the folded-LayerNorm
-consumers) and w8[5] / w8[6] / lwk[3] / lwk[4] (8-bit lo planes) belong to tests/test_ln_fold_gpu.py and tests/test_residual_x2_gpu.py.
+Variants no case reaches: LW_TRACE_FAST160 / LW_TRACE160 (the stamped conv3_lw instantiations: debug bit 16384 only); W8_LN / W8_GEGLU_LN / GLW_LN (the folded-LayerNorm
+consumers) and W8_LO8 / W8_LO8_STATS / GLW_LO8 / GLW_LO8_STATS (8-bit lo planes) belong to tests/test_ln_fold_gpu.py and tests/test_residual_x2_gpu.py.
 """
 import math
 
@@ -173,7 +174,7 @@ def test_halo_conv3(case):
 
 @pytest.mark.parametrize("case", R.LW_CASES, ids=repr)
 def test_loader_wave_conv3(case):
-    """conv3_lw_kernel: every reachable entry of variants[] by its index"""
+    """conv3_lw_kernel: every reachable ConvLwVariant by its number"""
     run_conv_case(case)
 
 
@@ -544,6 +545,22 @@ def test_refusals_leave_the_output_untouched():
             assert rc == CS_E_SHAPE and untouched(obuf) and ops.igemm_last_route().family == "none"
     finally:
         ops.reset_tuning()
+
+
+def test_empty_batch_launches_nothing_and_reports_one_row_group():
+    """B = 0 with row statistics asked for: CS_OK, no kernel and no statistics pass (the record stays at "none", nothing is written), and the layout returned is the
+    statistics pass's one group (IgemmArgs::row_stats, ops.h)"""
+    import ctypes
+    x = torch.zeros(1, 8, 8, 64, dtype=F16, device=DEV)
+    w = torch.zeros(128, 64, dtype=F16, device=DEV)
+    obuf, _ = guarded(1, 8, 8, 128)
+    sbuf, _ = guarded(64, 2, 2, dtype=F32)
+    groups = ctypes.c_int(-7)
+    rc = L.lib().cs_op_conv2d_x2(L.ptr(x), None, 64, None, None, 0, 0, 8, 8, 1, 1, 0, L.ptr(w), None, 128, None, 0, None, None, L.ptr(obuf[G:]), None,
+                                 L.ptr(sbuf[G:]), ctypes.byref(groups), None, 0, L.stream_ptr(DEV))
+    torch.cuda.synchronize()
+    assert rc == 0 and groups.value == 1 and ops.igemm_last_route().family == "none"
+    assert untouched(obuf) and untouched(sbuf)
 
 
 def test_conv_down_floors_odd_sizes_by_definition():

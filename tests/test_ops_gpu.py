@@ -647,7 +647,7 @@ def test_xattn_block_fused_kernel(B, HW, Nk, tile):
         assert all(torch.equal(x, y) for x, y in zip(a128, a64))
 
 
-XCD_GRID_CASES = [   # weight-heavy SD1.5 layers (16 x 16 / 8 x 8 levels, batch 32) where launch_igemm_impl maps the XCDs as a 2-D grid (tile_of, pn > 0)
+XCD_GRID_CASES = [   # weight-heavy SD1.5 layers (16 x 16 / 8 x 8 levels, batch 32) where igemm_plan (choose_xcd_grid) maps the XCDs as a 2-D grid (tile_of, pn > 0)
     ("conv", 32, 8, 1280, 1280), ("conv", 32, 8, 2560, 1280), ("conv", 32, 16, 1280, 1280), ("conv", 32, 16, 2560, 1280),
     ("linear", 8192, 1280, 3840, False), ("linear", 8192, 1280, 10240, True), ("linear", 8192, 5120, 1280, False), ("linear", 2048, 1280, 10240, True),
     ("linear", 2048, 1280, 1280, False),

@@ -30,7 +30,7 @@ def test_segformer_host_under_asan_ubsan(tmp_path):
         pytest.skip("hipcc not found")
     flags = ["-x", "hip", "--cuda-host-only", "--offload-arch=gfx950", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-gpu-sanitize",
              "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer", "-w", "-I" + os.path.join(ROOT, "include")]
-    srcs = [os.path.join(CSRC, s) for s in HOST_SOURCES] + [os.path.join(ROOT, "tests", "sanitize", f) for f in ("stubs.cpp", "seg_stubs.cpp", "seg_harness.cpp")]
+    srcs = [os.path.join(CSRC, s) for s in HOST_SOURCES] + [os.path.join(ROOT, "tests", "sanitize", f) for f in ("stubs.cpp", "tune_default.cpp", "seg_stubs.cpp", "seg_harness.cpp")]
     objs, procs = [], []
     for s in srcs:
         o = str(tmp_path / (os.path.basename(s) + ".o"))
